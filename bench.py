@@ -9,11 +9,13 @@ is replicated on every rank and path p is walked by rank p mod N; no collective 
 region; afterwards the whole CSR is gathered on rank 0 over RCCL.  --scaling weak: every rank holds
 its own contig of the same shape (seed 42 + rank).
 
-Next to the steady-state `value` the line carries the one-shot flow (open_ms, sample_walk_ms,
-first_pass_ms, value_cold), the same passes without sequence samples (value_unsampled) and a second
-workload whose rows do not move in lock step (secondary) and BASELINE config 5 (high_degree).
+A plain run sets up, warms up, times --steps passes and prints the headline: `value`, `ms_per_step` and what describes the
+workload.  With --full the line also carries the one-shot flow (open_ms, sample_walk_ms, first_pass_ms, value_cold), the check of
+every row against the generator, the same passes without sequence samples (value_unsampled), a second workload whose rows do not
+move in lock step (secondary), the other BASELINE configs, `roofline` and `cpu_baseline`; at N > 1 the other cut, the final gather
+and config 4 sharded.  --dump-outputs DIR writes what the last timed pass computed as DIR/<name>.npy (dump_outputs).
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Output: ONE JSON line on rank 0.
 
 `--gpus N` with N > 1 outside a torchrun launch starts the N ranks itself (a child `python -m torch.distributed.run`,
 before this process has touched a GPU) and passes their output through; under torchrun (RANK / WORLD_SIZE set) it is
@@ -63,7 +65,15 @@ def parse_args():
     ap.add_argument("--c4-size", choices=["full", "small", "medium", "tiny"], default="full",
                     help="config 4's stand-in (tools/c4_bench.py: SIZES): full = the size SURVEY 8(d) states (~42 000 walks over ~90 M nodes, labels of 1..1024 bp); "
                          "small / tiny for rehearsals")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline (see the module docstring); the --no-* options above apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed passes, write rank 0's CSR of the last one as DIR/<name>.npy (float64): the row offsets and a seeded "
+                         "sample of the node ids with their positions")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(index_path, n_paths, target_seconds):
@@ -470,6 +480,26 @@ def shard_paths(n_paths, rank, world):
     return np.arange(rank, n_paths, world, dtype=np.uint64)
 
 
+DUMP_SAMPLE = 1 << 21       # node ids written by --dump-outputs: ids + positions are 2 x 16 MB of float64
+
+
+def dump_outputs(directory, out, device, torch):
+    """--dump-outputs: the CSR an extraction returns (offsets int64[n + 1], node ids u32), as float64 arrays, exact below 2^53:
+    `offsets` whole, and the node ids at a fixed seeded sample of positions (`nodes_sample` at `nodes_sample_pos`; every position when
+    there are at most DUMP_SAMPLE).  The workload comes from --seed, so the same arguments give the same positions."""
+    from gbwt_rs_amd import dist as D
+    offsets, nodes = D.paths_tensors(out, device)
+    total = int(nodes.numel())
+    if total <= DUMP_SAMPLE:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(0).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+    picked = nodes[torch.from_numpy(pos).to(nodes.device)].to(torch.int64).cpu().numpy() & 0xFFFFFFFF
+    os.makedirs(directory, exist_ok=True)
+    for name, a in (("offsets", offsets.cpu().numpy()), ("nodes_sample_pos", pos), ("nodes_sample", picked)):
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float64))
+
+
 def timed_passes(index, ids, passes, part=0, parts=1):
     """`passes` extractions of `ids`: (walk-kernel ms, everything-on-the-stream ms) per pass from the workspace's HIP events."""
     walk, total, out = [], [], None
@@ -530,20 +560,23 @@ def main():
     s.save(index_path, as_gbz=True)  # same .gbz for the GPU path and the CPU baseline
 
     # The HIP runtime (context, code objects) is started by a throw-away open of a tiny index, so that `open_ms` below is the open
-    # of THIS index and not of the process; what a one-shot tool pays on top is reported as runtime_init_ms.
-    t0 = time.perf_counter()
-    tiny = S.Synth.chain(sites=8, haplotypes=4, alleles=2, model=model, founders=2, switch_rate=0.1, seed=1)
-    tiny_dev = G.GBWT.from_records(tiny.data(), tiny.starts(), tiny.alphabet_offset, tiny.alphabet_size, tiny.sequences, tiny.size, True, device=local_rank)
-    tiny_dev.sequences_csr(np.arange(tiny.sequences, dtype=np.uint64))
-    tiny_dev.close()
-    # ... and the runtime's path for LARGE pageable copies, which it sets up on first use (the first 60 MB host-to-device copy of a process
-    # takes 31 ms, every later one 1.1 ms: profiles/r06_upload_probe.txt; the first open of a file in a process paid 8-10 ms of it in its
-    # parse, profiles/r06_open_probe.txt): one 64 MB round trip of a throw-away buffer, counted with the runtime's start like the rest
-    scratch = torch.empty(64 << 20, dtype=torch.uint8)
-    scratch.cuda(local_rank).cpu()
-    del scratch
-    torch.cuda.synchronize()
-    runtime_init_ms = (time.perf_counter() - t0) * 1e3
+    # of THIS index and not of the process; what a one-shot tool pays on top is reported as runtime_init_ms.  (--full only: a plain
+    # run reports no one-shot figures, and its open starts the runtime.)
+    runtime_init_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        tiny = S.Synth.chain(sites=8, haplotypes=4, alleles=2, model=model, founders=2, switch_rate=0.1, seed=1)
+        tiny_dev = G.GBWT.from_records(tiny.data(), tiny.starts(), tiny.alphabet_offset, tiny.alphabet_size, tiny.sequences, tiny.size, True, device=local_rank)
+        tiny_dev.sequences_csr(np.arange(tiny.sequences, dtype=np.uint64))
+        tiny_dev.close()
+        # ... and the runtime's path for LARGE pageable copies, which it sets up on first use (the first 60 MB host-to-device copy of a process
+        # takes 31 ms, every later one 1.1 ms: profiles/r06_upload_probe.txt; the first open of a file in a process paid 8-10 ms of it in its
+        # parse, profiles/r06_open_probe.txt): one 64 MB round trip of a throw-away buffer, counted with the runtime's start like the rest
+        scratch = torch.empty(64 << 20, dtype=torch.uint8)
+        scratch.cuda(local_rank).cpu()
+        del scratch
+        torch.cuda.synchronize()
+        runtime_init_ms = (time.perf_counter() - t0) * 1e3
 
     def barrier():
         if dist is not None:
@@ -592,35 +625,38 @@ def main():
     finally:
         gc.enable()
     assert int(out.total) == steps_done and (by_parts or steps_done == expected_steps), (int(out.total), steps_done, expected_steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, torch.device("cuda", local_rank), torch)
 
-    # untimed: full-size check of the last extraction against the generator's ground truth
-    sums = index.path_sums(len(ids))
-    hashes = index.path_hashes(len(ids))
-    row_lens = np.diff(index.last_offsets(len(ids)))
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:      # (the generator's own walk of every path, in C without the interpreter lock: 5 000 x 667 k nodes)
-        truth = np.array(list(pool.map(s.path_checksum, [int(p) for p in my_paths])), dtype=np.uint64)
-    part_from = None
-    if by_parts:
-        # a row's stretches add up to the row: the per-row sums of all ranks together are the generator's, and this rank's stretch of a row
-        # is the row from where the ranks before it stopped
-        off_mine = index.last_offsets(len(ids))
-        lens = torch.from_numpy(np.diff(off_mine).astype(np.int64)).to(comm_device)
-        all_lens = [torch.zeros_like(lens) for _ in range(world)]
-        dist.all_gather(all_lens, lens)
-        part_from = sum((x.cpu().numpy() for x in all_lens[:rank]), np.zeros(len(ids), dtype=np.int64))
-        row_len = sum(x.cpu().numpy() for x in all_lens)
-        assert np.all(row_len == path_len), "the stretches of a row do not add up to its length"
-        t_sums = torch.from_numpy(sums.astype(np.int64)).to(comm_device)      # (sums mod 2^64: int64 wraps the same way)
-        dist.all_reduce(t_sums, op=dist.ReduceOp.SUM)
-        assert np.array_equal(t_sums.cpu().numpy().astype(np.uint64), truth), "extracted paths differ from the generator's ground truth"
-        for k in (0, len(ids) // 2, len(ids) - 1):
-            lo = int(part_from[k])
-            assert np.array_equal(index.copy_path(k), s.path(int(my_paths[k]))[lo:lo + int(lens[k])]), f"stretch {rank} of row {k}"
-    else:
-        assert np.array_equal(sums, truth), "extracted paths differ from the generator's ground truth"
-        for k in (0, len(ids) // 2, len(ids) - 1):
-            assert np.array_equal(index.copy_path(k), s.path(int(my_paths[k])))
+    if args.full:
+        # untimed: full-size check of the last extraction against the generator's ground truth
+        sums = index.path_sums(len(ids))
+        hashes = index.path_hashes(len(ids))
+        row_lens = np.diff(index.last_offsets(len(ids)))
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:      # (the generator's own walk of every path, in C without the interpreter lock: 5 000 x 667 k nodes)
+            truth = np.array(list(pool.map(s.path_checksum, [int(p) for p in my_paths])), dtype=np.uint64)
+        part_from = None
+        if by_parts:
+            # a row's stretches add up to the row: the per-row sums of all ranks together are the generator's, and this rank's stretch of a row
+            # is the row from where the ranks before it stopped
+            off_mine = index.last_offsets(len(ids))
+            lens = torch.from_numpy(np.diff(off_mine).astype(np.int64)).to(comm_device)
+            all_lens = [torch.zeros_like(lens) for _ in range(world)]
+            dist.all_gather(all_lens, lens)
+            part_from = sum((x.cpu().numpy() for x in all_lens[:rank]), np.zeros(len(ids), dtype=np.int64))
+            row_len = sum(x.cpu().numpy() for x in all_lens)
+            assert np.all(row_len == path_len), "the stretches of a row do not add up to its length"
+            t_sums = torch.from_numpy(sums.astype(np.int64)).to(comm_device)      # (sums mod 2^64: int64 wraps the same way)
+            dist.all_reduce(t_sums, op=dist.ReduceOp.SUM)
+            assert np.array_equal(t_sums.cpu().numpy().astype(np.uint64), truth), "extracted paths differ from the generator's ground truth"
+            for k in (0, len(ids) // 2, len(ids) - 1):
+                lo = int(part_from[k])
+                assert np.array_equal(index.copy_path(k), s.path(int(my_paths[k]))[lo:lo + int(lens[k])]), f"stretch {rank} of row {k}"
+        else:
+            assert np.array_equal(sums, truth), "extracted paths differ from the generator's ground truth"
+            for k in (0, len(ids) // 2, len(ids) - 1):
+                assert np.array_equal(index.copy_path(k), s.path(int(my_paths[k])))
 
     gather_info = None
     other_cut = None
@@ -639,7 +675,7 @@ def main():
         per_rank = torch.zeros(world, dtype=torch.float64, device=comm_device)
         dist.all_gather_into_tensor(per_rank, torch.tensor([float(np.mean(walk_ms))], dtype=torch.float64, device=comm_device))
         rank_kernel_ms = [float(x) for x in per_rank.cpu().tolist()]
-        if strong:
+        if strong and args.full:
             # ... and the SAME batch under the other cut (north_star: "the path set shards ... across the 8 GPUs" = --shard paths; the default
             # is --shard parts, every rank its stretch of every row): the same K timed passes between the same barriers
             o_parts = 1 if by_parts else world
@@ -699,9 +735,10 @@ def main():
             return box["value"]
 
         # The one exchange of the job (outside the timed region, src/bin/gbunzip.rs:421-434: the writer's mutex)
-        gather_info = bounded("final_gather", lambda: final_gather(args, index, out, s, rank, world, local_rank, backend, comm_device, by_parts, strong, n_paths, all_steps,
-                                                                      my_paths, barrier, dist, torch))
-        if not (args.no_extras or args.no_config4):
+        if args.full:
+            gather_info = bounded("final_gather", lambda: final_gather(args, index, out, s, rank, world, local_rank, backend, comm_device, by_parts, strong, n_paths,
+                                                                          all_steps, my_paths, barrier, dist, torch))
+        if args.full and not (args.no_extras or args.no_config4):
             if abandoned:
                 c4_sharded = {"error": "skipped: " + abandoned[0] + " was abandoned on this rank", "rank": rank}
             else:
@@ -712,7 +749,7 @@ def main():
     if rank == 0:
         # cpu_baseline is reported at N = 1 only (rank 0's host cores)
         cpu, parity_checked = None, 0
-        if not (args.no_cpu_baseline or world > 1):
+        if args.full and not (args.no_cpu_baseline or world > 1):
             # ... and every run of the baseline is a parity run at headline size: the oracle's walk of the sampled paths against the rows of
             # the last timed extraction (length, sum of node ids, order-dependent hash of every path: gbwt_hip_path_sums / _hashes)
             cpu, o_paths, o_lens, o_sums, o_hashes = cpu_baseline(index_path, n_paths, args.cpu_seconds)
@@ -722,10 +759,9 @@ def main():
             assert np.array_equal(hashes[o_paths], o_hashes), "order-dependent hashes of the extracted paths differ from the oracle's"
             parity_checked = int(len(o_paths))
             cpu["parity_checked_paths"] = parity_checked
-        b_per_step, sampled_steps = algorithmic_bytes(index_path, n_paths, args.bytes_sample)
         walk_avg_ms = float(np.mean(walk_ms))
         extras = {}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # (a) the same passes WITHOUT sequence samples: one walker per end of every row, the "one lane per active path" shape
             saved = {k: os.environ.get(k) for k in ("GBWT_HIP_SAMPLE_INTERVAL", "GBWT_HIP_VMM")}
             os.environ["GBWT_HIP_SAMPLE_INTERVAL"] = "0"
@@ -791,22 +827,6 @@ def main():
                         got = {"config4": got}
                     for name in names:
                         extras[name] = config_roofline(got[name], name, c4_definition)
-        # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes of this same command
-        # (tools/measure_round.sh -> profiles/*_hbm_traffic.json).  It is quoted only when those passes ran THIS build with
-        # THESE knobs on THIS workload (fingerprint of the kernel sources + GBWT_HIP_* environment); a profile of another
-        # build says nothing about this run.
-        fingerprint = source_fingerprint()
-        workload_key = f"sites={args.sites} haplotypes={args.haplotypes} model={args.model} seed={args.seed}"
-        traffic, traffic_source = lookup_traffic(workload_key) if world == 1 else (None, "N > 1: no profile")
-        seconds = walk_avg_ms * 1e-3
-        # What this kernel must move per LF-step whatever happens in the caches: the emitted u32 node id.  (The index it
-        # reads -- two-step blocks and descriptors -- is shared by the 64+ steps of a block and mostly survives in L2 /
-        # MALL; those bytes are in `traffic`.)  SURVEY 8d's H + P + 4 is the byte count of the REFERENCE's scan of every
-        # record up to the offset; rank blocks answer a step without that scan (the run-length decode happens once, at open:
-        # open.upload_ms), so that figure is reported next to it as `survey_8d` and not as the fraction of the roofline.
-        out_bytes = 4.0 * steps_done
-        achieved = out_bytes / seconds / 1e9
-        reference_rate = b_per_step * steps_done / seconds / 1e9
         result = {
             "metric": "LF-steps/sec (batched path extract)",
             "value": all_steps * args.steps / elapsed,
@@ -820,18 +840,7 @@ def main():
             "vs_baseline": None,
             "dtype": "u32",   # device arithmetic: record indices, offsets and node ids are 32-bit (the C ABI widens to u64 where the reference has usize)
             "data": "synthetic",
-            # paths of the last timed extraction whose length, node sum and order-dependent hash equal the CPU oracle's walk (the cpu_baseline leg)
-            "parity_checked_paths": parity_checked,
-            # the one-shot flow (load, extract once) next to the steady state `value` is quoted on
-            # LF-steps of all ranks / (open + first pass) of the slowest rank; value_cold_incl_init also counts what starting the HIP runtime cost
-            "value_cold": all_steps / (cold_ms * 1e-3),
-            "value_cold_incl_init": all_steps / ((cold_ms + runtime_init_ms) * 1e-3),
             "kernel_ms_per_rank": rank_kernel_ms,
-            # N > 1: one pass + the gather of its rows on rank 0 (the only collective of the job, outside `value`'s timed region)
-            "value_incl_gather": None if not (gather_info and "ms" in gather_info) else all_steps / ((elapsed / args.steps) + gather_info["ms"] * 1e-3),
-            "open_ms": open_ms,
-            "sample_walk_ms": open_times["sample_ms"],
-            "first_pass_ms": first_pass_ms,
             "config": {
                 "workload": (f"bubble-chain GBZ, {args.haplotypes} paths x {3 * args.sites} nodes ({args.sites} sites, {args.model}, seed {args.seed}), "
                              f"all forward sequences -> device CSR; index replicated, " +
@@ -848,64 +857,96 @@ def main():
                             else "one contig (index + path set) per rank, no data-path collective",
                 "generator_seconds": round(gen_s, 1),
             },
-            "open": {
-                "open_ms": open_ms, "flags": "GBWT_HIP_OPEN_EXTRACT" if open_flags == G.OPEN_EXTRACT else "GBWT_HIP_OPEN_ALL",
-                "parse_ms": open_times["parse_ms"], "upload_ms": open_times["upload_ms"], "sample_ms": open_times["sample_ms"],
-                "index_device_bytes": int(index.memory_usage()["index_device_bytes"]),
-                "samples": int(open_times["samples"]), "checkpoint_sampling": bool(open_times["checkpoint_sampling"]),
-                "checkpoint_walkers": int(open_times["checkpoint_walkers"]), "checkpoint_orphans": int(open_times["checkpoint_orphans"]),
-                "first_pass_ms": first_pass_ms, "first_pass_kernel_ms": first_walk_ms, "runtime_init_ms": runtime_init_ms,
-                "note": "open_ms = GBZ.load of the .gbz (file read + parse, upload, rank blocks and descriptors, sequence samples) with the HIP "
-                        "runtime already started (runtime_init_ms: what starting it cost, once per process -- context, code objects, a tiny open, and "
-                        "one 64 MB pageable copy each way, which sets up the runtime's staging for large copies); first_pass_ms includes the "
-                        "allocation of the rows; value_cold = LF-steps / (open_ms + first_pass_ms)",
-            },
-            "roofline": {
-                "bound": "hbm",
-                "definition": "emitted bytes: the u32 node id every LF-step writes (4 B per step) / kernel time -- a STORE roofline; SURVEY 8(d)'s per-step "
-                              "figure (what the reference's scan reads) is priced in `cold` (with the open, where the run-length decode happens) and in `survey_8d`",
-                "kernel": "k_walk_direct",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "algorithmic_bytes_per_step": 4.0,
-                "algorithmic_note": "bytes this kernel must move per LF-step: the emitted u32 node id, written once "
-                                    "(index reads are shared by all steps of a rank block and show up in `traffic`)",
-                "traffic": traffic,
-                "traffic_frac": None if traffic is None else traffic / seconds / 1e9 / HBM_PEAK_GBS,
-                "traffic_source": traffic_source,
-                "survey_8d": {
-                    "bytes_per_step": b_per_step,
-                    "achieved": reference_rate,
-                    "frac": reference_rate / HBM_PEAK_GBS,
-                    "note": "SURVEY 8d's definition: H + P + 4 = record header + run stream scanned up to the offset + emitted id per step, i.e. what "
-                            "an implementation with the reference's access pattern would read to keep this pace.  Above the peak because the "
-                            "run-length decode is done once, at open (rank blocks, open.upload_ms), and the timed step is a popcount on a "
-                            "16-byte packed half-block -- an algorithmic gain, not a fraction of the roofline",
-                    "sample": f"exact over {sampled_steps} LF-steps of {min(args.bytes_sample, n_paths)} paths, scaled to {steps_done}",
-                },
-                "cold": {
-                    "bytes": b_per_step * all_steps, "ms": cold_ms, "achieved": b_per_step * all_steps / (cold_ms * 1e-3) / 1e9,
-                    "frac": b_per_step * all_steps / (cold_ms * 1e-3) / 1e9 / (HBM_PEAK_GBS * world),
-                    "note": "SURVEY 8(d)'s algorithmic bytes (H + P + 4 per step) / (open_ms + first_pass_ms) / peak: the one figure that contains ALL the work "
-                            "8(d) prices -- the run-length decode into rank blocks and the sampling walk at open, then one extraction",
-                },
-                "kernel_ms": walk_avg_ms,
-                "extract_ms": float(np.mean(total_ms)),
-                "source_fingerprint": fingerprint,
-            },
         }
-        result.update(extras)
         if world > 1:
             result["shard"] = args.shard if strong else None
-            result["other_cut"] = other_cut          # the same batch under the other partition, same K passes: both on every N > 1 line
-            if c4_sharded is not None:
-                result["config4"] = c4_sharded       # BASELINE config 4 as named: sharded over the N GPUs, RCCL gather of the text
-        if cpu is not None:
-            result["cpu_baseline"] = cpu
-        if gather_info is not None:
-            result["config"]["final_gather"] = gather_info
+        if args.full:
+            b_per_step, sampled_steps = algorithmic_bytes(index_path, n_paths, args.bytes_sample)
+            # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes of this same command
+            # (tools/measure_round.sh -> profiles/*_hbm_traffic.json).  It is quoted only when those passes ran THIS build with
+            # THESE knobs on THIS workload (fingerprint of the kernel sources + GBWT_HIP_* environment); a profile of another
+            # build says nothing about this run.
+            fingerprint = source_fingerprint()
+            workload_key = f"sites={args.sites} haplotypes={args.haplotypes} model={args.model} seed={args.seed}"
+            traffic, traffic_source = lookup_traffic(workload_key) if world == 1 else (None, "N > 1: no profile")
+            seconds = walk_avg_ms * 1e-3
+            # What this kernel must move per LF-step whatever happens in the caches: the emitted u32 node id.  (The index it
+            # reads -- two-step blocks and descriptors -- is shared by the 64+ steps of a block and mostly survives in L2 /
+            # MALL; those bytes are in `traffic`.)  SURVEY 8d's H + P + 4 is the byte count of the REFERENCE's scan of every
+            # record up to the offset; rank blocks answer a step without that scan (the run-length decode happens once, at open:
+            # open.upload_ms), so that figure is reported next to it as `survey_8d` and not as the fraction of the roofline.
+            out_bytes = 4.0 * steps_done
+            achieved = out_bytes / seconds / 1e9
+            reference_rate = b_per_step * steps_done / seconds / 1e9
+            result.update({
+                # paths of the last timed extraction whose length, node sum and order-dependent hash equal the CPU oracle's walk (the cpu_baseline leg)
+                "parity_checked_paths": parity_checked,
+                # the one-shot flow (load, extract once) next to the steady state `value` is quoted on
+                # LF-steps of all ranks / (open + first pass) of the slowest rank; value_cold_incl_init also counts what starting the HIP runtime cost
+                "value_cold": all_steps / (cold_ms * 1e-3),
+                "value_cold_incl_init": all_steps / ((cold_ms + runtime_init_ms) * 1e-3),
+                # N > 1: one pass + the gather of its rows on rank 0 (the only collective of the job, outside `value`'s timed region)
+                "value_incl_gather": None if not (gather_info and "ms" in gather_info) else all_steps / ((elapsed / args.steps) + gather_info["ms"] * 1e-3),
+                "open_ms": open_ms,
+                "sample_walk_ms": open_times["sample_ms"],
+                "first_pass_ms": first_pass_ms,
+                "open": {
+                    "open_ms": open_ms, "flags": "GBWT_HIP_OPEN_EXTRACT" if open_flags == G.OPEN_EXTRACT else "GBWT_HIP_OPEN_ALL",
+                    "parse_ms": open_times["parse_ms"], "upload_ms": open_times["upload_ms"], "sample_ms": open_times["sample_ms"],
+                    "index_device_bytes": int(index.memory_usage()["index_device_bytes"]),
+                    "samples": int(open_times["samples"]), "checkpoint_sampling": bool(open_times["checkpoint_sampling"]),
+                    "checkpoint_walkers": int(open_times["checkpoint_walkers"]), "checkpoint_orphans": int(open_times["checkpoint_orphans"]),
+                    "first_pass_ms": first_pass_ms, "first_pass_kernel_ms": first_walk_ms, "runtime_init_ms": runtime_init_ms,
+                    "note": "open_ms = GBZ.load of the .gbz (file read + parse, upload, rank blocks and descriptors, sequence samples) with the HIP "
+                            "runtime already started (runtime_init_ms: what starting it cost, once per process -- context, code objects, a tiny open, and "
+                            "one 64 MB pageable copy each way, which sets up the runtime's staging for large copies); first_pass_ms includes the "
+                            "allocation of the rows; value_cold = LF-steps / (open_ms + first_pass_ms)",
+                },
+                "roofline": {
+                    "bound": "hbm",
+                    "definition": "emitted bytes: the u32 node id every LF-step writes (4 B per step) / kernel time -- a STORE roofline; SURVEY 8(d)'s per-step "
+                                  "figure (what the reference's scan reads) is priced in `cold` (with the open, where the run-length decode happens) and in `survey_8d`",
+                    "kernel": "k_walk_direct",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "algorithmic_bytes_per_step": 4.0,
+                    "algorithmic_note": "bytes this kernel must move per LF-step: the emitted u32 node id, written once "
+                                        "(index reads are shared by all steps of a rank block and show up in `traffic`)",
+                    "traffic": traffic,
+                    "traffic_frac": None if traffic is None else traffic / seconds / 1e9 / HBM_PEAK_GBS,
+                    "traffic_source": traffic_source,
+                    "survey_8d": {
+                        "bytes_per_step": b_per_step,
+                        "achieved": reference_rate,
+                        "frac": reference_rate / HBM_PEAK_GBS,
+                        "note": "SURVEY 8d's definition: H + P + 4 = record header + run stream scanned up to the offset + emitted id per step, i.e. what "
+                                "an implementation with the reference's access pattern would read to keep this pace.  Above the peak because the "
+                                "run-length decode is done once, at open (rank blocks, open.upload_ms), and the timed step is a popcount on a "
+                                "16-byte packed half-block -- an algorithmic gain, not a fraction of the roofline",
+                        "sample": f"exact over {sampled_steps} LF-steps of {min(args.bytes_sample, n_paths)} paths, scaled to {steps_done}",
+                    },
+                    "cold": {
+                        "bytes": b_per_step * all_steps, "ms": cold_ms, "achieved": b_per_step * all_steps / (cold_ms * 1e-3) / 1e9,
+                        "frac": b_per_step * all_steps / (cold_ms * 1e-3) / 1e9 / (HBM_PEAK_GBS * world),
+                        "note": "SURVEY 8(d)'s algorithmic bytes (H + P + 4 per step) / (open_ms + first_pass_ms) / peak: the one figure that contains ALL the work "
+                                "8(d) prices -- the run-length decode into rank blocks and the sampling walk at open, then one extraction",
+                    },
+                    "kernel_ms": walk_avg_ms,
+                    "extract_ms": float(np.mean(total_ms)),
+                    "source_fingerprint": fingerprint,
+                },
+            })
+            result.update(extras)
+            if world > 1:
+                result["other_cut"] = other_cut          # the same batch under the other partition, same K passes: both on every N > 1 line
+                if c4_sharded is not None:
+                    result["config4"] = c4_sharded       # BASELINE config 4 as named: sharded over the N GPUs, RCCL gather of the text
+            if cpu is not None:
+                result["cpu_baseline"] = cpu
+            if gather_info is not None:
+                result["config"]["final_gather"] = gather_info
         if abandoned:
             result["abandoned"] = abandoned
         if failed_checks:

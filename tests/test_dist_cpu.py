@@ -273,7 +273,7 @@ def test_config4_partition_over_gloo(tmp_path, world):
     assert (tmp_path / "ok").exists()
 
 
-def _rehearse_bench(world, extra_env=None, timeout=420):
+def _rehearse_bench(world, extra_env=None, timeout=420, bench_args=("--full",)):
     """tests/bench_rehearsal.py under torch.distributed.run, `world` gloo ranks on CPU: (exit code, the JSON lines on stdout, stderr)."""
     import json
     import subprocess
@@ -283,7 +283,7 @@ def _rehearse_bench(world, extra_env=None, timeout=420):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(root, "tests", "bench_rehearsal.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--sites", "300", "--haplotypes", "24", "--c4-size", "tiny"]
+           os.path.join(root, "tests", "bench_rehearsal.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--sites", "300", "--haplotypes", "24", "--c4-size", "tiny", *bench_args]
     done = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     lines = [json.loads(x) for x in done.stdout.splitlines() if x.startswith("{")]
     return done.returncode, lines, done.stderr
@@ -347,3 +347,26 @@ def test_bench_abandons_a_step_that_hangs():
     line = lines[0]
     assert line["abandoned"] == ["final_gather"] and "abandoned" in line["config"]["final_gather"]["error"] and "skipped" in line["config4"]["error"]
     assert line["value"] > 0 and line["other_cut"]["value"] > 0 and line["n_gpus"] == 2 and line["value_incl_gather"] is None
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_plain_bench_prints_the_headline_and_dumps_outputs(world, tmp_path):
+    """bench.py without --full: the headline alone (none of what --full adds), and --dump-outputs writes the CSR of the last timed pass
+    (rank 0's stretches of the rows at N > 1) -- at this size every node id, which at N = 1 are the generator's paths."""
+    from gbwt_rs_amd import synth as S
+    rc, lines, err = _rehearse_bench(world, bench_args=("--dump-outputs", str(tmp_path)))
+    assert rc == 0 and len(lines) == 1, err[-3000:]
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "kernel_ms_per_rank", "config"):
+        assert key in line, key
+    assert line["steps"] == 2 and line["n_gpus"] == world and line["ms_per_step"] > 0 and line["value"] > 0
+    for key in ("roofline", "cpu_baseline", "value_cold", "open", "value_unsampled", "secondary", "other_cut", "config4", "value_incl_gather"):
+        assert key not in line, key
+    assert "final_gather" not in line["config"]
+    offsets, pos, nodes = (np.load(tmp_path / f"{name}.npy") for name in ("offsets", "nodes_sample_pos", "nodes_sample"))
+    assert offsets.dtype == pos.dtype == nodes.dtype == np.float64
+    assert len(offsets) == 24 + 1 and offsets[0] == 0 and np.array_equal(pos, np.arange(offsets[-1]))
+    if world == 1:
+        s = S.Synth.chain(sites=300, haplotypes=24, alleles=2, model=S.MOSAIC, founders=32, switch_rate=2e-3, seed=42)
+        for k in range(24):
+            assert np.array_equal(nodes[int(offsets[k]):int(offsets[k + 1])], s.path(k)), k

@@ -3,4 +3,4 @@ timeout 1500 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "parts_of
 timeout 900 python -m pytest tests/test_gpu_dist.py -m gpu -x -q > $O/tests2.log 2>&1; tail -5 $O/tests2.log
 timeout 600 python tools/slab_probe.py 2>&1 | grep -v amdgpu
 export BENCH_DIST_BACKEND=gloo BENCH_SHARE_GPU=1
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 > $O/bench2.log 2>&1; tail -3 $O/bench2.log | cut -c1-1500
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 > $O/bench2.log 2>&1; tail -3 $O/bench2.log | cut -c1-1500

@@ -9,7 +9,7 @@ run GBWT_HIP_ALIGN_SEGMENTS=0
 run GBWT_HIP_ALIGN_SEGMENTS=1 GBWT_HIP_SAMPLE_INTERVAL=1024
 run GBWT_HIP_ALIGN_SEGMENTS=0 GBWT_HIP_SAMPLE_INTERVAL=1024
 for A in 1 0 1 0; do
-GBWT_HIP_ALIGN_SEGMENTS=$A timeout 600 python bench.py --no-cpu-baseline --no-extras --steps 30 --warmup 10 2>/dev/null | python -c "
+GBWT_HIP_ALIGN_SEGMENTS=$A timeout 600 python bench.py --full --no-cpu-baseline --no-extras --steps 30 --warmup 10 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('align $A headline', j['value'], j['roofline']['kernel_ms'])"
 done

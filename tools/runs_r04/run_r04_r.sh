@@ -1,5 +1,5 @@
 R=$GRAFT_REPO_ROOT; cd $R
-run() { env "$@" timeout 600 python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | python -c "
+run() { env "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('$*', 'kernel_ms', round(j['roofline']['kernel_ms'],3), 'value', round(j['value']/1e9,1))" 2>/dev/null || echo "$* failed (wrong output by design?)"; }
 run A=1

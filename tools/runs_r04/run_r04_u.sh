@@ -2,7 +2,7 @@ R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/r04_u; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_parity.py -m gpu -x -q > $O/tests.log 2>&1; tail -3 $O/tests.log
 for L in new old new old; do
 if [ $L = old ]; then export GBWT_HIP_LIB=$R/tools/probe_csrc/libgbwt_hip.so; else unset GBWT_HIP_LIB; fi
-timeout 600 python bench.py --no-cpu-baseline --no-extras --steps 30 --warmup 10 2>/dev/null | python -c "
+timeout 600 python bench.py --full --no-cpu-baseline --no-extras --steps 30 --warmup 10 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('$L headline', j['value'], j['roofline']['kernel_ms'])"
 done

@@ -5,4 +5,4 @@ unset GBWT_HIP_SAMPLE_INTERVAL GBWT_HIP_SAMPLE_STRIDE
 timeout 600 python tools/shard_probe.py 2>&1 | grep -v amdgpu
 GBWT_HIP_SAMPLE_COARSE=1 timeout 600 python tools/shard_probe.py 2>&1 | grep -v amdgpu
 timeout 600 python tools/shard_probe.py 2>&1 | grep -v amdgpu
-GBWT_HIP_TRACE_OPEN=1 timeout 600 python bench.py --steps 10 --warmup 3 --no-config4 --no-search 2>&1 | grep -v amdgpu | tail -60
+GBWT_HIP_TRACE_OPEN=1 timeout 600 python bench.py --full --steps 10 --warmup 3 --no-config4 --no-search 2>&1 | grep -v amdgpu | tail -60
