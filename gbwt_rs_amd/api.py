@@ -10,6 +10,8 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBWT.sequences_csr(ids)    the batched form of sequence(): CSR arrays
   GBWT.find / extend / bd_find / extend_forward / extend_backward     src/gbwt.rs:269-367
   GBZ.path(path_id, orientation)   GBZ::path        src/gbz.rs:461-466
+  GBZ.node_sequence(node_id)       GBZ::sequence    src/gbz.rs:292-298   (None for a node that does not exist)
+  GBZ.path_sequences(ids, o)       gbz-extract's extract_sequence, src/bin/gbz-extract.rs:173-189 (bases of paths)
 
 Every call goes through the C ABI of libgbwt_hip.so (hand-written HIP); "not found" is reported as
 None / a False entry of the validity mask, never as an exception.
@@ -455,6 +457,73 @@ class GBZ(GBWT):
         """[(segment id, orientation), ...] of one path (GBZ::segment_path(path_id, orientation))."""
         _, tokens = self.segment_paths([2 * path_id + (1 if orientation else 0)])
         return [(int(t) >> 1, int(t) & 1) for t in tokens]
+
+    @staticmethod
+    def _endmarker(endmarker):
+        if endmarker is None:
+            return -1
+        if isinstance(endmarker, (bytes, bytearray)):
+            if len(endmarker) != 1:
+                raise ValueError("endmarker must be one byte")
+            return endmarker[0]
+        e = int(endmarker)
+        if not 0 <= e <= 255:
+            raise ValueError("endmarker must be None or a byte value 0..255")
+        return e
+
+    def path_sequences(self, path_ids, orientation=FORWARD, endmarker=None, out=None):
+        """The bases of every path (gbz-extract's extract_sequence, src/bin/gbz-extract.rs:173-189): labels joined along GBZ::path(id,
+        orientation), reverse-oriented ones reverse-complemented, `endmarker` (None or a byte value) behind every row.  Returns (offsets[n + 1],
+        bases): bytes, or a view of `out` -- a writable C-contiguous uint8 array, used when it is large enough.  A path id without such a
+        sequence gives an empty row without endmarker."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        em, rev = self._endmarker(endmarker), 1 if orientation else 0
+        if out is not None:
+            if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous or not out.flags.writeable:
+                raise TypeError("out must be a writable C-contiguous 1-d numpy uint8 array")
+        offsets = np.zeros(ids.size + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_path_sequences(self._h, self._ws, _ptr(ids), ids.size, rev, em, None, _ptr(offsets), 0, C.byref(total)))
+        if out is not None and out.size >= total.value:
+            check(self._L.gbwt_hip_path_sequences(self._h, self._ws, _ptr(ids), ids.size, rev, em, _ptr(out), None, out.size, C.byref(total)))
+            return offsets, out[: total.value]
+        buf = np.empty(max(1, total.value), dtype=np.uint8)
+        check(self._L.gbwt_hip_path_sequences(self._h, self._ws, _ptr(ids), ids.size, rev, em, buf.ctypes.data, None, buf.size, C.byref(total)))
+        return offsets, buf[: total.value].tobytes()
+
+    def path_sequences_device(self, path_ids, orientation=FORWARD, endmarker=None):
+        """The same bases left in HBM: a Lines struct (d_text, d_line_offsets[n + 1], total, n), valid until the next request for bases on
+        this workspace."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        out = Lines()
+        check(self._L.gbwt_hip_path_sequences_device(self._h, self._ws, _ptr(ids), ids.size, 1 if orientation else 0, self._endmarker(endmarker), C.byref(out)))
+        return out
+
+    def last_sequences_ms(self):
+        """(walk ms, sizing ms, bases kernel ms) of the last path_sequences / path_sequences_device request (HIP events)."""
+        walk, sizes, bases = C.c_float(0), C.c_float(0), C.c_float(0)
+        check(self._L.gbwt_hip_last_sequences_ms(self._ws, C.byref(walk), C.byref(sizes), C.byref(bases)))
+        return walk.value, sizes.value, bases.value
+
+    def node_sequence(self, node_id):
+        """GBZ::sequence(node_id) (src/gbz.rs:292-298): the label as bytes, or None for a node that does not exist."""
+        length, found = C.c_uint64(0), C.c_uint8(0)
+        check(self._L.gbwt_hip_node_sequence(self._h, int(node_id), None, 0, C.byref(length), C.byref(found)))
+        if not found.value:
+            return None
+        buf = C.create_string_buffer(max(1, length.value))
+        check(self._L.gbwt_hip_node_sequence(self._h, int(node_id), buf, length.value, C.byref(length), C.byref(found)))
+        return buf.raw[: length.value]
+
+    def write_sequences(self, path, path_ids=None, endmarker=0):
+        """The files `gbz-extract -o path` writes (src/bin/gbz-extract.rs:266-294): the forward bases of the paths (None = all) with an
+        endmarker behind each (None: none), and `path`.names."""
+        ids = None if path_ids is None else np.ascontiguousarray(path_ids, dtype=np.uint64)
+        n = 0 if ids is None else ids.size
+        if ids is not None and ids.size == 0:
+            ids = np.zeros(1, dtype=np.uint64)             # (an empty list is not NULL = all paths)
+        ptr = None if ids is None else ids.ctypes.data
+        check(self._L.gbwt_hip_write_sequences(self._h, self._ws, os.fsencode(path), ptr, n, self._endmarker(endmarker)))
 
     def path_lines_device(self, path_ids, mode):
         """The same lines left in HBM: a Lines struct (device pointers to the text and to the n + 1 line offsets)."""

@@ -207,6 +207,12 @@ struct HostCopier {
 #define GBWT_HIP_GUARD_BEGIN try {
 #define GBWT_HIP_GUARD_END } catch (...) { return gbwt_hip::status_of_current_exception(); }
 
+// gfa.hip: the chunk plan of the line formatter (chunks of GFA_LINE_CHUNK positions per row) for other passes over a batch of rows, and
+// GBZ::has_node (src/gbz.rs:286-289) on the host image (makes the host's records on first use: HostIndex::ensure_records)
+void launch_chunk_plan(const uint64_t *d_offsets, uint64_t n, uint64_t chunks_cap, uint64_t *d_chunk_counts, uint64_t *d_chunk_first, uint32_t *d_chunk_path, void *d_temp,
+                       size_t temp_bytes, hipStream_t s);
+bool node_exists(const HostIndex &h, uint64_t node_id);
+
 // The full-width two-step blocks of a handle, built on first need, and a copy of its DeviceIndex with them put in (capi_open.hip)
 const uint4 *ensure_cblocks(const gbwt_hip_index *index);
 DeviceIndex with_cblocks(const gbwt_hip_index *ix);
@@ -245,6 +251,13 @@ struct gbwt_hip_index {
     gbwt_hip::DeviceBuffer lc_chunk_first, lc_text, lc_path;    // u64[paths + 1]: first chunk of every path; u64 per chunk: W-token bytes of the path in front of it; u64[2] per path: {W-token bytes, summed label lengths}
     int lc_state = 0;                                             // 1 = filled at open, -1 = not for this index (written before the handle is handed out)
     std::vector<uint32_t> host_seq_len;   // host copy of seq_len (empty when the lengths are not known): sizes byte-bounded batches of a whole-file write
+    // NODE LABELS IN HBM, made by the first request for bases (sequences.hip: ensure_labels), never by an open: the bytes of every potential
+    // node's label (+ 64 zero bytes, so that the aligned dword loads of the bases kernel may read past the last one) and u64 offsets[nodes + 1].
+    // One upload per handle whichever thread asks first (a mutex and a flag; the flag alone is read by gbwt_hip_memory_usage).
+    mutable std::mutex labels_lock;
+    mutable std::atomic<bool> labels_made{false};
+    mutable gbwt_hip::DeviceBuffer label_bytes, label_off;
+    mutable uint64_t max_label_len = 0;
     gbwt_hip::DeviceIndex dev{};
     // The full-width two-step blocks (cblocks, as large as gblocks: 1.7 GB on the headline index) are only read by the loops for records
     // whose counts do not fit the packed half-blocks, by the pool-output kernel and by the serial walks at open: built at open when one of
@@ -322,12 +335,21 @@ struct gbwt_hip_workspace {
     std::vector<uint64_t> extract_key, lines_key;
     std::vector<uint8_t> follow_key;
     int follow_backward = 0, lines_mode = 0, lines_slot = 0;
+    // Bases of paths (sequences.hip): text and row offsets of the last gbwt_hip_path_sequences* request (seq_text2: the second text buffer of a
+    // pipelined whole-file write), the request they answer, and events around its sizing (sev[0] .. sev[1]) and its bases kernel (sev[1] .. sev[2]).
+    gbwt_hip::DeviceBuffer seq_text, seq_text2, seq_offsets;
+    bool seq_cached = false, seq_timed = false;
+    std::vector<uint64_t> seq_key;
+    int seq_reverse = 0, seq_endmarker = -1, seq_slot = 0;
+    uint64_t seq_total = 0;
+    hipEvent_t sev[3] = {nullptr, nullptr, nullptr};
     gbwt_hip::HostCopier copier;      // pinned staging of the large device-to-host copies
     uint64_t follow_total = 0, lines_total = 0;
     ~gbwt_hip_workspace() {
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         for (auto &e : qev) if (e) (void)hipEventDestroy(e);
         for (auto &e : gev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : sev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (pinned_words) (void)hipHostFree(pinned_words);
     }

@@ -814,6 +814,8 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
                                    &ix.line_prefix_off[0], &ix.line_prefix_off[1], &ix.line_prefix_off[2], &ix.line_fragment, &ix.lc_chunk_first, &ix.lc_text, &ix.lc_path});
     // (the full-width two-step blocks: at open, or by the first request that needs them -- the atomic says when they are there)
     if (ix.dev.cblocks != nullptr || ix.lazy_cblocks.load(std::memory_order_acquire) != nullptr) out->index_device_bytes += ix.cblocks.bytes;
+    // (the node labels: by the first request for bases -- the flag says when they are there)
+    if (ix.labels_made.load(std::memory_order_acquire)) out->index_device_bytes += ix.label_bytes.bytes + ix.label_off.bytes;
     const HostIndex &h = ix.host;
     out->index_host_bytes = (h.records_made() ? h.data.size() + h.starts.size() * sizeof(uint64_t) : 0) + h.da_samples.size() * sizeof(uint64_t) + h.path_names.size() * sizeof(PathName) +
                             h.sample_names.bytes.size() + h.contig_names.bytes.size() + h.sequences_labels.bytes.size() + h.sequences_labels.offsets.size() * sizeof(uint64_t) +
@@ -823,10 +825,10 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
         out->workspace_device_bytes = sum({&ws->seq_ids, &ws->lengths, &ws->offsets, &ws->head, &ws->pool, &ws->next, &ws->counters, &ws->nodes, &ws->scan_temp,
                                            &ws->order_keys, &ws->order_rows, &ws->order_counts, &ws->order_level, &ws->order_temp, &ws->in_a, &ws->in_b, &ws->out_a,
                                            &ws->out_valid, &ws->follow_off, &ws->gfa_a, &ws->gfa_b, &ws->gfa_c, &ws->gfa_text, &ws->gfa_text2, &ws->gfa_valid, &ws->gfa_chunk_first,
-                                           &ws->gfa_chunks, &ws->gfa_plan});
+                                           &ws->gfa_chunks, &ws->gfa_plan, &ws->seq_text, &ws->seq_text2, &ws->seq_offsets});
         out->rows_bytes = ws->nodes.bytes;
         out->rows_chunks = ws->nodes.chunks.size();
-        out->text_bytes = ws->gfa_text.bytes + ws->gfa_text2.bytes;
+        out->text_bytes = ws->gfa_text.bytes + ws->gfa_text2.bytes + ws->seq_text.bytes + ws->seq_text2.bytes;
     }
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END

@@ -30,6 +30,7 @@
 #include <thread>
 #include <vector>
 
+#include "batch_writer.hpp"
 #include "capi_internal.hpp"
 #include "gfa_tokens.hpp"
 
@@ -667,6 +668,18 @@ void upload_label_lengths(gbwt_hip_index &ix) {
 }  // namespace gbwt_hip
 
 namespace gbwt_hip {
+// The chunk plan of a batch of rows for the bases of gbwt_hip_path_sequences* (sequences.hip): the same chunks of GFA_LINE_CHUNK positions the
+// line formatter works in -- first chunk of every row (d_chunk_first[n + 1], d_chunk_counts[n] scratch) and the row of every chunk (d_chunk_path[chunks_cap]).
+void launch_chunk_plan(const uint64_t *d_offsets, uint64_t n, uint64_t chunks_cap, uint64_t *d_chunk_counts, uint64_t *d_chunk_first, uint32_t *d_chunk_path, void *d_temp,
+                       size_t temp_bytes, hipStream_t s) {
+    hipLaunchKernelGGL(k_chunk_counts, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, d_offsets, n, d_chunk_counts);
+    launch_scan(d_chunk_counts, d_chunk_first, n, d_temp, temp_bytes, s);
+    hipLaunchKernelGGL(k_chunk_paths, dim3(static_cast<unsigned>((chunks_cap + 255) / 256)), dim3(256), 0, s, d_chunk_first, n, chunks_cap, d_chunk_path);
+}
+bool node_exists(const HostIndex &h, uint64_t node_id) { return host_has_node(h, node_id); }
+}  // namespace gbwt_hip
+
+namespace gbwt_hip {
 void mask_label_lengths(gbwt_hip_index &ix) {
     if (!ix.host.is_gbz || ix.label_len.ptr == nullptr) return;
     launch_mask_label_lengths(ix.dev, ix.label_len.as<uint32_t>(), ix.host.sequences_labels.size(), nullptr);
@@ -909,21 +922,6 @@ static gbwt_hip_status path_lines_impl(const gbwt_hip_index *ix, gbwt_hip_worksp
 
 namespace {
 
-// A file written at positions: every producer knows (or is told, in order) where its bytes go, so several threads write at once --
-// one thread moved config 4's 4.5 GB to /dev/shm at 2.4 GB/s, most of it spent in the page cache's per-page work.
-struct PositionalFile {
-    int fd = -1;
-    std::atomic<int> failed{0};
-    ~PositionalFile() { if (fd >= 0) ::close(fd); }
-    bool write_at(const char *data, size_t bytes, uint64_t at) {
-        while (bytes != 0) {
-            const ssize_t w = ::pwrite(fd, data, bytes, static_cast<off_t>(at));
-            if (w <= 0) { failed = 1; return false; }
-            data += w; bytes -= static_cast<size_t>(w); at += static_cast<uint64_t>(w);
-        }
-        return true;
-    }
-};
 
 // H-, S- and L-lines of the whole graph (write_gfa_header / write_segments / write_links, src/bin/gbunzip.rs:193-317).  Serial host work in
 // the reference; here the node ids are cut into ranges that a few threads turn into text side by side (the S-lines of all ranges, then
@@ -1058,133 +1056,6 @@ uint64_t host_graph_lines(const HostIndex &h, bool translated, PositionalFile &f
     return out.cursor;
 }
 
-// The writer's side of a whole-file write: one thread that first puts out the graph lines (which precede the paths in the file; see
-// host_graph_lines), then takes finished batches of path lines -- device text -- and moves them to the file in pieces of 32 MiB: the
-// piece travels into one of four pinned buffers (the copy of the next piece runs under whatever happens to this one) and a small pool of
-// threads writes the buffers at their positions.  The main thread formats the next batch into the other device text buffer meanwhile.
-struct GfaWriter {
-    static constexpr size_t PIECE = size_t(32) << 20;
-    int WRITERS = 3, BUFFERS = 5;            // GBWT_HIP_GFA_WRITERS (1 .. 16); two more pinned buffers than writing threads
-    struct Job { const char *text; uint64_t bytes; int slot; };
-    struct Piece { int buffer; uint64_t bytes, at; };
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<Job> jobs;
-    std::deque<Piece> pieces;              // pinned buffers that hold a piece on its way to the file
-    std::vector<char> buffer_busy;
-    bool closing = false, no_more_pieces = false, slot_busy[2] = {false, false};
-    gbwt_hip_status status = GBWT_HIP_OK;
-    std::string message;
-    std::thread worker;
-    PositionalFile *file = nullptr;
-    const HostIndex *host = nullptr;
-    bool translated = false;
-    int device = 0;
-
-    void fail_with(gbwt_hip_status st, const std::string &msg) {
-        std::lock_guard<std::mutex> lock(m);
-        if (status == GBWT_HIP_OK) { status = st; message = msg; }
-        cv.notify_all();
-    }
-    void run() {
-        if (const char *v = std::getenv("GBWT_HIP_GFA_WRITERS")) WRITERS = std::min(16, std::max(1, std::atoi(v)));
-        BUFFERS = WRITERS + 2;
-        std::vector<void *> pinned(BUFFERS, nullptr);
-        buffer_busy.assign(BUFFERS, 0);
-        hipStream_t stream = nullptr;
-        const bool trace = std::getenv("GBWT_HIP_TRACE_GFA") != nullptr;       // phases of a whole-file write on stderr
-        const auto t0 = std::chrono::steady_clock::now();
-        const auto since = [&t0]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-        uint64_t path_bytes = 0;
-        std::vector<std::thread> pool;
-        try {
-            uint64_t cursor = host_graph_lines(*host, translated, *file);
-            if (file->failed) throw std::runtime_error("short write");
-            if (trace) std::fprintf(stderr, "[gfa] H/S/L lines: %llu bytes generated and written in %.1f ms\n", static_cast<unsigned long long>(cursor), since());
-            HIP_CHECK(hipSetDevice(device));
-            HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            for (int i = 0; i < BUFFERS; i++) HIP_CHECK(hipHostMalloc(&pinned[i], PIECE, hipHostMallocDefault));
-            for (int t = 0; t < WRITERS; t++)
-                pool.emplace_back([this, &pinned]() {
-                    for (;;) {
-                        Piece p;
-                        {
-                            std::unique_lock<std::mutex> lock(m);
-                            cv.wait(lock, [&] { return !pieces.empty() || no_more_pieces; });
-                            if (pieces.empty()) return;
-                            p = pieces.front(); pieces.pop_front();
-                        }
-                        if (!file->write_at(static_cast<const char *>(pinned[p.buffer]), p.bytes, p.at)) fail_with(GBWT_HIP_IO_ERROR, "short write");
-                        { std::lock_guard<std::mutex> lock(m); buffer_busy[p.buffer] = 0; }
-                        cv.notify_all();
-                    }
-                });
-            for (;;) {
-                Job job;
-                {
-                    std::unique_lock<std::mutex> lock(m);
-                    cv.wait(lock, [&] { return !jobs.empty() || closing || status != GBWT_HIP_OK; });
-                    if (status != GBWT_HIP_OK || jobs.empty()) break;
-                    job = jobs.front(); jobs.pop_front();
-                }
-                path_bytes += job.bytes;
-                for (uint64_t done = 0; done < job.bytes; done += PIECE) {
-                    int b = -1;
-                    {
-                        std::unique_lock<std::mutex> lock(m);
-                        cv.wait(lock, [&] { for (int i = 0; i < BUFFERS; i++) if (!buffer_busy[i]) return true; return status != GBWT_HIP_OK; });
-                        if (status != GBWT_HIP_OK) break;
-                        for (int i = 0; i < BUFFERS; i++) if (!buffer_busy[i]) { b = i; break; }
-                        buffer_busy[b] = 1;
-                    }
-                    const uint64_t len = std::min<uint64_t>(PIECE, job.bytes - done);
-                    HIP_CHECK(hipMemcpyAsync(pinned[b], job.text + done, len, hipMemcpyDeviceToHost, stream));
-                    HIP_CHECK(hipStreamSynchronize(stream));
-                    { std::lock_guard<std::mutex> lock(m); pieces.push_back(Piece{b, len, cursor + done}); }
-                    cv.notify_all();
-                }
-                cursor += job.bytes;
-                {   // the device text of this batch has left: the formatter may have the slot back
-                    std::lock_guard<std::mutex> lock(m);
-                    slot_busy[job.slot] = false;
-                }
-                cv.notify_all();
-            }
-        } catch (const HipError &e) {
-            fail_with(GBWT_HIP_DEVICE_ERROR, std::string(e.what) + ": " + hipGetErrorString(e.err));
-        } catch (const std::exception &e) {
-            fail_with(GBWT_HIP_IO_ERROR, std::string("GFA writer: ") + e.what());
-        }
-        { std::lock_guard<std::mutex> lock(m); no_more_pieces = true; }
-        cv.notify_all();
-        for (auto &t : pool) t.join();
-        if (trace) std::fprintf(stderr, "[gfa] path lines: %llu bytes; writer threads done at %.1f ms\n", static_cast<unsigned long long>(path_bytes), since());
-        for (int i = 0; i < BUFFERS; i++) if (pinned[i]) (void)hipHostFree(pinned[i]);
-        if (stream) (void)hipStreamDestroy(stream);
-        std::lock_guard<std::mutex> lock(m);
-        closing = true; slot_busy[0] = slot_busy[1] = false;
-        cv.notify_all();
-    }
-    // the formatter's side: wait until the device text buffer of `slot` has been read out; false when the writer has failed
-    bool acquire(int slot) {
-        std::unique_lock<std::mutex> lock(m);
-        cv.wait(lock, [&] { return !slot_busy[slot] || status != GBWT_HIP_OK; });
-        if (status != GBWT_HIP_OK) return false;
-        slot_busy[slot] = true;
-        return true;
-    }
-    void submit(const char *text, uint64_t bytes, int slot) {
-        { std::lock_guard<std::mutex> lock(m); jobs.push_back(Job{text, bytes, slot}); }
-        cv.notify_all();
-    }
-    gbwt_hip_status finish() {
-        { std::lock_guard<std::mutex> lock(m); closing = true; }
-        cv.notify_all();
-        if (worker.joinable()) worker.join();
-        return status;
-    }
-    ~GfaWriter() { (void)finish(); }
-};
 
 }  // namespace
 
@@ -1312,7 +1183,7 @@ gbwt_hip_status gbwt_hip_write_gfa(const gbwt_hip_index *ix, gbwt_hip_workspace 
 // The reference builds the lines of the paths in parallel and hands them to a writer under a mutex, behind an 8 MiB BufWriter
 // (src/bin/gbunzip.rs:96, 205-226, 421-434).  Here: batches bounded by BYTES of text (GBWT_HIP_GFA_BATCH_MIB, default 1 GiB: config 4's
 // 32 000 walks are four batches, the headline's 5 000 paths of 4.5 MB each a few hundred), formatted on the device into two text
-// buffers in turn, while a writer thread moves the previous batch to the file through two 64 MiB pinned buffers (GfaWriter) -- and
+// buffers in turn, while a writer thread moves the previous batch to the file through pinned buffers (batch_writer.hpp) -- and
 // writes the H-, S- and L-lines of the graph, host work, while the first batch is walked.
 gbwt_hip_status gbwt_hip_write_gfa_mode(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const char *path, int path_mode) {
     GBWT_HIP_GUARD_BEGIN
@@ -1325,9 +1196,11 @@ gbwt_hip_status gbwt_hip_write_gfa_mode(const gbwt_hip_index *ix, gbwt_hip_works
         PositionalFile file;
         file.fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (file.fd < 0) return fail(GBWT_HIP_IO_ERROR, std::string("cannot create ") + path);
-        GfaWriter writer;
-        writer.file = &file; writer.host = &h; writer.translated = translated; writer.device = ix->device;
-        writer.worker = std::thread([&writer]() { writer.run(); });
+        // the writer's thread first puts out the graph lines, which precede the paths in the file (host_graph_lines), then the batches
+        BatchWriter writer;
+        writer.file = &file; writer.device = ix->device;
+        writer.preamble = [&h, translated, &file]() { return host_graph_lines(h, translated, file); };
+        writer.start();
         // write_gfa_impl's match on the path mode (src/bin/gbunzip.rs:212-222), ascending path id (-t 1 order):
         //   default: paths of the generic sample as P-lines, then the others as W-lines (write_paths / write_walks, 343-417)
         //   pan-sn : every path as a P-line with its PanSN name (write_pan_sn, 371-393)

@@ -136,7 +136,8 @@ gbwt_hip_status gbwt_hip_get_stats(const gbwt_hip_index *index, gbwt_hip_stats *
  * descriptors, rank blocks, tables, samples, GFA tables; the full-width two-step blocks are counted once they have been built (on first
  * need).  An index is replicated per GPU, so this is also the cost of one more rank.  index_host_bytes: the host image (record
  * bytes, starts, names, node labels).  workspace_device_bytes (0 for ws == NULL): all scratch of the workspace, of which rows_bytes are
- * the extracted rows (the CSR node ids) and text_bytes the formatted GFA lines. */
+ * the extracted rows (the CSR node ids) and text_bytes the formatted GFA lines and the bases of paths.  The node labels of a GBZ are in
+ * index_device_bytes once the first request for bases has made them. */
 typedef struct {
     uint64_t index_device_bytes, index_host_bytes;
     uint64_t workspace_device_bytes, rows_bytes, text_bytes;
@@ -314,6 +315,38 @@ gbwt_hip_status gbwt_hip_write_gfa(const gbwt_hip_index *index, gbwt_hip_workspa
  * 371-393); ref-only = the P-lines of the default mode and nothing else. */
 enum { GBWT_HIP_PATHS_DEFAULT = 0, GBWT_HIP_PATHS_PAN_SN = 1, GBWT_HIP_PATHS_REF_ONLY = 2 };
 gbwt_hip_status gbwt_hip_write_gfa_mode(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *path, int path_mode);
+
+/* ---- bases of paths (GBZ handles opened with GBWT_HIP_OPEN_EXTRACT) --------------------------------------------------------------
+ * gbz-extract's `sequences` mode (src/bin/gbz-extract.rs:173-194, 266-294).  The bases of a path are GBZ::sequence(node) joined along
+ * GBZ::path(path_id, orientation) (src/gbz.rs:292-305, 461-466), the label of a reverse-oriented node reverse-complemented
+ * (support::reverse_complement, src/support.rs:87-110: A, C, G, T in either case to the upper-case complement, every other byte to N).
+ * The node labels reach HBM on the first such request on a handle (one upload whichever thread asks first; counted in
+ * gbwt_hip_memory_usage's index_device_bytes from then on); an open never makes them.  A handle that is not a GBZ, or was not opened for
+ * extraction, gives GBWT_HIP_BAD_ARGUMENT; so does an endmarker outside -1 .. 255.
+ *
+ * gbwt_hip_path_sequences_device: extract_sequence (src/bin/gbz-extract.rs:173-189) for every path id, in the order given, orientation
+ * Reverse where `reverse` != 0; `endmarker` = -1: none, 0 .. 255: that byte behind every row (gbz-extract's --endmarker-value, default 0).
+ * Row k = d_text[d_line_offsets[k] .. d_line_offsets[k + 1]) (device pointers, valid until the next request for bases on `ws`).  A path id
+ * whose sequence 2 id + orientation does not exist gives an empty row without endmarker (as gbwt_hip_extract_paths, whose rows these are). */
+gbwt_hip_status gbwt_hip_path_sequences_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int reverse,
+                                               int endmarker, gbwt_hip_lines *out);
+/* The same copied to host buffers: out_offsets[n + 1] (may be NULL), out[total]; out == NULL is a size query, capacity < total ->
+ * GBWT_HIP_CAPACITY.  `*total` always receives the bytes.  The fill call that repeats the request of a size query does not walk again. */
+gbwt_hip_status gbwt_hip_path_sequences(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int reverse, int endmarker,
+                                        char *out, uint64_t *out_offsets, uint64_t capacity, uint64_t *total);
+/* GBZ::sequence / sequence_len (src/gbz.rs:292-305) from the host image: *found = 0 for a node that does not exist (GBZ::has_node,
+ * src/gbz.rs:286-289; not an error), else *len = the label's bytes and, unless out == NULL (size query), the label in out[0 .. len);
+ * capacity < len -> GBWT_HIP_CAPACITY.  GBWT_HIP_BAD_ARGUMENT for a bare GBWT. */
+gbwt_hip_status gbwt_hip_node_sequence(const gbwt_hip_index *index, uint64_t node_id, char *out, uint64_t capacity, uint64_t *len, uint8_t *found);
+/* gbz-extract -o path (extract_sequences, src/bin/gbz-extract.rs:266-294), byte for byte: the forward bases of the given paths (NULL = all,
+ * ascending), each followed by `endmarker` (-1: none), into `path`, and for every path the line path_name_as_line writes (:191-194)
+ * "path_id \t sample \t contig \t phase \t fragment \t bases \n" into `path`.names (names fall back to the number, src/gbwt.rs:755-761,
+ * 803-809).  Batches bounded by bytes (GBWT_HIP_SEQ_BATCH_MIB, read at each call; default 1024) go through two device buffers while a writer
+ * thread moves the previous one to the file.  GBWT_HIP_BAD_ARGUMENT without metadata or path names, and for a path id out of range. */
+gbwt_hip_status gbwt_hip_write_sequences(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *path, const uint64_t *path_ids, uint64_t n, int endmarker);
+/* Device time of the last request for bases on `ws` (HIP events): *walk_ms = the walk of its extraction, *sizes_ms = sizing and placing its rows
+ * up to the host's one wait, *bases_ms = the chunk plan and the bases kernel. */
+gbwt_hip_status gbwt_hip_last_sequences_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *sizes_ms, float *bases_ms);
 
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex

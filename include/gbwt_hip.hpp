@@ -239,6 +239,31 @@ public:
     // GBZ::follow_forward / follow_backward collected (StateIter, src/gbz.rs:519-544, 1211-1251); nullopt = no iterator
     std::optional<std::vector<BidirectionalState>> follow_forward(const BidirectionalState &state) const { return follow(state, false); }
     std::optional<std::vector<BidirectionalState>> follow_backward(const BidirectionalState &state) const { return follow(state, true); }
+    // GBZ::sequence(node_id) (src/gbz.rs:292-298): the node's label, or nullopt for a node that does not exist
+    std::optional<std::string> sequence(uint64_t node_id) const {
+        uint64_t len = 0;
+        uint8_t found = 0;
+        check(gbwt_hip_node_sequence(index_.get(), node_id, nullptr, 0, &len, &found));
+        if (!found) return std::nullopt;
+        std::string label(len, '\0');
+        if (len) check(gbwt_hip_node_sequence(index_.get(), node_id, label.data(), len, &len, &found));
+        return label;
+    }
+    // The bases of GBZ::path(path_id, orientation) (gbz-extract's extract_sequence without the endmarker, src/bin/gbz-extract.rs:173-189):
+    // labels joined, reverse-oriented ones reverse-complemented; nullopt = no such path
+    std::optional<std::string> path_sequence(uint64_t path_id, Orientation orientation) const {
+        if (path_id >= paths()) return std::nullopt;
+        const int reverse = orientation == Orientation::Reverse ? 1 : 0;
+        uint64_t total = 0;
+        check(gbwt_hip_path_sequences(index_.get(), ws_.get(), &path_id, 1, reverse, -1, nullptr, nullptr, 0, &total));
+        std::string bases(total, '\0');
+        if (total) check(gbwt_hip_path_sequences(index_.get(), ws_.get(), &path_id, 1, reverse, -1, bases.data(), nullptr, total, &total));
+        return bases;
+    }
+    // gbz-extract -o path: `path` and `path`.names for all paths (src/bin/gbz-extract.rs:266-294)
+    void write_sequences(const std::string &path, int endmarker = 0) const {
+        check(gbwt_hip_write_sequences(index_.get(), ws_.get(), path.c_str(), nullptr, 0, endmarker));
+    }
     // the lines gbunzip writes for these paths (mode 0 = P-lines, 1 = W-lines) and the whole GFA file
     std::string path_lines(const std::vector<uint64_t> &path_ids, int mode) const {
         uint64_t total = 0;
