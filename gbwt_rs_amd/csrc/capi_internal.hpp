@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <new>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -18,6 +19,7 @@
 #include "device_index.hpp"
 #include "host_index.hpp"
 #include "kernels.hpp"
+#include "lazy_build.hpp"
 
 namespace gbwt_hip {
 
@@ -219,62 +221,52 @@ DeviceIndex with_cblocks(const gbwt_hip_index *ix);
 
 }  // namespace gbwt_hip
 
-struct gbwt_hip_index {
-    gbwt_hip::HostIndex host;
-    int device = 0;
-    bool lean_extract = false;           // opened without SEARCH and no record needs the generic decoder: desc_raw was given back after the open (capi_open.hip: open_common)
-    uint64_t slow_records = ~uint64_t(0); // non-empty records whose walk descriptor says "generic decoder" (k_link_desc2's count; ~0 = not counted)
-    uint32_t caps = GBWT_HIP_OPEN_ALL;   // what the handle was opened for (gbwt_hip_open_*_flags): which arrays exist, which entry points answer
-    uint64_t table_positions = 0;     // BWT positions in records with LF tables (outdegree > 2)
-    gbwt_hip::DeviceBuffer data, starts, endmarker, desc, desc_raw, block_base, blocks, desc2, cblocks, gblocks, tables, wtables, wtables_deep, seq_len, samples, sample_base;
-    gbwt_hip::DeviceBuffer label_len;   // GBZ only: label length per potential node (0 for nodes that do not exist)
-    // GBZ with a node-to-segment translation (src/graph.rs:186-218), flattened for the line formatter:
-    gbwt_hip::DeviceBuffer seg_of;        // u32 per node id < mapping_len: segment holding the node (~0 before the first segment)
-    gbwt_hip::DeviceBuffer seg_start;     // u32 per segment + 1: first node id of the segment, last = mapping_len
-    gbwt_hip::DeviceBuffer seg_name_off;  // u64 per segment + 1: offsets into seg_names
-    gbwt_hip::DeviceBuffer seg_names;     // segment names, concatenated
-    gbwt_hip::DeviceBuffer seg_seq_len;   // u64 per segment: length of the segment's sequence
-    gbwt_hip::DeviceBuffer node_real;     // u8 per node id < mapping_len: GBZ::has_node
-    // GFA line headers, one table per line mode (0 = P-line named by the contig, 1 = W-line, 2 = P-line with the PanSN name): for every path of
-    // the metadata the bytes of its line up to the node tokens -- for a W-line up to and including "<fragment>\t"; the end coordinate
-    // (fragment + summed label lengths, path_to_w_line, src/bin/gbunzip.rs:532-540) is only known once the path has been walked and is
-    // appended by the device.  Built once at open (gfa.hip: upload_label_lengths), so that a request formats its lines without the host.
-    gbwt_hip::DeviceBuffer line_prefix[3], line_prefix_off[3], line_fragment;
-    std::vector<char> host_line_prefix[3];
-    std::vector<uint64_t> host_line_prefix_off[3];
-    // LINE CACHE (gfa.hip): what the GFA line of a path is made of -- the text bytes of its node tokens, chunk by chunk, and its summed label
-    // lengths (the W-line's end coordinate) -- is a property of the index, not of the request.  Round 5 let the first request that formats a
-    // path leave them here; since round 6 ONE walk at open fills them for every path (fill_line_cache_at_open; kernels.hpp: LineCacheFill), so
-    // that no request sizes a line: the node ids cross HBM twice (written by the walk, read by the formatter), never three times.
-    // 8 bytes per 4 096 path positions + 16 per path.  Absent (-1) without sequence samples, for graphs with a node-to-segment translation
-    // and with GBWT_HIP_LINE_CACHE=0: requests then size their lines themselves (k_chunk_stats).
-    gbwt_hip::DeviceBuffer lc_chunk_first, lc_text, lc_path;    // u64[paths + 1]: first chunk of every path; u64 per chunk: W-token bytes of the path in front of it; u64[2] per path: {W-token bytes, summed label lengths}
-    int lc_state = 0;                                             // 1 = filled at open, -1 = not for this index (written before the handle is handed out)
-    std::vector<uint32_t> host_seq_len;   // host copy of seq_len (empty when the lengths are not known): sizes byte-bounded batches of a whole-file write
-    // NODE LABELS IN HBM, made by the first request for bases (sequences.hip: ensure_labels), never by an open: the bytes of every potential
-    // node's label (+ 64 zero bytes, so that the aligned dword loads of the bases kernel may read past the last one) and u64 offsets[nodes + 1].
-    // One upload per handle whichever thread asks first (a mutex and a flag; the flag alone is read by gbwt_hip_memory_usage).
-    mutable std::mutex labels_lock;
-    mutable std::atomic<bool> labels_made{false};
-    mutable gbwt_hip::DeviceBuffer label_bytes, label_off;
-    mutable uint64_t max_label_len = 0;
-    gbwt_hip::DeviceIndex dev{};
-    // The full-width two-step blocks (cblocks, as large as gblocks: 1.7 GB on the headline index) are only read by the loops for records
-    // whose counts do not fit the packed half-blocks, by the pool-output kernel and by the serial walks at open: built at open when one of
-    // those is certain to run, else on the first request that needs them (ensure_cblocks; once, whichever thread comes first).
-    mutable std::once_flag cblocks_once;
-    std::atomic<const uint4 *> lazy_cblocks{nullptr};
-    bool packed_blocks = true;        // gblocks was built (false: the index is too large for 32-bit half-block indices, or GBWT_HIP_GATHER_LIMIT=0)
-    uint32_t max_samples = 0;         // the largest number of samples of a sequence
-    uint32_t sample_coarse = 1;       // the samples are this many times finer than a batch of the whole index wants: extractions stride over them (capi_extract.hip)
-    std::vector<uint32_t> sample_counts;   // samples of every sequence (host copy: an extraction looks whether its rows all have the same number)
-    uint32_t uniform_samples = 0;     // every sequence has this many samples (0: they differ): the walkers of an extraction are then w = segment * n + row
-    bool starts_uploaded = false;         // ... and the record starts
-    bool record_bytes_uploaded = false;   // gbwt_hip_open_file has copied the record bytes to `data` while the loader was still decoding
-    gbwt_hip_open_times times{};      // where the time of the open went (gbwt_hip_get_open_times)
-    uint32_t uniform_len = 0;         // every sequence has this many nodes (0: lengths differ, or unknown): an extraction then knows its offsets without asking the device
-    bool orientation_pairs = false;   // verified at open: sequence 2k + 1 is sequence 2k reversed (rows can be filled from both ends)
-    gbwt_hip_stats stats{};
+// The GBWT_HIP_* settings of an open, read ONCE by gbwt_hip_open_file_flags / gbwt_hip_open_records_flags before the loader or any thread
+// of the open starts, and kept on the handle: nothing else of an open looks at the environment (getenv is not safe against a concurrent
+// setenv, and the early copy, the tail thread and the loader's jobs run next to the caller).  Unset = std::nullopt where it matters whether
+// a setting is there at all, or where its default depends on the index.
+struct OpenKnobs {
+    bool seq_len = true;                               // GBWT_HIP_SEQ_LEN (0: no lengths, no samples)
+    std::optional<uint32_t> sample_interval;           // GBWT_HIP_SAMPLE_INTERVAL (0: no samples; unset: by the size of the index, and coarse samples may be kept)
+    std::optional<uint32_t> sample_coarse;             // GBWT_HIP_SAMPLE_COARSE (unset: nominal interval / 512)
+    bool serial_samples = false;                       // GBWT_HIP_SERIAL_SAMPLES: a walk of every sequence instead of checkpoints
+    bool two_pass = false;                             // GBWT_HIP_TWO_PASS_OPEN: lengths, then samples, by two walks of every sequence
+    bool orientation_check = false;                    // GBWT_HIP_ORIENTATION_CHECK: fingerprints even where samples make them unnecessary
+    std::optional<double> checkpoint_gap;              // GBWT_HIP_CHECKPOINT_GAP (unset: by the interval and the chains)
+    std::optional<uint32_t> checkpoint_cap;            // GBWT_HIP_CHECKPOINT_CAP (unset: the interval)
+    std::optional<uint32_t> chains;                    // GBWT_HIP_CHAINS (unset: CHAIN_MAX, and a handful of chained records are linked again without)
+    uint32_t gather_limit = 1u << 21;                  // GBWT_HIP_GATHER_LIMIT: the counts of the packed blocks (0: none; tests lower it)
+    uint32_t lookahead_hops = 15;                      // GBWT_HIP_LOOKAHEAD_HOPS
+    bool walk_tables = true, deep_tables = true, compact_tables = true;   // GBWT_HIP_WALK_TABLES / _DEEP_TABLES / _COMPACT_TABLES (0 switches off)
+    std::optional<uint64_t> table_bytes;               // GBWT_HIP_TABLE_BYTES (unset: by the device's memory)
+    bool line_cache = true;                            // GBWT_HIP_LINE_CACHE (0: requests size their lines themselves)
+    bool trace = false;                                // GBWT_HIP_TRACE_OPEN set (any value): phase timings on stderr
+    static OpenKnobs from_env() {
+        OpenKnobs k;
+        const auto on = [](const char *name) { const char *v = std::getenv(name); return !(v && std::atoi(v) == 0); };     // "0" switches off
+        const auto forced = [](const char *name) { const char *v = std::getenv(name); return v && std::atoi(v) != 0; };  // anything but "0" switches on
+        k.seq_len = on("GBWT_HIP_SEQ_LEN");
+        if (const char *v = std::getenv("GBWT_HIP_SAMPLE_INTERVAL")) k.sample_interval = static_cast<uint32_t>(std::max(0, std::atoi(v)));
+        if (const char *v = std::getenv("GBWT_HIP_SAMPLE_COARSE")) k.sample_coarse = static_cast<uint32_t>(std::max(1, std::atoi(v)));
+        k.serial_samples = forced("GBWT_HIP_SERIAL_SAMPLES");
+        k.two_pass = forced("GBWT_HIP_TWO_PASS_OPEN");
+        k.orientation_check = forced("GBWT_HIP_ORIENTATION_CHECK");
+        if (const char *v = std::getenv("GBWT_HIP_CHECKPOINT_GAP")) k.checkpoint_gap = std::max(2.0, std::atof(v));
+        if (const char *v = std::getenv("GBWT_HIP_CHECKPOINT_CAP")) k.checkpoint_cap = static_cast<uint32_t>(std::max(1, std::atoi(v)));
+        if (const char *v = std::getenv("GBWT_HIP_CHAINS")) k.chains = static_cast<uint32_t>(std::min<long>(gbwt_hip::CHAIN_MAX, std::max<long>(0, std::atol(v))));
+        if (const char *v = std::getenv("GBWT_HIP_GATHER_LIMIT")) k.gather_limit = static_cast<uint32_t>(std::min<long>(1l << 21, std::max<long>(0, std::atol(v))));
+        if (const char *v = std::getenv("GBWT_HIP_LOOKAHEAD_HOPS")) k.lookahead_hops = static_cast<uint32_t>(std::max(0, std::atoi(v)));
+        k.walk_tables = on("GBWT_HIP_WALK_TABLES"); k.deep_tables = on("GBWT_HIP_DEEP_TABLES"); k.compact_tables = on("GBWT_HIP_COMPACT_TABLES");
+        if (const char *v = std::getenv("GBWT_HIP_TABLE_BYTES")) k.table_bytes = std::strtoull(v, nullptr, 10);
+        k.line_cache = on("GBWT_HIP_LINE_CACHE");
+        k.trace = std::getenv("GBWT_HIP_TRACE_OPEN") != nullptr;
+        return k;
+    }
+    // GBWT_HIP_LAZY_HOST_RECORDS, once per process: 0 = an open from a file makes the host's copy of the records in the loader's background
+    static bool lazy_host_records() {
+        static const bool lazy = [] { const char *e = std::getenv("GBWT_HIP_LAZY_HOST_RECORDS"); return !(e && e[0] == '0'); }();
+        return lazy;
+    }
 };
 
 // The GBWT_HIP_* tuning / measurement switches of an extraction, read ONCE when the workspace is created: gbwt_hip_extract_device
@@ -311,6 +303,64 @@ struct ExtractKnobs {
         k.copy_threads = static_cast<unsigned>(std::min(64, std::max(1, num("GBWT_HIP_COPY_THREADS", 8))));
         return k;
     }
+};
+
+struct gbwt_hip_index {
+    gbwt_hip::HostIndex host;
+    int device = 0;
+    OpenKnobs knobs;                      // the open's settings (gbwt_hip_open_*_flags)
+    bool lean_extract = false;           // opened without SEARCH and no record needs the generic decoder: desc_raw was given back after the open (capi_open.hip: open_common)
+    uint64_t slow_records = ~uint64_t(0); // non-empty records whose walk descriptor says "generic decoder" (k_link_desc2's count; ~0 = not counted)
+    uint32_t caps = GBWT_HIP_OPEN_ALL;   // what the handle was opened for (gbwt_hip_open_*_flags): which arrays exist, which entry points answer
+    uint64_t table_positions = 0;     // BWT positions in records with LF tables (outdegree > 2)
+    gbwt_hip::DeviceBuffer data, starts, endmarker, desc, desc_raw, block_base, blocks, desc2, cblocks, gblocks, tables, wtables, wtables_deep, seq_len, samples, sample_base;
+    gbwt_hip::DeviceBuffer label_len;   // GBZ only: label length per potential node (0 for nodes that do not exist)
+    // GBZ with a node-to-segment translation (src/graph.rs:186-218), flattened for the line formatter:
+    gbwt_hip::DeviceBuffer seg_of;        // u32 per node id < mapping_len: segment holding the node (~0 before the first segment)
+    gbwt_hip::DeviceBuffer seg_start;     // u32 per segment + 1: first node id of the segment, last = mapping_len
+    gbwt_hip::DeviceBuffer seg_name_off;  // u64 per segment + 1: offsets into seg_names
+    gbwt_hip::DeviceBuffer seg_names;     // segment names, concatenated
+    gbwt_hip::DeviceBuffer seg_seq_len;   // u64 per segment: length of the segment's sequence
+    gbwt_hip::DeviceBuffer node_real;     // u8 per node id < mapping_len: GBZ::has_node
+    // GFA line headers, one table per line mode (0 = P-line named by the contig, 1 = W-line, 2 = P-line with the PanSN name): for every path of
+    // the metadata the bytes of its line up to the node tokens -- for a W-line up to and including "<fragment>\t"; the end coordinate
+    // (fragment + summed label lengths, path_to_w_line, src/bin/gbunzip.rs:532-540) is only known once the path has been walked and is
+    // appended by the device.  Built once at open (gfa.hip: upload_label_lengths), so that a request formats its lines without the host.
+    gbwt_hip::DeviceBuffer line_prefix[3], line_prefix_off[3], line_fragment;
+    std::vector<char> host_line_prefix[3];
+    std::vector<uint64_t> host_line_prefix_off[3];
+    // LINE CACHE (gfa.hip): what the GFA line of a path is made of -- the text bytes of its node tokens, chunk by chunk, and its summed label
+    // lengths (the W-line's end coordinate) -- is a property of the index, not of the request.  Round 5 let the first request that formats a
+    // path leave them here; since round 6 ONE walk at open fills them for every path (fill_line_cache_at_open; kernels.hpp: LineCacheFill), so
+    // that no request sizes a line: the node ids cross HBM twice (written by the walk, read by the formatter), never three times.
+    // 8 bytes per 4 096 path positions + 16 per path.  Absent (-1) without sequence samples, for graphs with a node-to-segment translation
+    // and with GBWT_HIP_LINE_CACHE=0: requests then size their lines themselves (k_chunk_stats).
+    gbwt_hip::DeviceBuffer lc_chunk_first, lc_text, lc_path;    // u64[paths + 1]: first chunk of every path; u64 per chunk: W-token bytes of the path in front of it; u64[2] per path: {W-token bytes, summed label lengths}
+    int lc_state = 0;                                             // 1 = filled at open, -1 = not for this index (written before the handle is handed out)
+    std::vector<uint32_t> host_seq_len;   // host copy of seq_len (empty when the lengths are not known): sizes byte-bounded batches of a whole-file write
+    // NODE LABELS IN HBM, made by the first request for bases (sequences.hip: ensure_labels), never by an open: the bytes of every potential
+    // node's label (+ 64 zero bytes, so that the aligned dword loads of the bases kernel may read past the last one) and u64 offsets[nodes + 1].
+    // One upload per handle whichever thread asks first (gbwt_hip_memory_usage counts them once labels_built.made()).
+    mutable gbwt_hip::LazyBuild labels_built;
+    mutable gbwt_hip::DeviceBuffer label_bytes, label_off;
+    mutable uint64_t max_label_len = 0;
+    gbwt_hip::DeviceIndex dev{};
+    // The full-width two-step blocks (cblocks, as large as gblocks: 1.7 GB on the headline index) are only read by the loops for records
+    // whose counts do not fit the packed half-blocks, by the pool-output kernel and by the serial walks at open: built at open when one of
+    // those is certain to run, else on the first request that needs them (ensure_cblocks; once, whichever thread comes first).
+    mutable gbwt_hip::LazyBuild cblocks_built;
+    bool packed_blocks = false;       // gblocks holds the packed half-blocks (set by the open's walk layout, capi_open.hip: layout_walks; false: a handle
+                                      // not opened for extraction, an index too large for 32-bit half-block indices, or GBWT_HIP_GATHER_LIMIT=0)
+    uint32_t max_samples = 0;         // the largest number of samples of a sequence
+    uint32_t sample_coarse = 1;       // the samples are this many times finer than a batch of the whole index wants: extractions stride over them (capi_extract.hip)
+    std::vector<uint32_t> sample_counts;   // samples of every sequence (host copy: an extraction looks whether its rows all have the same number)
+    uint32_t uniform_samples = 0;     // every sequence has this many samples (0: they differ): the walkers of an extraction are then w = segment * n + row
+    bool starts_uploaded = false;         // ... and the record starts
+    bool record_bytes_uploaded = false;   // gbwt_hip_open_file has copied the record bytes to `data` while the loader was still decoding
+    gbwt_hip_open_times times{};      // where the time of the open went (gbwt_hip_get_open_times)
+    uint32_t uniform_len = 0;         // every sequence has this many nodes (0: lengths differ, or unknown): an extraction then knows its offsets without asking the device
+    bool orientation_pairs = false;   // verified at open: sequence 2k + 1 is sequence 2k reversed (rows can be filled from both ends)
+    gbwt_hip_stats stats{};
 };
 
 struct gbwt_hip_workspace {

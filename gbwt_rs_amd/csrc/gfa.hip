@@ -698,11 +698,10 @@ void fill_line_cache_at_open(gbwt_hip_index &ix) {
     ix.lc_state = -1;
     const uint64_t paths = h.path_names.size();
     const bool translated = h.has_translation && !h.segment_starts.empty();
-    const char *off = std::getenv("GBWT_HIP_LINE_CACHE");
-    if (!(ix.caps & GBWT_HIP_OPEN_GFA) || !h.is_gbz || !h.has_metadata || translated || paths == 0 || (off && std::atoi(off) == 0)) return;
+    if (!(ix.caps & GBWT_HIP_OPEN_GFA) || !h.is_gbz || !h.has_metadata || translated || paths == 0 || !ix.knobs.line_cache) return;
     if (ix.host_seq_len.size() < 2 * paths || ix.sample_counts.size() < 2 * paths || 2 * paths > h.sequences) return;
     const DeviceIndex &d = ix.dev;
-    if (d.samples == nullptr || d.sample_base == nullptr || d.seq_len == nullptr || d.desc2 == nullptr || (d.gblocks == nullptr && d.cblocks == nullptr)) return;
+    if (d.samples == nullptr || d.sample_base == nullptr || d.seq_len == nullptr || d.desc2 == nullptr || (!ix.packed_blocks && d.cblocks == nullptr)) return;
     if (ix.label_len.ptr == nullptr) return;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint64_t> first(paths + 1, 0);
@@ -729,7 +728,7 @@ void fill_line_cache_at_open(gbwt_hip_index &ix) {
     f.label_len = ix.label_len.as<uint32_t>(); f.n_labels = h.sequences_labels.size(); f.paths = paths; f.max_samples = max_samples;
     f.chunk_first = ix.lc_chunk_first.as<uint64_t>(); f.chunks = first[paths]; f.chunk_text = ix.lc_text.as<uint64_t>(); f.path_totals = ix.lc_path.as<uint64_t>();
     f.chunk_seg = chunk_seg.as<uint32_t>(); f.seg_text = seg_text.as<uint64_t>(); f.flags = flags.as<uint32_t>();
-    launch_fill_line_cache(d, f, nullptr);
+    launch_fill_line_cache(d, f, ix.packed_blocks, nullptr);
     uint32_t bad = 0;
     HIP_CHECK(hipMemcpy(&bad, flags.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());

@@ -1,6 +1,7 @@
 // host_index.cpp -- simple-sds reader for .gbwt / .gbz (product code; see host_index.hpp).
 // Layout: SURVEY.md Appendix A.  Every structure is a run of little-endian u64 "elements".
 #include "host_index.hpp"
+#include "lazy_build.hpp"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -18,7 +19,6 @@
 #include <exception>
 #include <functional>
 #include <memory>
-#include <mutex>
 #include <thread>
 
 namespace gbwt_hip {
@@ -532,8 +532,7 @@ struct HostIndex::Pending {
 struct HostIndex::LazyRecords {
     std::shared_ptr<Pending> image;                            // the mapping `make` reads -- and record_bytes() / starts_view point into: lives as long as the index
     std::function<void()> make;
-    std::once_flag once;
-    std::atomic<bool> made{false};
+    LazyBuild build;
 };
 
 void HostIndex::finish() {
@@ -549,18 +548,16 @@ void HostIndex::finish() {
     if (is_gbz) check_graph(*this);
 }
 
-bool HostIndex::records_made() const { return !lazy_records || lazy_records->made.load(std::memory_order_acquire); }
+bool HostIndex::records_made() const { return !lazy_records || lazy_records->build.made(); }
 
 void HostIndex::ensure_records() const {
-    if (!lazy_records) return;
-    LazyRecords &lazy = *lazy_records;
-    std::call_once(lazy.once, [&lazy]() { lazy.make(); lazy.made.store(true, std::memory_order_release); });   // (a throw leaves the flag unset: the next caller tries again)
+    if (lazy_records) lazy_records->build.ensure(lazy_records->make);
 }
 
 namespace {
-// GBWT_HIP_TRACE_OPEN=1: the loader's phases on stderr, like the device side of an open (capi_open.hip: OpenTrace)
+// `trace` (an open's GBWT_HIP_TRACE_OPEN): the loader's phases on stderr, like the device side of an open (capi_open.hip: OpenTrace)
 struct LoadTrace {
-    bool on = std::getenv("GBWT_HIP_TRACE_OPEN") != nullptr;
+    bool on;
     std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
     void mark(const char *what) {
         if (!on) return;
@@ -571,8 +568,9 @@ struct LoadTrace {
 };
 }  // namespace
 
-void load_index_file_into(const std::string &path, HostIndex &h, bool background, const std::function<void(HostIndex &)> &on_located, bool lazy_records) {
-    LoadTrace trace;
+void load_index_file_into(const std::string &path, HostIndex &h, bool background, const std::function<void(HostIndex &)> &on_located, bool lazy_records,
+                          bool trace_phases) {
+    LoadTrace trace{trace_phases};
     h = HostIndex();
     std::shared_ptr<HostIndex::Pending> pending = std::make_shared<HostIndex::Pending>();
     open_image(path, pending->image);
@@ -638,12 +636,11 @@ void load_index_file_into(const std::string &path, HostIndex &h, bool background
     HostIndex::Pending *raw = pending.get();
     std::vector<std::function<void()>> jobs = std::move(later.background);
     if (!jobs.empty())
-        raw->worker = std::thread([raw, jobs]() {
-            const bool trace_jobs = std::getenv("GBWT_HIP_TRACE_OPEN") != nullptr;
+        raw->worker = std::thread([raw, jobs, trace_phases]() {
             try { run_pieces(static_cast<unsigned>(jobs.size()), [&](unsigned p) {        // the record bytes, the record starts and the labels side by side
                 const auto t0 = std::chrono::steady_clock::now();
                 jobs[p]();
-                if (trace_jobs) std::fprintf(stderr, "[load] (background job %u of %zu)     %8.3f ms\n", p, jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+                if (trace_phases) std::fprintf(stderr, "[load] (background job %u of %zu)     %8.3f ms\n", p, jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             }); }
             catch (...) { raw->failure = std::current_exception(); }
         });

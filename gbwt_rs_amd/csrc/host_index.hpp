@@ -122,7 +122,9 @@ HostIndex load_index_file(const std::string &path);
 // `on_located` (optional) runs once the file has been walked -- header fields set, record_bytes() valid -- and before anything is decoded:
 // an open starts the host-to-device copy of the record bytes there, next to the Elias-Fano decode of the starts.
 // `lazy_records`: see HostIndex::ensure_records (only with `background`, a file of 4 MB or more, and an on_located that has set starts_on_device).
-void load_index_file_into(const std::string &path, HostIndex &out, bool background, const std::function<void(HostIndex &)> &on_located = nullptr, bool lazy_records = false);
+// `trace_phases`: the loader's phases on stderr (the caller's GBWT_HIP_TRACE_OPEN: the loader itself never reads the environment).
+void load_index_file_into(const std::string &path, HostIndex &out, bool background, const std::function<void(HostIndex &)> &on_located = nullptr, bool lazy_records = false,
+                          bool trace_phases = false);
 
 // Writes the index back in the simple-sds format (GBWT v5; GBZ v1 container with an uncompressed
 // graph, version 3), following the Serialize impls src/gbwt.rs:389-400, src/gbz.rs:662-672,

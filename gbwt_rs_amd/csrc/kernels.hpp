@@ -148,7 +148,7 @@ struct LineCacheFill {
     uint64_t *seg_text;            // scratch, [2 * samples of all sequences]: {token bytes, label lengths} of every segment, then the token bytes in front of it
     uint32_t *flags;               // [1] zeroed by the caller; bit 0: a segment did not deliver its nodes (the cache is not used)
 };
-void launch_fill_line_cache(const DeviceIndex &ix, const LineCacheFill &f, hipStream_t stream);
+void launch_fill_line_cache(const DeviceIndex &ix, const LineCacheFill &f, bool packed, hipStream_t stream);   // packed: the handle has packed half-blocks (gbwt_hip_index::packed_blocks)
 // walker order of a segmented extraction: per-row segment counts -> rows sorted by count (descending, stable) and
 // level[j] = number of walkers in segments < j.  d_keys / d_rows: 2 x n scratch each (double buffers of the sort).
 size_t walker_order_temp_bytes(uint64_t n);

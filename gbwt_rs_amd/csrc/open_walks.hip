@@ -551,11 +551,10 @@ __global__ void __launch_bounds__(256) k_place_chunk_text(DeviceIndex ix, LineCa
 
 }  // namespace
 
-void launch_fill_line_cache(const DeviceIndex &ix, const LineCacheFill &f, hipStream_t stream) {
+void launch_fill_line_cache(const DeviceIndex &ix, const LineCacheFill &f, bool packed, hipStream_t stream) {
     if (f.paths == 0) return;
     const uint64_t walkers = static_cast<uint64_t>(f.max_samples) * f.paths;
-    const uint32_t packed = ix.gblocks != nullptr ? 1u : 0u;
-    if (walkers) hipLaunchKernelGGL(k_segment_text, dim3(grid_for(walkers, 256)), dim3(256), 0, stream, ix, f, packed);
+    if (walkers) hipLaunchKernelGGL(k_segment_text, dim3(grid_for(walkers, 256)), dim3(256), 0, stream, ix, f, packed ? 1u : 0u);
     hipLaunchKernelGGL(k_path_text, dim3(grid_for(f.paths, 256 / WAVE)), dim3(256), 0, stream, ix, f);
     if (f.chunks) hipLaunchKernelGGL(k_place_chunk_text, dim3(grid_for(f.chunks, 256)), dim3(256), 0, stream, ix, f);
 }

@@ -223,24 +223,22 @@ Labels labels_of(const gbwt_hip_index *ix) {
                   static_cast<uint32_t>(ix->host.alphabet_offset + 1)};
 }
 
-// The node labels in HBM, made once per handle by the first request for bases (any thread, any workspace).  A failure leaves the flag unset:
+// The node labels in HBM, made once per handle by the first request for bases (any thread, any workspace).  A failure marks nothing:
 // the next request tries again.
 void ensure_labels(const gbwt_hip_index *ix) {
-    if (ix->labels_made.load(std::memory_order_acquire)) return;
-    std::lock_guard<std::mutex> lock(ix->labels_lock);
-    if (ix->labels_made.load(std::memory_order_relaxed)) return;
-    const Strings &s = ix->host.sequences_labels;
-    HIP_CHECK(hipSetDevice(ix->device));
-    const uint64_t bytes = s.bytes.size(), offsets = s.offsets.size();
-    ix->label_bytes.reserve(bytes + LABEL_PAD);
-    ix->label_off.reserve(offsets * sizeof(uint64_t));
-    if (bytes) HIP_CHECK(hipMemcpy(ix->label_bytes.ptr, s.bytes.data(), bytes, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(ix->label_bytes.as<uint8_t>() + bytes, 0, LABEL_PAD));
-    HIP_CHECK(hipMemcpy(ix->label_off.ptr, s.offsets.data(), offsets * sizeof(uint64_t), hipMemcpyHostToDevice));
-    uint64_t longest = 0;
-    for (uint64_t k = 0; k + 1 < offsets; k++) longest = std::max<uint64_t>(longest, s.offsets[k + 1] - s.offsets[k]);
-    ix->max_label_len = longest;
-    ix->labels_made.store(true, std::memory_order_release);
+    ix->labels_built.ensure([ix]() {
+        const Strings &s = ix->host.sequences_labels;
+        HIP_CHECK(hipSetDevice(ix->device));
+        const uint64_t bytes = s.bytes.size(), offsets = s.offsets.size();
+        ix->label_bytes.reserve(bytes + LABEL_PAD);
+        ix->label_off.reserve(offsets * sizeof(uint64_t));
+        if (bytes) HIP_CHECK(hipMemcpy(ix->label_bytes.ptr, s.bytes.data(), bytes, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(ix->label_bytes.as<uint8_t>() + bytes, 0, LABEL_PAD));
+        HIP_CHECK(hipMemcpy(ix->label_off.ptr, s.offsets.data(), offsets * sizeof(uint64_t), hipMemcpyHostToDevice));
+        uint64_t longest = 0;
+        for (uint64_t k = 0; k + 1 < offsets; k++) longest = std::max<uint64_t>(longest, s.offsets[k + 1] - s.offsets[k]);
+        ix->max_label_len = longest;
+    });
 }
 
 void require_bases_capable(const gbwt_hip_index *ix) {

@@ -200,6 +200,25 @@ def test_loader_under_sanitizers(tmp_path):
     assert "accepted" in out.stdout
 
 
+def test_lazy_records_under_sanitizers(tmp_path):
+    """The host's record image built on first use (HostIndex::ensure_records) from a file of 4.5 MB whose last record starts lie past the
+    record bytes, loaded as an open from a file loads it (background, lazy_records, starts decoded elsewhere): the load finishes, and
+    every build -- a second one, two threads at once -- throws InvalidData without marking the records made.  g++ with
+    -fsanitize=address,undefined (host compiler, CPU only)."""
+    import shutil
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "lazy_records"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run([gxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", _lib.CSRC,
+                    os.path.join(root, "tests", "cpp", "lazy_records.cpp"), os.path.join(_lib.CSRC, "host_index.cpp"),
+                    os.path.join(_lib.CSRC, "sds_writer.cpp"), "-ldl", "-lpthread", "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe), str(tmp_path / "lazy.gbwt")], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "lazy records ok" in out.stdout
+
+
 def test_walk_kernel_keeps_four_waves_per_simd():
     """k_walk_direct is sized for four waves per SIMD = eight workgroups per CU: 128 VGPRs at most and nothing spilled.
     Round 4 lost a tenth of the headline for a few commits to a table decoder that kept sixteen more registers alive (135 VGPRs, three

@@ -443,7 +443,8 @@ def test_line_cache_serves_every_mode(tmp_path, monkeypatch, fill_mode):
     every request sizes and places its lines from them without a sizing pass, in ANY line mode (a P-line's text is the W-line's plus
     separators).  Lines of paths longer than one chunk (chunk boundaries inside and at the end of a segment), paths that visit nodes
     again, empty paths, duplicates and subsets in another order: asked for in all three modes, whichever comes first, against the oracle
-    and against a handle with the cache switched off (GBWT_HIP_LINE_CACHE=0: every request sizes its lines itself)."""
+    and against a handle with the cache switched off (GBWT_HIP_LINE_CACHE=0: every request sizes its lines itself), and against a handle
+    without packed half-blocks (GBWT_HIP_GATHER_LIMIT=0: the cache is filled on the full-width blocks)."""
     paths = [[2 * (1 + (7 * k + j) % 50) + ((k + j) % 3 == 0) for j in range(ln)] for k, ln in enumerate([0, 1, 9000, 4096, 4097, 12289, 5, 0, 8192, 300])]
     s = S.Synth.from_paths(paths, bidirectional=True).attach_gbz(seed=3)
     path = str(tmp_path / "cache.gbz")
@@ -453,14 +454,18 @@ def test_line_cache_serves_every_mode(tmp_path, monkeypatch, fill_mode):
     monkeypatch.setenv("GBWT_HIP_LINE_CACHE", "0")
     plain = G.GBZ.load(path)
     monkeypatch.delenv("GBWT_HIP_LINE_CACHE")
+    monkeypatch.setenv("GBWT_HIP_GATHER_LIMIT", "0")
+    full_width = G.GBZ.load(path)
+    monkeypatch.delenv("GBWT_HIP_GATHER_LIMIT")
     everything = list(range(len(paths)))
     first = [2, 0, 5, 9]
     assert dev.open_times()["line_sizes_ms"] > 0 and plain.open_times()["line_sizes_ms"] == 0
+    assert full_width.open_times()["line_sizes_ms"] > 0
     assert dev.path_lines(first, fill_mode) == oracle.path_lines(first, fill_mode)
     for mode in (0, 1, 2):
         for ids in (first, [5, 5, 2], everything, everything[::-1], [7], [3, 2]):
             got = dev.path_lines(ids, mode)
-            assert got == oracle.path_lines(ids, mode) == plain.path_lines(ids, mode), (fill_mode, mode, ids)
+            assert got == oracle.path_lines(ids, mode) == plain.path_lines(ids, mode) == full_width.path_lines(ids, mode), (fill_mode, mode, ids)
     out = tmp_path / "whole.gfa"
     dev.write_gfa(str(out))
     assert out.read_bytes() == oracle.gfa()
