@@ -69,6 +69,16 @@ class Lines(C.Structure):
     _fields_ = [("d_text", C.c_void_p), ("d_line_offsets", C.c_void_p), ("total", C.c_uint64), ("n", C.c_uint64)]
 
 
+class Components(C.Structure):
+    _fields_ = [("d_component", C.c_void_p), ("d_offsets", C.c_void_p), ("d_nodes", C.c_void_p), ("d_path_component", C.c_void_p),
+                ("min_node", C.c_uint64), ("slots", C.c_uint64), ("components", C.c_uint64), ("nodes", C.c_uint64), ("paths", C.c_uint64)]
+
+
+class ComponentsTimes(C.Structure):
+    _fields_ = [("hook_ms", C.c_float), ("jump_ms", C.c_float), ("shape_ms", C.c_float), ("hook_launches", C.c_uint32),
+                ("jump_launches", C.c_uint32), ("shape_launches", C.c_uint32)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -116,6 +126,12 @@ SIGNATURES = {
     "gbwt_hip_node_sequence": (_int, [_p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(C.c_uint8)]),
     "gbwt_hip_write_sequences": (_int, [_p, _p, C.c_char_p, _p, _u64, _int]),
     "gbwt_hip_last_sequences_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gbwt_hip_components_device": (_int, [_p, C.POINTER(Components)]),
+    "gbwt_hip_weakly_connected_components": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gbwt_hip_path_components": (_int, [_p, _p, _u64, _p]),
+    "gbwt_hip_last_components_ms": (_int, [_p, C.POINTER(ComponentsTimes)]),
+    "gbwt_hip_select_paths": (_int, [_p, _p, C.c_char_p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_write_sequences_contig": (_int, [_p, _p, C.c_char_p, C.c_char_p, _int]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_copy_path": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64)]),

@@ -12,6 +12,8 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBZ.path(path_id, orientation)   GBZ::path        src/gbz.rs:461-466
   GBZ.node_sequence(node_id)       GBZ::sequence    src/gbz.rs:292-298   (None for a node that does not exist)
   GBZ.path_sequences(ids, o)       gbz-extract's extract_sequence, src/bin/gbz-extract.rs:173-189 (bases of paths)
+  GBWT.weakly_connected_components()   GBZ::weakly_connected_components   src/gbz.rs:570-598
+  GBZ.select_paths(contig)         gbz-extract's select_paths, src/bin/gbz-extract.rs:196-264
 
 Every call goes through the C ABI of libgbwt_hip.so (hand-written HIP); "not found" is reported as
 None / a False entry of the validity mask, never as an exception.
@@ -22,7 +24,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BdState, GbwtHipError, Lines, Memory, OpenTimes, Paths, Pos, State, Stats, check
+from ._lib import BdState, Components, GbwtHipError, Lines, Memory, OpenTimes, Paths, Pos, State, Stats, check
 
 FORWARD, REVERSE = 0, 1  # support::Orientation, src/support.rs:30-47
 PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY = 0, 1, 2  # gbunzip's PathMode, src/bin/gbunzip.rs:63-76
@@ -293,6 +295,47 @@ class GBWT:
     def stream(self):
         return self._L.gbwt_hip_workspace_stream(self._ws)
 
+    # ---- graph topology -----------------------------------------------------------------------
+    def components_device(self):
+        """The weakly connected components as they lie in HBM (gbwt_hip_components_device): a Components struct -- d_component[slots] (slot s =
+        node id min_node + s; 0xFFFFFFFF for a node that does not exist), the CSR d_offsets[components + 1] / d_nodes[nodes], d_path_component[paths]
+        and the counts.  Made by the first call on the handle, valid while it is open."""
+        out = Components()
+        check(self._L.gbwt_hip_components_device(self._h, C.byref(out)))
+        return out
+
+    def components_csr(self):
+        """GBZ::weakly_connected_components (src/gbz.rs:570-598) as CSR: (offsets[u64, components + 1], node ids[u64]); the components in order of
+        their smallest node id, the nodes ascending inside."""
+        components, nodes = C.c_uint64(0), C.c_uint64(0)
+        check(self._L.gbwt_hip_weakly_connected_components(self._h, None, 0, None, 0, C.byref(components), C.byref(nodes)))
+        offsets = np.zeros(components.value + 1, dtype=np.uint64)
+        ids = np.zeros(max(1, nodes.value), dtype=np.uint64)
+        check(self._L.gbwt_hip_weakly_connected_components(self._h, _ptr(offsets), offsets.size, _ptr(ids), ids.size, C.byref(components), C.byref(nodes)))
+        return offsets, ids[: nodes.value]
+
+    def weakly_connected_components(self):
+        """GBZ::weakly_connected_components: a list of numpy arrays of node ids, in the reference's order."""
+        offsets, ids = self.components_csr()
+        return [ids[int(offsets[c]):int(offsets[c + 1])] for c in range(offsets.size - 1)]
+
+    def path_components(self, path_ids):
+        """The component of the first node of every path (uint32; 0xFFFFFFFF for an empty path): what select_paths looks up
+        (src/bin/gbz-extract.rs:243-246).  GbwtHipError(BAD_ARGUMENT) for an id that is no path."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        if ids.ndim != 1:
+            raise ValueError("path_ids must be one-dimensional")
+        out = np.zeros(ids.size, dtype=np.uint32)
+        check(self._L.gbwt_hip_path_components(self._h, _ptr(ids), ids.size, _ptr(out)))
+        return out
+
+    def last_components_ms(self):
+        """HIP-event time of the build that made the components of this handle and its launches (gbwt_hip_last_components_ms): a dict with
+        hook_ms, jump_ms, shape_ms, hook_launches, jump_launches, shape_launches."""
+        t = _lib.ComponentsTimes()
+        check(self._L.gbwt_hip_last_components_ms(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in _lib.ComponentsTimes._fields_}
+
     # ---- search -------------------------------------------------------------------------------
     def find(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
@@ -515,9 +558,33 @@ class GBZ(GBWT):
         check(self._L.gbwt_hip_node_sequence(self._h, int(node_id), buf, length.value, C.byref(length), C.byref(found)))
         return buf.raw[: length.value]
 
-    def write_sequences(self, path, path_ids=None, endmarker=0):
+    @staticmethod
+    def _contig(contig):
+        if contig is None or isinstance(contig, bytes):
+            return contig
+        if isinstance(contig, str):
+            return contig.encode()
+        raise TypeError("contig must be None, str or bytes")
+
+    def select_paths(self, contig=None):
+        """select_paths of gbz-extract (src/bin/gbz-extract.rs:196-264): every path id for contig=None; otherwise the ascending ids of every path
+        whose first node lies in a weakly connected component in which a path with that contig name starts.  GbwtHipError(BAD_ARGUMENT) with the
+        reference's messages: no contig names, an unknown contig, a contig no path carries."""
+        name = self._contig(contig)
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_select_paths(self._h, self._ws, name, None, 0, C.byref(total)))
+        out = np.zeros(max(1, total.value), dtype=np.uint64)
+        check(self._L.gbwt_hip_select_paths(self._h, self._ws, name, _ptr(out), out.size, C.byref(total)))
+        return out[: total.value]
+
+    def write_sequences(self, path, path_ids=None, endmarker=0, contig=None):
         """The files `gbz-extract -o path` writes (src/bin/gbz-extract.rs:266-294): the forward bases of the paths (None = all) with an
-        endmarker behind each (None: none), and `path`.names."""
+        endmarker behind each (None: none), and `path`.names.  contig=NAME is `gbz-extract -c NAME`: the paths select_paths(NAME) gives."""
+        if contig is not None:
+            if path_ids is not None:
+                raise ValueError("contig and path_ids exclude each other")
+            check(self._L.gbwt_hip_write_sequences_contig(self._h, self._ws, os.fsencode(path), self._contig(contig), self._endmarker(endmarker)))
+            return
         ids = None if path_ids is None else np.ascontiguousarray(path_ids, dtype=np.uint64)
         n = 0 if ids is None else ids.size
         if ids is not None and ids.size == 0:
@@ -533,5 +600,5 @@ class GBZ(GBWT):
         return out
 
 
-__all__ = ["GBWT", "GBZ", "GbwtHipError", "Lines", "Paths", "FORWARD", "REVERSE", "PATHS_DEFAULT", "PATHS_PAN_SN", "PATHS_REF_ONLY", "POS_DTYPE", "STATE_DTYPE", "BD_DTYPE", "encode_node",
+__all__ = ["GBWT", "GBZ", "GbwtHipError", "Components", "Lines", "Paths", "FORWARD", "REVERSE", "PATHS_DEFAULT", "PATHS_PAN_SN", "PATHS_REF_ONLY", "POS_DTYPE", "STATE_DTYPE", "BD_DTYPE", "encode_node",
            "decode_node", "flip_node", "encode_path", "device_count", "device_memory", "parse_file", "Pos", "State", "BdState"]

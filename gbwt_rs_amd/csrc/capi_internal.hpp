@@ -1,4 +1,4 @@
-// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, gfa.hip, comm.hip).
+// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, gfa.hip, comm.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -344,6 +344,15 @@ struct gbwt_hip_index {
     mutable gbwt_hip::LazyBuild labels_built;
     mutable gbwt_hip::DeviceBuffer label_bytes, label_off;
     mutable uint64_t max_label_len = 0;
+    // WEAKLY CONNECTED COMPONENTS IN HBM (capi_graph.hip: ensure_components), made by the first call that asks for them, never by an open:
+    // the component of every node slot, the CSR of the components (u64 offsets, u32 node ids) and the component of every path; the path
+    // components on the host as well (what select_paths reads).  Once per handle whichever thread asks first.
+    mutable gbwt_hip::LazyBuild components_built;
+    mutable gbwt_hip::DeviceBuffer comp_of, comp_offsets, comp_nodes, comp_paths;
+    mutable gbwt_hip::ComponentGeometry comp_geometry{0, 0};
+    mutable uint64_t comp_count = 0, comp_node_count = 0;
+    mutable std::vector<uint32_t> host_path_component;
+    mutable gbwt_hip_components_times comp_times{};
     gbwt_hip::DeviceIndex dev{};
     // The full-width two-step blocks (cblocks, as large as gblocks: 1.7 GB on the headline index) are only read by the loops for records
     // whose counts do not fit the packed half-blocks, by the pool-output kernel and by the serial walks at open: built at open when one of

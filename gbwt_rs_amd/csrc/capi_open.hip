@@ -853,6 +853,8 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
     if (ix.dev.cblocks != nullptr || ix.cblocks_built.made()) out->index_device_bytes += ix.cblocks.bytes;
     // (the node labels: by the first request for bases)
     if (ix.labels_built.made()) out->index_device_bytes += ix.label_bytes.bytes + ix.label_off.bytes;
+    // (the weakly connected components: by the first call for them)
+    if (ix.components_built.made()) out->index_device_bytes += ix.comp_of.bytes + ix.comp_offsets.bytes + ix.comp_nodes.bytes + ix.comp_paths.bytes;
     const HostIndex &h = ix.host;
     out->index_host_bytes = (h.records_made() ? h.data.size() + h.starts.size() * sizeof(uint64_t) : 0) + h.da_samples.size() * sizeof(uint64_t) + h.path_names.size() * sizeof(PathName) +
                             h.sample_names.bytes.size() + h.contig_names.bytes.size() + h.sequences_labels.bytes.size() + h.sequences_labels.offsets.size() * sizeof(uint64_t) +

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch wrappers of the gfx950 kernels (load_kernels.hip, walk_kernels.hip, query_kernels.hip).
+// kernels.hpp -- launch wrappers of the gfx950 kernels (load_kernels.hip, walk_kernels.hip, query_kernels.hip, components.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -198,6 +198,27 @@ void launch_starts_check(const uint32_t *d_starts32, const uint64_t *d_starts64,
 // label_len[s] = 0 for every potential node s < n whose forward record (2 s + 1) is empty or has no edge (GBZ::has_node); reads the record bytes
 // and starts on the device -- the host's image of them may not exist (HostIndex::ensure_records)
 void launch_mask_label_lengths(const DeviceIndex &ix, uint32_t *d_label_len, uint64_t n, hipStream_t s);
+
+// ---- graph topology (components.hip) -----------------------------------------------------------
+// NODE SLOTS: slot s = node id min_node + s, the numbering of k_mask_label_lengths (in a bidirectional index: forward record 2 s + 1,
+// reverse record 2 s + 2); min_node = node_id(first_node) (GBZ::min_node, src/gbz.rs:274-276), slots = node_id(alphabet_size - 1) - min_node + 1.
+struct ComponentGeometry { uint64_t min_node, slots; };
+constexpr uint32_t COMPONENT_NONE = 0xFFFFFFFFu;
+// labels: init (parent[s] = s), then hook passes (one lane per record) and jump passes (one lane per slot) until *d_changed stays 0
+void launch_component_init(uint32_t *d_parent, uint64_t slots, hipStream_t s);
+void launch_component_hook(const DeviceIndex &ix, const ComponentGeometry &g, uint32_t *d_parent, uint32_t *d_changed, hipStream_t s);
+void launch_component_jump(uint32_t *d_parent, uint64_t slots, uint32_t *d_changed, hipStream_t s);
+// output shaping.  Scratch of `slots` u32 each; label holds the converged labels and becomes the component of every slot (COMPONENT_NONE
+// for a slot whose node does not exist): launch_component_numbers leaves the number of components in rank[slots - 1] + flag[slots - 1];
+// launch_component_counts the nodes of every component (d_counts[components]); launch_component_csr the node ids in component order,
+// ascending inside a component (d_nodes[nodes]).
+struct ComponentShape { uint32_t *label, *first, *flag, *rank, *key, *value; void *temp; size_t temp_bytes; };
+size_t component_shape_temp_bytes(uint64_t slots);
+void launch_component_numbers(const DeviceIndex &ix, const ComponentGeometry &g, const ComponentShape &w, hipStream_t s);
+void launch_component_counts(const ComponentGeometry &g, const uint32_t *d_component, uint64_t components, uint64_t *d_counts, hipStream_t s);
+void launch_component_csr(const ComponentGeometry &g, const ComponentShape &w, uint64_t components, uint32_t *d_nodes, hipStream_t s);
+// d_out[p] = component of the first node of path p (sequence p * stride; COMPONENT_NONE for an empty path)
+void launch_path_components(const DeviceIndex &ix, const ComponentGeometry &g, const uint32_t *d_component, uint64_t paths, uint32_t stride, uint32_t *d_out, hipStream_t s);
 
 // inclusive scan of lengths[n] into offsets[1..n], offsets[0] = 0 (hipcub); temp storage managed by caller
 size_t scan_temp_bytes(uint64_t n);

@@ -116,6 +116,16 @@ __device__ __forceinline__ void record_bounds(const DeviceIndex &ix, uint64_t re
     else { start = ix.starts64[rec]; limit = ix.starts64[rec + 1]; }
 }
 
+// GBZ::has_node (src/gbz.rs:286-289; the real nodes are cached at :694-705) as the device states it, for the FORWARD record of a node: the
+// record is non-empty and holds an edge (BWT::id_iter skips the others, src/bwt.rs:341-351).  The one statement of that rule on the device
+// (k_mask_label_lengths, the components kernels).
+__device__ __forceinline__ bool record_is_real(const DeviceIndex &ix, uint64_t rec) {
+    if (rec >= ix.n_records) return false;
+    uint64_t a, b;
+    record_bounds(ix, rec, a, b);
+    return b > a && b <= ix.data_len && ix.data[a] != 0;
+}
+
 // Opens the record of GBWT node `node` the way GBWT::forward / find / extend do: None when
 // node < first_node, when the record id is out of range, when the slice is empty or sigma == 0.
 // On success the cursor stands right after the sigma varint.

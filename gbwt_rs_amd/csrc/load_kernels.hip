@@ -810,13 +810,7 @@ __global__ void __launch_bounds__(256) k_starts_check(const uint32_t *s32, const
 __global__ void __launch_bounds__(256) k_mask_label_lengths(DeviceIndex ix, uint32_t *label_len, uint64_t n) {
     const uint64_t s = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     if (s >= n) return;
-    const uint64_t rec = 2 * s + 1;
-    bool real = false;
-    if (rec < ix.n_records) {
-        const uint64_t a = ix.starts32 ? ix.starts32[rec] : ix.starts64[rec], b = ix.starts32 ? ix.starts32[rec + 1] : ix.starts64[rec + 1];
-        real = b > a && b <= ix.data_len && ix.data[a] != 0;
-    }
-    if (!real) label_len[s] = 0;
+    if (!record_is_real(ix, 2 * s + 1)) label_len[s] = 0;
 }
 
 void launch_mask_label_lengths(const DeviceIndex &ix, uint32_t *d_label_len, uint64_t n, hipStream_t s) {

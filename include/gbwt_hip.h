@@ -137,7 +137,7 @@ gbwt_hip_status gbwt_hip_get_stats(const gbwt_hip_index *index, gbwt_hip_stats *
  * need).  An index is replicated per GPU, so this is also the cost of one more rank.  index_host_bytes: the host image (record
  * bytes, starts, names, node labels).  workspace_device_bytes (0 for ws == NULL): all scratch of the workspace, of which rows_bytes are
  * the extracted rows (the CSR node ids) and text_bytes the formatted GFA lines and the bases of paths.  The node labels of a GBZ are in
- * index_device_bytes once the first request for bases has made them. */
+ * index_device_bytes once the first request for bases has made them, the weakly connected components once the first call for them has. */
 typedef struct {
     uint64_t index_device_bytes, index_host_bytes;
     uint64_t workspace_device_bytes, rows_bytes, text_bytes;
@@ -347,6 +347,54 @@ gbwt_hip_status gbwt_hip_write_sequences(const gbwt_hip_index *index, gbwt_hip_w
 /* Device time of the last request for bases on `ws` (HIP events): *walk_ms = the walk of its extraction, *sizes_ms = sizing and placing its rows
  * up to the host's one wait, *bases_ms = the chunk plan and the bases kernel. */
 gbwt_hip_status gbwt_hip_last_sequences_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *sizes_ms, float *bases_ms);
+
+/* ---- graph topology: weakly connected components, contig path selection -------------------------------------------------------------
+ * GBZ::weakly_connected_components (src/gbz.rs:570-598; known answer src/gbz/tests.rs:503-518): the node ids of the graph that the GBWT
+ * records describe, partitioned by "joined through an edge, whatever the orientations" (the successors and predecessors of both
+ * orientations of every node, EdgeIter with the ENDMARKER edge skipped, src/gbz.rs:819-855), the components in order of their smallest
+ * node id, the nodes ascending inside (DisjointSets::extract, src/support.rs:1551-1576).  A node exists by GBZ::has_node (src/gbz.rs:286-289):
+ * its forward record is non-empty and holds an edge.
+ *
+ * Components belong to the index.  They are computed on the device from the record bytes, the record starts and the endmarker -- what
+ * EVERY handle keeps, whatever its GBWT_HIP_OPEN_* flags, GBZ or bare GBWT -- by the first call below on a handle (once, whichever
+ * thread asks first; an open never makes them), stay in HBM (4 bytes per node slot, the CSR and 4 bytes per path) and are counted in
+ * gbwt_hip_memory_usage's index_device_bytes from then on.
+ *
+ * NODE SLOTS: slot s stands for node id min_node + s, min_node = GBZ::min_node (src/gbz.rs:274-276), slots = max_node + 1 - min_node
+ * (GBZ::max_node, :280-282): the domain of the reference's DisjointSets.
+ *
+ * gbwt_hip_components_device: the device-resident view, valid while the handle is open: d_component[slots] = component of the node of
+ * every slot (UINT32_MAX for a node that does not exist); component c = d_nodes[d_offsets[c] .. d_offsets[c + 1]) (u32 node ids);
+ * d_path_component[paths] as gbwt_hip_path_components. */
+typedef struct {
+    const uint32_t *d_component; const uint64_t *d_offsets; const uint32_t *d_nodes; const uint32_t *d_path_component;
+    uint64_t min_node, slots, components, nodes, paths;
+} gbwt_hip_components;
+gbwt_hip_status gbwt_hip_components_device(const gbwt_hip_index *index, gbwt_hip_components *out);
+/* GBZ::weakly_connected_components as a host CSR: out_offsets[components + 1], out_nodes[nodes] (node ids).  *components and *nodes
+ * always receive the counts; out_offsets == NULL and out_nodes == NULL is a size query; offsets_capacity < components + 1 or
+ * nodes_capacity < nodes -> GBWT_HIP_CAPACITY. */
+gbwt_hip_status gbwt_hip_weakly_connected_components(const gbwt_hip_index *index, uint64_t *out_offsets, uint64_t offsets_capacity, uint64_t *out_nodes,
+                                                     uint64_t nodes_capacity, uint64_t *components, uint64_t *nodes);
+/* out[k] = the component of path path_ids[k]: that of the first node of GBZ::path(id, Forward) (src/gbz.rs:461-466; what select_paths looks
+ * up, src/bin/gbz-extract.rs:243-246, 253-256), UINT32_MAX for an empty path (`if let Some(..)` there).  Path p is sequence 2 p of a
+ * bidirectional index (support::encode_path), sequence p of a unidirectional one.  An id >= paths -> GBWT_HIP_BAD_ARGUMENT. */
+gbwt_hip_status gbwt_hip_path_components(const gbwt_hip_index *index, const uint64_t *path_ids, uint64_t n, uint32_t *out);
+/* Device time (HIP events) of the build that made the components of this handle, and its launches: hook = the passes over the edge lists
+ * of all records, jump = the pointer-jumping passes over the labels, shape = component numbers, CSR and path components.
+ * GBWT_HIP_BAD_ARGUMENT before the components have been made. */
+typedef struct { float hook_ms, jump_ms, shape_ms; uint32_t hook_launches, jump_launches, shape_launches; } gbwt_hip_components_times;
+gbwt_hip_status gbwt_hip_last_components_ms(const gbwt_hip_index *index, gbwt_hip_components_times *out);
+/* select_paths of gbz-extract (src/bin/gbz-extract.rs:196-264), for an index with metadata and path names: contig == NULL selects every
+ * path of the metadata; otherwise the ascending ids of every path whose first node lies in a component in which a path with contig name
+ * `contig` starts.  *total always receives the number of paths; out_path_ids == NULL is a size query; capacity < total ->
+ * GBWT_HIP_CAPACITY.  GBWT_HIP_BAD_ARGUMENT with the reference's messages (:212-224): "Cannot select a contig without contig names",
+ * "The graph does not contain contig NAME", "The graph does not contain any paths for contig NAME"; and without metadata or path names. */
+gbwt_hip_status gbwt_hip_select_paths(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *contig, uint64_t *out_path_ids, uint64_t capacity,
+                                      uint64_t *total);
+/* gbz-extract -c contig -o path (extract_sequences, src/bin/gbz-extract.rs:266-294): gbwt_hip_write_sequences for the paths
+ * gbwt_hip_select_paths selects, byte for byte. */
+gbwt_hip_status gbwt_hip_write_sequences_contig(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *path, const char *contig, int endmarker);
 
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex

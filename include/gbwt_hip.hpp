@@ -10,6 +10,7 @@
 // (the reference shares &GBZ across rayon workers, src/bin/gbunzip.rs:421-434): use clone_workspace().
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <optional>
@@ -167,6 +168,19 @@ public:
         return extend_backward(std::vector<BidirectionalState>{state}, std::vector<uint64_t>{node})[0];
     }
 
+    // ---- graph topology
+    // GBZ::weakly_connected_components (src/gbz.rs:570-598): the node ids of every component, the components in order of their smallest
+    // node id, the nodes ascending inside.  Made on the device by the first call on the handle.
+    std::vector<std::vector<size_t>> weakly_connected_components() const {
+        uint64_t components = 0, nodes = 0;
+        check(gbwt_hip_weakly_connected_components(index_.get(), nullptr, 0, nullptr, 0, &components, &nodes));
+        std::vector<uint64_t> offsets(components + 1, 0), ids(nodes);
+        check(gbwt_hip_weakly_connected_components(index_.get(), offsets.data(), offsets.size(), ids.data(), ids.size(), &components, &nodes));
+        std::vector<std::vector<size_t>> out(components);
+        for (uint64_t c = 0; c < components; c++) out[c].assign(ids.begin() + offsets[c], ids.begin() + offsets[c + 1]);
+        return out;
+    }
+
     const gbwt_hip_index *handle() const { return index_.get(); }
     gbwt_hip_workspace *workspace() const { return ws_.get(); }
 
@@ -263,6 +277,20 @@ public:
     // gbz-extract -o path: `path` and `path`.names for all paths (src/bin/gbz-extract.rs:266-294)
     void write_sequences(const std::string &path, int endmarker = 0) const {
         check(gbwt_hip_write_sequences(index_.get(), ws_.get(), path.c_str(), nullptr, 0, endmarker));
+    }
+    // select_paths of gbz-extract (src/bin/gbz-extract.rs:196-264): every path (nullopt), or the paths of the components in which a path
+    // with that contig name starts; throws Error with the reference's messages
+    std::vector<size_t> select_paths(const std::optional<std::string> &contig = std::nullopt) const {
+        const char *name = contig ? contig->c_str() : nullptr;
+        uint64_t total = 0;
+        check(gbwt_hip_select_paths(index_.get(), ws_.get(), name, nullptr, 0, &total));
+        std::vector<uint64_t> ids(std::max<uint64_t>(total, 1));
+        check(gbwt_hip_select_paths(index_.get(), ws_.get(), name, ids.data(), ids.size(), &total));
+        return std::vector<size_t>(ids.begin(), ids.begin() + total);
+    }
+    // gbz-extract -c contig -o path
+    void write_sequences(const std::string &path, const std::string &contig, int endmarker) const {
+        check(gbwt_hip_write_sequences_contig(index_.get(), ws_.get(), path.c_str(), contig.c_str(), endmarker));
     }
     // the lines gbunzip writes for these paths (mode 0 = P-lines, 1 = W-lines) and the whole GFA file
     std::string path_lines(const std::vector<uint64_t> &path_ids, int mode) const {
