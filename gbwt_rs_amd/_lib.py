@@ -126,6 +126,10 @@ SIGNATURES = {
     "gbwt_hip_node_sequence": (_int, [_p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(C.c_uint8)]),
     "gbwt_hip_write_sequences": (_int, [_p, _p, C.c_char_p, _p, _u64, _int]),
     "gbwt_hip_last_sequences_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gbwt_hip_tags_device": (_int, [_p, _p, _p, _u64, _p, _u64, _p, C.POINTER(_u64)]),
+    "gbwt_hip_tags": (_int, [_p, _p, _p, _u64, _p, _u64, _p, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gbwt_hip_write_tag_array": (_int, [_p, _p, C.c_char_p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_last_tags_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gbwt_hip_components_device": (_int, [_p, C.POINTER(Components)]),
     "gbwt_hip_weakly_connected_components": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_path_components": (_int, [_p, _p, _u64, _p]),

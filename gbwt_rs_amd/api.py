@@ -14,6 +14,7 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBZ.path_sequences(ids, o)       gbz-extract's extract_sequence, src/bin/gbz-extract.rs:173-189 (bases of paths)
   GBWT.weakly_connected_components()   GBZ::weakly_connected_components   src/gbz.rs:570-598
   GBZ.select_paths(contig)         gbz-extract's select_paths, src/bin/gbz-extract.rs:196-264
+  GBZ.tag_array(ids, sa)           gbz-extract's extract_tag_array, src/bin/gbz-extract.rs:346-371, 408-482 (tags of a suffix array)
 
 Every call goes through the C ABI of libgbwt_hip.so (hand-written HIP); "not found" is reported as
 None / a False entry of the validity mask, never as an exception.
@@ -591,6 +592,51 @@ class GBZ(GBWT):
             ids = np.zeros(1, dtype=np.uint64)             # (an empty list is not NULL = all paths)
         ptr = None if ids is None else ids.ctypes.data
         check(self._L.gbwt_hip_write_sequences(self._h, self._ws, os.fsencode(path), ptr, n, self._endmarker(endmarker)))
+
+    def text_length(self, path_ids):
+        """The length of the text gbz-extract's `sequences` mode writes for these paths (the bases of every path and one endmarker each): the
+        expected_len of its `tag-array` mode (src/bin/gbz-extract.rs:408-411)."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        expected = C.c_uint64(0)
+        check(self._L.gbwt_hip_tags(self._h, self._ws, _ptr(ids), ids.size, None, 0, None, C.byref(expected), None))
+        return expected.value
+
+    def tag_array(self, path_ids, sa, return_runs=False):
+        """gbz-extract's tag array (src/bin/gbz-extract.rs:346-371, 408-470) for the text of these paths: TAG[i] = the graph position of
+        text position sa[i] -- ((node id << 11) | (orientation << 10)) + the offset inside the node, 0 for an endmarker -- as a numpy uint64
+        array [, the number of runs].  GbwtHipError(INVALID_DATA) for a value >= text_length(path_ids)."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        sa = np.ascontiguousarray(sa, dtype=np.uint64)
+        if sa.ndim != 1:
+            raise ValueError("sa must be one-dimensional")
+        tags = np.zeros(sa.size, dtype=np.uint64)
+        runs = C.c_uint64(0)
+        if sa.size:
+            check(self._L.gbwt_hip_tags(self._h, self._ws, _ptr(ids), ids.size, _ptr(sa), sa.size, _ptr(tags), None, C.byref(runs)))
+        else:
+            self.text_length(ids)                          # (the checks of the request, nothing to look up)
+        return (tags, runs.value) if return_runs else tags
+
+    def tags_device(self, path_ids, d_sa, count, d_tags):
+        """gbwt_hip_tags_device: `d_sa` and `d_tags` are device pointers (int) to `count` uint64 values in HBM -- any slice of a suffix array --
+        and stay there; returns the runs of these entries."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        runs = C.c_uint64(0)
+        check(self._L.gbwt_hip_tags_device(self._h, self._ws, _ptr(ids), ids.size, C.c_void_p(int(d_sa)), count, C.c_void_p(int(d_tags)), C.byref(runs)))
+        return runs.value
+
+    def write_tag_array(self, base, sa_skip=1):
+        """`gbz-extract -m tag-array -o base` (src/bin/gbz-extract.rs:408-482): reads `base`.names and `base`.sa (sa_skip leading values
+        skipped), writes `base`.tags; returns the reference's "Tag array runs"."""
+        runs = C.c_uint64(0)
+        check(self._L.gbwt_hip_write_tag_array(self._h, self._ws, os.fsencode(base), sa_skip, C.byref(runs)))
+        return runs.value
+
+    def last_tags_ms(self):
+        """(walk ms, plan ms, gather kernel ms) of the last request for tags (HIP events; the plan's while it is reused)."""
+        walk, plan, gather = C.c_float(0), C.c_float(0), C.c_float(0)
+        check(self._L.gbwt_hip_last_tags_ms(self._ws, C.byref(walk), C.byref(plan), C.byref(gather)))
+        return walk.value, plan.value, gather.value
 
     def path_lines_device(self, path_ids, mode):
         """The same lines left in HBM: a Lines struct (device pointers to the text and to the n + 1 line offsets)."""

@@ -402,6 +402,17 @@ struct gbwt_hip_workspace {
     int seq_reverse = 0, seq_endmarker = -1, seq_slot = 0;
     uint64_t seq_total = 0;
     hipEvent_t sev[3] = {nullptr, nullptr, nullptr};
+    // Tags of a suffix array (tags.hip).  The PLAN of the last list of path ids: for every position of the text's walk -- the nodes of the rows and
+    // one endmarker position behind each -- its node (tag_node, u32) and its text offset (tag_off, u64, one more entry = the text length), and
+    // the sampled top level (tag_top: the position that holds text offset h << TAG_SHIFT; u32, u64 from 2^32 positions).  tag_rows: the text
+    // offset of every row (+ the text length) on the host.  tag_state: run count, last tags and the out-of-range flag of a request;
+    // tag_sa* / tag_out*: the staging of the host and file forms.  Times of the last request: the plan's are kept with the plan.
+    gbwt_hip::DeviceBuffer tag_node, tag_off, tag_top, tag_state, tag_sa, tag_sa2, tag_out, tag_out2;
+    bool tag_planned = false, tag_timed = false, tag_wide = false;
+    std::vector<uint64_t> tag_key, tag_rows;
+    uint64_t tag_positions = 0, tag_text_len = 0;
+    float tag_walk_ms = 0, tag_plan_ms = 0, tag_gather_ms = 0;
+    hipEvent_t tev[2] = {nullptr, nullptr};
     gbwt_hip::HostCopier copier;      // pinned staging of the large device-to-host copies
     uint64_t follow_total = 0, lines_total = 0;
     ~gbwt_hip_workspace() {
@@ -409,12 +420,30 @@ struct gbwt_hip_workspace {
         for (auto &e : qev) if (e) (void)hipEventDestroy(e);
         for (auto &e : gev) if (e) (void)hipEventDestroy(e);
         for (auto &e : sev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : tev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (pinned_words) (void)hipHostFree(pinned_words);
     }
 };
 
 namespace gbwt_hip {
+// The labels of a handle as the kernels see them (sequences.hip, tags.hip): node v (GBWT-encoded, 2 id + o) has label bytes[off[s] .. off[s + 1])
+// with s = (v & ~1 - first_node) / 2 (GBZ::graph_node_to_sequence, src/gbz.rs:246-255); a node outside [first_node, first_node + 2 n) has none.
+struct Labels { const uint8_t *bytes; const uint64_t *off; uint64_t n; uint32_t first_node; };
+
+__device__ __forceinline__ void label_of(const Labels &L, uint32_t node, uint64_t &lo, uint64_t &hi) {
+    const uint32_t fwd = node & ~1u;
+    const uint64_t s = (static_cast<uint64_t>(fwd) - L.first_node) / 2;
+    if (fwd < L.first_node || s >= L.n) { lo = 0; hi = 0; return; }
+    lo = L.off[s]; hi = L.off[s + 1];
+}
+
+// sequences.hip: the labels of a handle in HBM (made by the first request that needs them), and the test every entry point for bases and
+// tags starts with (InvalidData for a bare GBWT or a handle without GBWT_HIP_OPEN_EXTRACT)
+Labels labels_of(const gbwt_hip_index *ix);
+void ensure_labels(const gbwt_hip_index *ix);
+void require_bases_capable(const gbwt_hip_index *ix);
+
 // Device -> pageable host memory over the workspace's copy threads (GBWT_HIP_COPY_THREADS, default 8), each with two pinned staging
 // buffers and a stream of its own (capi_extract.hip)
 void copy_to_host(gbwt_hip_workspace *ws, void *dst, const void *src, size_t bytes, size_t piece = HostCopier::CHUNK);

@@ -33,17 +33,6 @@ constexpr uint32_t BASES_THREADS = 256, PER_THREAD = 4, BATCH = BASES_THREADS * 
 constexpr uint64_t LABEL_PAD = 64;                 // zero bytes behind the last label (the dword loads of a unit read up to 3 bytes past it)
 constexpr uint64_t REVERSE_BIT = uint64_t(1) << 63;
 
-// The labels of a handle as the kernels see them: node v (GBWT-encoded, 2 id + o) has label bytes[off[s] .. off[s + 1]) with
-// s = (v & ~1 - first_node) / 2 (GBZ::graph_node_to_sequence, src/gbz.rs:246-255); a node outside [first_node, first_node + 2 n) has none.
-struct Labels { const uint8_t *bytes; const uint64_t *off; uint64_t n; uint32_t first_node; };
-
-__device__ __forceinline__ void label_of(const Labels &L, uint32_t node, uint64_t &lo, uint64_t &hi) {
-    const uint32_t fwd = node & ~1u;
-    const uint64_t s = (static_cast<uint64_t>(fwd) - L.first_node) / 2;
-    if (fwd < L.first_node || s >= L.n) { lo = 0; hi = 0; return; }
-    lo = L.off[s]; hi = L.off[s + 1];
-}
-
 // support::COMPLEMENT (src/support.rs:87-99)
 __host__ __device__ __forceinline__ uint8_t complement(uint32_t c) {
     switch (c) {
@@ -218,6 +207,10 @@ __global__ void __launch_bounds__(BASES_THREADS) k_bases(const uint32_t *nodes, 
     }
 }
 
+}  // namespace
+
+namespace gbwt_hip {
+
 Labels labels_of(const gbwt_hip_index *ix) {
     return Labels{ix->label_bytes.as<uint8_t>(), ix->label_off.as<uint64_t>(), static_cast<uint64_t>(ix->host.sequences_labels.size()),
                   static_cast<uint32_t>(ix->host.alphabet_offset + 1)};
@@ -246,7 +239,7 @@ void require_bases_capable(const gbwt_hip_index *ix) {
     if (!(ix->caps & GBWT_HIP_OPEN_EXTRACT)) throw InvalidData("the handle was not opened for extraction (GBWT_HIP_OPEN_EXTRACT)");
 }
 
-}  // namespace
+}  // namespace gbwt_hip
 
 // The bases of a batch of paths, computed ONCE into device memory (text buffer of `slot`: ws->seq_text or seq_text2; row k at
 // [offsets[k], offsets[k + 1]) of ws->seq_offsets).  The request is remembered in the workspace: the fill call after a size query, and the

@@ -136,7 +136,8 @@ gbwt_hip_status gbwt_hip_get_stats(const gbwt_hip_index *index, gbwt_hip_stats *
  * descriptors, rank blocks, tables, samples, GFA tables; the full-width two-step blocks are counted once they have been built (on first
  * need).  An index is replicated per GPU, so this is also the cost of one more rank.  index_host_bytes: the host image (record
  * bytes, starts, names, node labels).  workspace_device_bytes (0 for ws == NULL): all scratch of the workspace, of which rows_bytes are
- * the extracted rows (the CSR node ids) and text_bytes the formatted GFA lines and the bases of paths.  The node labels of a GBZ are in
+ * the extracted rows (the CSR node ids) and text_bytes the formatted GFA lines and the bases of paths; the plan and the staging of
+ * gbwt_hip_tags* are workspace scratch.  The node labels of a GBZ are in
  * index_device_bytes once the first request for bases has made them, the weakly connected components once the first call for them has. */
 typedef struct {
     uint64_t index_device_bytes, index_host_bytes;
@@ -347,6 +348,46 @@ gbwt_hip_status gbwt_hip_write_sequences(const gbwt_hip_index *index, gbwt_hip_w
 /* Device time of the last request for bases on `ws` (HIP events): *walk_ms = the walk of its extraction, *sizes_ms = sizing and placing its rows
  * up to the host's one wait, *bases_ms = the chunk plan and the bases kernel. */
 gbwt_hip_status gbwt_hip_last_sequences_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *sizes_ms, float *bases_ms);
+
+/* ---- tags of a suffix array (GBZ handles opened with GBWT_HIP_OPEN_EXTRACT) ------------------------------------------------------------
+ * gbz-extract's `tag-array` mode (src/bin/gbz-extract.rs:296-482).  The TEXT of paths p_0 .. p_{n-1}, in the order given, is what
+ * gbwt_hip_write_sequences writes for them: the forward bases of p_0, one endmarker, the bases of p_1, one endmarker, ...; row k starts at
+ * off_k = sum of (len_j + 1) over j < k, and expected_len = off_{n-1} + len_{n-1} + 1 (0 for n = 0).  The TAG of text position t
+ * (extract_path / encode_start, :346-371) is 0 for an endmarker, and otherwise ((v << 11) | (o << 10)) + w for the base that lies w bases --
+ * in reading direction, also on a reverse node -- behind the first base of the step (node id v, orientation o: 1 = reverse) of GBZ::path(p_k,
+ * Forward) it falls into.  Nodes are nodes, never segments.  The sum is a plain 64-bit addition: like the reference (its FIXME) nothing guards
+ * labels longer than 1 024 bases, whose w carries into the orientation bit and the node id.  TAG[i] = tag(SA[i]): what the reference's two
+ * sorts compute when the values they read are a permutation of 0 .. expected_len - 1; for other input the reference's result is unspecified,
+ * ours is this gather.  A value >= expected_len is GBWT_HIP_INVALID_DATA and is never read through.  RUNS: the number of i with
+ * TAG[i] != TAG[i - 1], the first entry of a request counting as one (the reference's "Tag array runs").
+ *
+ * The map from text offsets to walk positions (the PLAN: 12 bytes per node of the paths + 1 per 8 text positions) is made by the first
+ * request for a list of path ids and stays on the workspace, counted in workspace_device_bytes, while the list stays the same.  A plan, or
+ * the staging of a request, that does not fit in free device memory is GBWT_HIP_CAPACITY with a message that says what was needed.
+ * Preconditions as for gbwt_hip_path_sequences*: GBWT_HIP_BAD_ARGUMENT for a bare GBWT, a handle without GBWT_HIP_OPEN_EXTRACT, and a path id
+ * without a sequence 2 id.
+ *
+ * gbwt_hip_tags_device: d_tags[i] = tag(d_sa[i]) for i < count, both in HBM; `count` is any number of entries (a slice of a suffix array
+ * is fine); *runs (may be NULL) for these entries.  After GBWT_HIP_INVALID_DATA the contents of d_tags are unspecified (nothing was written
+ * for the offending entries). */
+gbwt_hip_status gbwt_hip_tags_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, const uint64_t *d_sa, uint64_t count,
+                                     uint64_t *d_tags, uint64_t *runs);
+/* The same with host pointers.  *expected_len (may be NULL) always receives the text length; sa == NULL and tags == NULL is the size query
+ * that returns it.  After an error `tags` is untouched. */
+gbwt_hip_status gbwt_hip_tags(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, const uint64_t *sa, uint64_t count,
+                              uint64_t *tags, uint64_t *expected_len, uint64_t *runs);
+/* gbz-extract -m tag-array -o base (extract_tag_array, :408-482): reads `base`.names (one line per path: first tab field = path id, last =
+ * bases; the metadata is not needed) and `base`.sa (little-endian u64: sa_skip values are skipped -- the reference's default is 1 -- then
+ * expected_len are read), writes `base`.tags: exactly 8 * expected_len bytes, the tags as little-endian u64 without a header.  The suffix array
+ * streams through two pairs of device buffers in batches bounded by bytes (GBWT_HIP_TAG_BATCH_MIB, read at each call; default 256) while a
+ * writer thread moves the previous batch of tags to the file.  GBWT_HIP_INVALID_DATA: an empty .names ("No path names found"), a line that
+ * does not parse, a path whose walked bases differ from its line ("Invalid length for path P: expected L, got M"), a value out of range;
+ * GBWT_HIP_IO_ERROR: a file that cannot be opened, a .sa shorter than sa_skip + expected_len values.  No .tags file stays behind a failure. */
+gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *base_path, uint64_t sa_skip, uint64_t *runs);
+/* Device time of the last request for tags on `ws` (HIP events): *walk_ms = the walk of the plan's extraction, *plan_ms = the rest of the plan
+ * (both those of the request that made the plan, while it is reused), *gather_ms = the gather kernel, summed over the batches of a file
+ * (0 for a size query). */
+gbwt_hip_status gbwt_hip_last_tags_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *plan_ms, float *gather_ms);
 
 /* ---- graph topology: weakly connected components, contig path selection -------------------------------------------------------------
  * GBZ::weakly_connected_components (src/gbz.rs:570-598; known answer src/gbz/tests.rs:503-518): the node ids of the graph that the GBWT

@@ -278,6 +278,25 @@ public:
     void write_sequences(const std::string &path, int endmarker = 0) const {
         check(gbwt_hip_write_sequences(index_.get(), ws_.get(), path.c_str(), nullptr, 0, endmarker));
     }
+    // gbz-extract -m tag-array (src/bin/gbz-extract.rs:408-482): TAG[i] = the graph position of text position sa[i] of the text of these
+    // paths (gbwt_hip_tags); `runs` receives the reference's "Tag array runs"
+    std::vector<uint64_t> tag_array(const std::vector<uint64_t> &path_ids, const std::vector<uint64_t> &sa, uint64_t *runs = nullptr) const {
+        std::vector<uint64_t> tags(sa.size());
+        check(gbwt_hip_tags(index_.get(), ws_.get(), path_ids.data(), path_ids.size(), sa.data(), sa.size(), tags.data(), nullptr, runs));
+        return tags;
+    }
+    // the length of that text: the bases of the paths and one endmarker each
+    uint64_t text_length(const std::vector<uint64_t> &path_ids) const {
+        uint64_t expected_len = 0;
+        check(gbwt_hip_tags(index_.get(), ws_.get(), path_ids.data(), path_ids.size(), nullptr, 0, nullptr, &expected_len, nullptr));
+        return expected_len;
+    }
+    // gbz-extract -m tag-array -o base: `base`.names + `base`.sa -> `base`.tags; returns the runs
+    uint64_t write_tag_array(const std::string &base, uint64_t sa_skip = 1) const {
+        uint64_t runs = 0;
+        check(gbwt_hip_write_tag_array(index_.get(), ws_.get(), base.c_str(), sa_skip, &runs));
+        return runs;
+    }
     // select_paths of gbz-extract (src/bin/gbz-extract.rs:196-264): every path (nullopt), or the paths of the components in which a path
     // with that contig name starts; throws Error with the reference's messages
     std::vector<size_t> select_paths(const std::optional<std::string> &contig = std::nullopt) const {
