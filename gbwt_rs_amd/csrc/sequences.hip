@@ -241,6 +241,12 @@ void require_bases_capable(const gbwt_hip_index *ix) {
 
 }  // namespace gbwt_hip
 
+// k_bases counts the bytes of a batch of BATCH positions, the slack of its units included, in 32 bits (after ensure_labels)
+static const char *const LABELS_TOO_LONG = "node labels too long for the bases kernel (32-bit offsets inside a batch of 1 024 positions)";
+static bool labels_fit_a_batch(const gbwt_hip_index *ix) {
+    return static_cast<uint64_t>(BATCH) * ix->max_label_len + 16 * BASES_THREADS + 16 <= 0xFFFFFFFFull;
+}
+
 // The bases of a batch of paths, computed ONCE into device memory (text buffer of `slot`: ws->seq_text or seq_text2; row k at
 // [offsets[k], offsets[k + 1]) of ws->seq_offsets).  The request is remembered in the workspace: the fill call after a size query, and the
 // copy-out of gbwt_hip_path_sequences after gbwt_hip_path_sequences_device, find the bases there.
@@ -269,8 +275,7 @@ static gbwt_hip_status sequences_compute(const gbwt_hip_index *ix, gbwt_hip_work
             return GBWT_HIP_OK;
         }
         ensure_labels(ix);
-        if (static_cast<uint64_t>(BATCH) * ix->max_label_len + 16 * BASES_THREADS + 16 > 0xFFFFFFFFull)
-            return fail(GBWT_HIP_UNSUPPORTED, "node labels too long for the bases kernel (32-bit offsets inside a batch of 1 024 positions)");
+        if (!labels_fit_a_batch(ix)) return fail(GBWT_HIP_UNSUPPORTED, LABELS_TOO_LONG);
         // 1. the rows: GBZ::path(id, orientation) = sequence 2 id + orientation (support::encode_path); an id whose sequence does not exist
         // walks nothing and gets an empty row (as in gbwt_hip_extract_paths)
         std::vector<uint64_t> seq_ids(n);
@@ -434,6 +439,8 @@ gbwt_hip_status gbwt_hip_write_sequences(const gbwt_hip_index *ix, gbwt_hip_work
         else for (uint64_t p = 0; p < h.path_names.size(); p++) ids.push_back(p);
         for (uint64_t p : ids)
             if (p >= h.path_names.size() || 2 * p >= h.sequences) return fail(GBWT_HIP_BAD_ARGUMENT, "path id out of range");
+        ensure_labels(ix);                                   // refused before a file is created or emptied
+        if (!ids.empty() && !labels_fit_a_batch(ix)) return fail(GBWT_HIP_UNSUPPORTED, LABELS_TOO_LONG);
         uint64_t budget = uint64_t(1) << 30;
         if (const char *v = std::getenv("GBWT_HIP_SEQ_BATCH_MIB")) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10)) << 20;
         // bytes of every path: exact from the line cache of the index (summed label lengths of the forward path); else nodes x the mean label

@@ -37,6 +37,8 @@ def lib():
         L.gbwt_synth_from_file.argtypes = [C.c_char_p, C.c_char_p, u64]
         L.gbwt_synth_attach_gbz.restype = C.c_int
         L.gbwt_synth_attach_gbz.argtypes = [p, p, u64, u64]
+        L.gbwt_synth_attach_gbz_labeled.restype = C.c_int
+        L.gbwt_synth_attach_gbz_labeled.argtypes = [p, p, u64, u64, p, u64]
         L.gbwt_synth_free.restype = None
         L.gbwt_synth_free.argtypes = [p]
         L.gbwt_synth_data.restype = p
@@ -83,10 +85,10 @@ class Synth:
 
     @classmethod
     def from_paths(cls, paths, bidirectional=True):
-        """paths: list of lists of GBWT-encoded nodes (2 * id + orientation)."""
+        """paths: list of lists (or numpy arrays) of GBWT-encoded nodes (2 * id + orientation)."""
         offsets = np.zeros(len(paths) + 1, dtype=np.uint64)
         np.cumsum([len(p) for p in paths], out=offsets[1:])
-        flat = np.array([x for p in paths for x in p] or [0], dtype=np.uint64)
+        flat = np.concatenate([np.asarray(p, dtype=np.uint64).reshape(-1) for p in paths] + [np.zeros(1, dtype=np.uint64)])
         return cls(lib().gbwt_synth_from_paths(offsets.ctypes.data, flat.ctypes.data, len(paths), int(bidirectional)))
 
     @classmethod
@@ -158,10 +160,20 @@ class Synth:
             return [0] if self.paths else []                   # the chain generators: path 0
         return [p for p in range(len(names)) if names[p][0] == self.generic_sample]
 
-    def attach_gbz(self, segment_starts=(), seed=1):
-        """Adds path metadata + node labels (+ a node-to-segment translation) so that the index can be saved as a GBZ."""
+    def attach_gbz(self, segment_starts=(), seed=1, label_lengths=None):
+        """Adds path metadata + node labels (+ a node-to-segment translation) so that the index can be saved as a GBZ.  The labels are 1-3
+        seeded bases per node, or -- with `label_lengths` -- label_lengths[q] seeded bases for potential node q (node id q + 1; one entry per
+        node id up to the largest; ids without a record keep empty labels, a node with a record needs at least one base).  The index must be
+        bidirectional and node id 1 must be on a path."""
         starts = np.array(list(segment_starts) or [0], dtype=np.uint64)
-        rc = self._L.gbwt_synth_attach_gbz(self._h, starts.ctypes.data, len(segment_starts), seed)
+        if label_lengths is None:
+            rc = self._L.gbwt_synth_attach_gbz(self._h, starts.ctypes.data, len(segment_starts), seed)
+        else:
+            lengths = np.ascontiguousarray(label_lengths, dtype=np.uint64)
+            if lengths.ndim != 1:
+                raise ValueError("label_lengths must be one-dimensional")
+            pad = lengths if lengths.size else np.zeros(1, dtype=np.uint64)
+            rc = self._L.gbwt_synth_attach_gbz_labeled(self._h, starts.ctypes.data, len(segment_starts), seed, pad.ctypes.data, lengths.size)
         if rc != 0:
             raise ValueError(f"gbwt_synth_attach_gbz failed ({rc})")
         return self

@@ -66,6 +66,13 @@ gbwt_synth *gbwt_synth_from_paths(const uint64_t *offsets, const uint64_t *nodes
  * next start and is named "seg<start>" (src/graph.rs:84-89, 186-218).  Returns 0 on success. */
 int gbwt_synth_attach_gbz(gbwt_synth *s, const uint64_t *segment_starts, uint64_t n_segments, uint64_t seed);
 
+/* The same with chosen label lengths: label_lengths[q] = bases of potential node q (node id q + 1), n_lengths = the potential nodes of the
+ * index ((alphabet_size - 1) / 2); the bases are seeded ACGT.  Potential nodes without a record keep empty labels whatever their entry says;
+ * a node with a record needs at least one base (return 4).  label_lengths == NULL is gbwt_synth_attach_gbz.  The constraints of above stay:
+ * a bidirectional index whose smallest node id is 1 (some path visits node id 1). */
+int gbwt_synth_attach_gbz_labeled(gbwt_synth *s, const uint64_t *segment_starts, uint64_t n_segments, uint64_t seed, const uint64_t *label_lengths,
+                                  uint64_t n_lengths);
+
 /* One index out of several chains (gbwt_synth_chain*): the graph components of a whole-genome GBZ.  The node ids of part k follow those
  * of part k - 1 (its ids are shifted, its records re-encoded with the shifted edge lists), its paths follow the paths of part k - 1, and
  * the endmarker records are merged.  `path_names` = 4 numbers per path of the merged index (sample, contig, phase, fragment: PathName,

@@ -546,8 +546,13 @@ gbwt_synth *gbwt_synth_from_paths(const uint64_t *offsets, const uint64_t *nodes
 }
 
 int gbwt_synth_attach_gbz(gbwt_synth *g, const uint64_t *segment_starts, uint64_t n_segments, uint64_t seed) {
+    return gbwt_synth_attach_gbz_labeled(g, segment_starts, n_segments, seed, nullptr, 0);
+}
+
+int gbwt_synth_attach_gbz_labeled(gbwt_synth *g, const uint64_t *segment_starts, uint64_t n_segments, uint64_t seed, const uint64_t *label_lengths, uint64_t n_lengths) {
     gbwt_hip::HostIndex &ix = g->index;
     if (!ix.bidirectional || ix.alphabet_offset != 1) return 1;   // node id v <-> label v - 1, as the translation assumes
+    if (label_lengths && n_lengths != (ix.alphabet_size > 2 ? (ix.alphabet_size - 1) / 2 : 0)) return 3;   // one length per potential node
     const uint64_t n = ix.sequences / 2;
     ix.has_metadata = true;
     ix.metadata_flags = 7;
@@ -569,10 +574,19 @@ int gbwt_synth_attach_gbz(gbwt_synth *g, const uint64_t *segment_starts, uint64_
     for (uint64_t q = 0; q < potential; q++) {
         const uint64_t rec = 2 * q + first - ix.alphabet_offset;
         const bool exists = rec < ix.records() && ix.starts[rec + 1] > ix.starts[rec] && ix.data[ix.starts[rec]] != 0;
-        if (exists) {
+        if (exists && !label_lengths) {
             real++;
             const uint64_t len = 1 + (rng.next() >> 62) % 3;
             for (uint64_t k = 0; k < len; k++) ix.sequences_labels.bytes.push_back("ACGT"[rng.next() >> 62]);
+        } else if (exists) {                                      // the requested length, 32 bases per draw
+            if (label_lengths[q] == 0) return 4;                  // (a node that exists has bases)
+            real++;
+            uint64_t word = 0;
+            for (uint64_t k = 0; k < label_lengths[q]; k++) {
+                if ((k & 31) == 0) word = rng.next();
+                ix.sequences_labels.bytes.push_back("ACGT"[word & 3]);
+                word >>= 2;
+            }
         }
         ix.sequences_labels.offsets.push_back(ix.sequences_labels.bytes.size());
     }
