@@ -79,6 +79,14 @@ class ComponentsTimes(C.Structure):
                 ("jump_launches", C.c_uint32), ("shape_launches", C.c_uint32)]
 
 
+class ReferencePath(C.Structure):
+    _fields_ = [("path_id", C.c_uint64), ("len", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64)]
+
+
+class ReferencePosition(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("pos", Pos)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -136,6 +144,13 @@ SIGNATURES = {
     "gbwt_hip_last_components_ms": (_int, [_p, C.POINTER(ComponentsTimes)]),
     "gbwt_hip_select_paths": (_int, [_p, _p, C.c_char_p, _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_write_sequences_contig": (_int, [_p, _p, C.c_char_p, C.c_char_p, _int]),
+    "gbwt_hip_reference_sample_names": (_int, [_p, _int, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_reference_paths": (_int, [_p, _int, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_path_positions_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(_p), C.POINTER(_p), C.POINTER(_u64)]),
+    "gbwt_hip_path_positions": (_int, [_p, _p, _p, _u64, _u64, _p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_reference_positions": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_last_positions_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gbwt_hip_last_positions_rounds": (_int, [_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_copy_path": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64)]),

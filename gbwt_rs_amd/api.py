@@ -15,6 +15,7 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBWT.weakly_connected_components()   GBZ::weakly_connected_components   src/gbz.rs:570-598
   GBZ.select_paths(contig)         gbz-extract's select_paths, src/bin/gbz-extract.rs:196-264
   GBZ.tag_array(ids, sa)           gbz-extract's extract_tag_array, src/bin/gbz-extract.rs:346-371, 408-482 (tags of a suffix array)
+  GBZ.reference_positions(interval)   GBZ::reference_positions   src/gbz.rs:600-657   (reference_sample_names / reference_paths: 146-196)
 
 Every call goes through the C ABI of libgbwt_hip.so (hand-written HIP); "not found" is reported as
 None / a False entry of the validity mask, never as an exception.
@@ -33,6 +34,8 @@ PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY = 0, 1, 2  # gbunzip's PathMode, src
 POS_DTYPE = np.dtype([("node", "<u8"), ("offset", "<u8")])
 STATE_DTYPE = np.dtype([("node", "<u8"), ("start", "<u8"), ("end", "<u8")])
 BD_DTYPE = np.dtype([("forward", STATE_DTYPE), ("reverse", STATE_DTYPE)])
+REFPATH_DTYPE = np.dtype([("path_id", "<u8"), ("len", "<u8"), ("first", "<u8"), ("count", "<u8")])      # gbwt_hip_reference_path
+REFPOS_DTYPE = np.dtype([("offset", "<u8"), ("node", "<u8"), ("pos_offset", "<u8")])                    # gbwt_hip_reference_position
 
 
 def encode_node(node_id, orientation):  # support::encode_node, src/support.rs:155-157
@@ -638,6 +641,82 @@ class GBZ(GBWT):
         check(self._L.gbwt_hip_last_tags_ms(self._ws, C.byref(walk), C.byref(plan), C.byref(gather)))
         return walk.value, plan.value, gather.value
 
+    # ---- reference positions ---------------------------------------------------------------------
+    def reference_sample_names(self, also_generic):
+        """GBZ::reference_sample_names (src/gbz.rs:183-196): the names of the GBWT tag `reference_samples` (split at ' ') and, with
+        also_generic, `_gbwt_ref`, those that the metadata's sample dictionary holds.  Nothing without metadata."""
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_reference_sample_names(self._h, int(bool(also_generic)), None, 0, C.byref(total)))
+        buf = C.create_string_buffer(max(1, total.value))
+        check(self._L.gbwt_hip_reference_sample_names(self._h, int(bool(also_generic)), buf, total.value, C.byref(total)))
+        return [name.decode() for name in buf.raw[: total.value].split(b"\n")[:-1]]
+
+    def reference_paths(self, also_generic=True):
+        """The ids (uint64, ascending) of the paths whose sample is a reference sample (src/gbz.rs:609-629).  GbwtHipError(BAD_ARGUMENT)
+        without metadata."""
+        count = C.c_uint64(0)
+        check(self._L.gbwt_hip_reference_paths(self._h, int(bool(also_generic)), None, 0, C.byref(count)))
+        out = np.zeros(max(1, count.value), dtype=np.uint64)
+        check(self._L.gbwt_hip_reference_paths(self._h, int(bool(also_generic)), _ptr(out), out.size, C.byref(count)))
+        return out[: count.value]
+
+    def path_positions_csr(self, path_ids, interval):
+        """gbwt_hip_path_positions: (paths[REFPATH_DTYPE, n], positions[REFPOS_DTYPE, total]); the positions of row k are
+        positions[paths[k].first : paths[k].first + paths[k].count]."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        if ids.ndim != 1:
+            raise ValueError("path_ids must be one-dimensional")
+        paths = np.zeros(ids.size, dtype=REFPATH_DTYPE)
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_path_positions(self._h, self._ws, _ptr(ids), ids.size, int(interval), _ptr(paths), None, 0, C.byref(total)))
+        positions = np.zeros(max(1, total.value), dtype=REFPOS_DTYPE)
+        check(self._L.gbwt_hip_path_positions(self._h, self._ws, _ptr(ids), ids.size, int(interval), None, _ptr(positions), positions.size, C.byref(total)))
+        return paths, positions[: total.value]
+
+    @staticmethod
+    def _reference_rows(paths, positions):
+        rows = []
+        for p in paths:
+            part = positions[int(p["first"]):int(p["first"] + p["count"])]
+            rows.append((int(p["path_id"]), int(p["len"]), part["offset"].copy(), np.stack([part["node"], part["pos_offset"]], axis=1)))
+        return rows
+
+    def path_positions(self, path_ids, interval):
+        """GBZ::reference_positions' rule (src/gbz.rs:630-648) for any forward path ids, in the order given, a duplicate as a row of its own:
+        a list of (id, len, offsets uint64[k], positions uint64[k, 2] = (node, offset) of bwt::Pos).  About every `interval` bases the base
+        offset of a node start and the GBWT position of that visit; len = the bases of the path."""
+        return self._reference_rows(*self.path_positions_csr(path_ids, interval))
+
+    def path_positions_device(self, path_ids, interval):
+        """The same left in HBM: (d_paths, d_positions, total) -- device pointers (int) to n gbwt_hip_reference_path and `total`
+        gbwt_hip_reference_position (24 bytes), valid until the next request for positions on this workspace."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        d_paths, d_positions, total = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        check(self._L.gbwt_hip_path_positions_device(self._h, self._ws, _ptr(ids), ids.size, int(interval), C.byref(d_paths), C.byref(d_positions), C.byref(total)))
+        return d_paths.value or 0, d_positions.value or 0, total.value
+
+    def reference_positions(self, interval):
+        """GBZ::reference_positions(interval) (src/gbz.rs:600-657): for every reference path, ascending, (id, len, offsets uint64[k],
+        positions uint64[k, 2]).  GbwtHipError: BAD_ARGUMENT without metadata, UNSUPPORTED for a bare GBWT."""
+        n, total = C.c_uint64(0), C.c_uint64(0)
+        check(self._L.gbwt_hip_reference_positions(self._h, self._ws, int(interval), None, 0, C.byref(n), None, 0, C.byref(total)))
+        paths = np.zeros(max(1, n.value), dtype=REFPATH_DTYPE)
+        positions = np.zeros(max(1, total.value), dtype=REFPOS_DTYPE)
+        check(self._L.gbwt_hip_reference_positions(self._h, self._ws, int(interval), _ptr(paths), paths.size, C.byref(n), _ptr(positions), positions.size, C.byref(total)))
+        return self._reference_rows(paths[: n.value], positions[: total.value])
+
+    def last_positions_ms(self):
+        """(walk ms, selection ms, offsets walk ms) of the last request for positions (HIP events)."""
+        walk, select, offsets = C.c_float(0), C.c_float(0), C.c_float(0)
+        check(self._L.gbwt_hip_last_positions_ms(self._ws, C.byref(walk), C.byref(select), C.byref(offsets)))
+        return walk.value, select.value, offsets.value
+
+    def last_positions_rounds(self):
+        """(pointer-doubling rounds that marked something, launches behind the extraction) of the last request for positions."""
+        rounds, launches = C.c_uint32(0), C.c_uint32(0)
+        check(self._L.gbwt_hip_last_positions_rounds(self._ws, C.byref(rounds), C.byref(launches)))
+        return rounds.value, launches.value
+
     def path_lines_device(self, path_ids, mode):
         """The same lines left in HBM: a Lines struct (device pointers to the text and to the n + 1 line offsets)."""
         ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
@@ -646,5 +725,5 @@ class GBZ(GBWT):
         return out
 
 
-__all__ = ["GBWT", "GBZ", "GbwtHipError", "Components", "Lines", "Paths", "FORWARD", "REVERSE", "PATHS_DEFAULT", "PATHS_PAN_SN", "PATHS_REF_ONLY", "POS_DTYPE", "STATE_DTYPE", "BD_DTYPE", "encode_node",
+__all__ = ["GBWT", "GBZ", "GbwtHipError", "Components", "Lines", "Paths", "FORWARD", "REVERSE", "PATHS_DEFAULT", "PATHS_PAN_SN", "PATHS_REF_ONLY", "POS_DTYPE", "STATE_DTYPE", "BD_DTYPE", "REFPATH_DTYPE", "REFPOS_DTYPE", "encode_node",
            "decode_node", "flip_node", "encode_path", "device_count", "device_memory", "parse_file", "Pos", "State", "BdState"]

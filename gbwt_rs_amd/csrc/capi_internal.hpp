@@ -413,7 +413,19 @@ struct gbwt_hip_workspace {
     uint64_t tag_positions = 0, tag_text_len = 0;
     float tag_walk_ms = 0, tag_plan_ms = 0, tag_gather_ms = 0;
     hipEvent_t tev[2] = {nullptr, nullptr};
-    gbwt_hip::HostCopier copier;      // pinned staging of the large device-to-host copies
+    // Reference positions (refpos.hip, capi_refpos.hip).  Scratch of the last request, per position (node of its rows): rp_off (u64 bases in
+    // front of it), rp_mark (u64: its label length, then whether it is kept), rp_jump (two u32 jump arrays, then its u64 slot); rp_rows: the
+    // sequence ids, path ids and segment counts of the rows; rp_flags: a word per pointer-doubling round, one for the walk.  Results:
+    // rp_paths[n], rp_positions[rp_total], and the request they answer (rp_key, rp_interval).  Events around the selection (rev[0] ..
+    // rev[1]) and the walk that writes the positions (rev[1] .. rev[2]).
+    gbwt_hip::DeviceBuffer rp_off, rp_mark, rp_jump, rp_rows, rp_flags, rp_paths, rp_positions;
+    bool rp_cached = false, rp_timed = false;
+    std::vector<uint64_t> rp_key;
+    uint64_t rp_interval = 0, rp_total = 0;
+    uint32_t rp_rounds = 0, rp_launches = 0;
+    float rp_walk_ms = 0, rp_select_ms = 0, rp_offsets_ms = 0;
+    hipEvent_t rev[3] = {nullptr, nullptr, nullptr};
+    gbwt_hip::HostCopier copier;     // pinned staging of the large device-to-host copies
     uint64_t follow_total = 0, lines_total = 0;
     ~gbwt_hip_workspace() {
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
@@ -421,6 +433,7 @@ struct gbwt_hip_workspace {
         for (auto &e : gev) if (e) (void)hipEventDestroy(e);
         for (auto &e : sev) if (e) (void)hipEventDestroy(e);
         for (auto &e : tev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : rev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (pinned_words) (void)hipHostFree(pinned_words);
     }

@@ -865,7 +865,8 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
                                            &ws->order_keys, &ws->order_rows, &ws->order_counts, &ws->order_level, &ws->order_temp, &ws->in_a, &ws->in_b, &ws->out_a,
                                            &ws->out_valid, &ws->follow_off, &ws->gfa_a, &ws->gfa_b, &ws->gfa_c, &ws->gfa_text, &ws->gfa_text2, &ws->gfa_valid, &ws->gfa_chunk_first,
                                            &ws->gfa_chunks, &ws->gfa_plan, &ws->seq_text, &ws->seq_text2, &ws->seq_offsets, &ws->tag_node, &ws->tag_off, &ws->tag_top, &ws->tag_state,
-                                           &ws->tag_sa, &ws->tag_sa2, &ws->tag_out, &ws->tag_out2});
+                                           &ws->tag_sa, &ws->tag_sa2, &ws->tag_out, &ws->tag_out2, &ws->rp_off, &ws->rp_mark, &ws->rp_jump, &ws->rp_rows, &ws->rp_flags,
+                                           &ws->rp_paths, &ws->rp_positions});
         out->rows_bytes = ws->nodes.bytes;
         out->rows_chunks = ws->nodes.chunks.size();
         out->text_bytes = ws->gfa_text.bytes + ws->gfa_text2.bytes + ws->seq_text.bytes + ws->seq_text2.bytes;

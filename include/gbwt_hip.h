@@ -437,6 +437,51 @@ gbwt_hip_status gbwt_hip_select_paths(const gbwt_hip_index *index, gbwt_hip_work
  * gbwt_hip_select_paths selects, byte for byte. */
 gbwt_hip_status gbwt_hip_write_sequences_contig(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *path, const char *contig, int endmarker);
 
+/* ---- reference positions (GBZ handles opened with GBWT_HIP_OPEN_GFA) --------------------------------------------------------------------
+ * GBZ::reference_positions (src/gbz.rs:600-657, result type ReferencePath :1255-1266; known answer src/gbz/tests.rs:521-567): for a forward
+ * path p (sequence 2 p) with nodes v_0 .. v_{m-1}, off_0 = 0 and off_{k+1} = off_k + sequence_len(node_id(v_k)), the path's length in bases
+ * len = off_m and the KEPT visits i_0 = 0 (if m > 0), i_{j+1} = the first k > i_j with off_k >= off_{i_j} + interval (the sum saturates at
+ * 2^64 - 1; interval = 0 keeps every visit), each as (off_k, Pos{v_k, o_k}) with Pos_0 = GBWT::start(2 p), Pos_{k+1} = GBWT::forward(Pos_k).
+ * An empty path has len = 0 and no positions.  Base offsets and lengths are u64 throughout.
+ *
+ * The walk, the offsets, the selection (pointer doubling over the successor of every visit, no chain serial in the path length) and the LF
+ * steps that carry the in-record offset all run on the device; scratch is 24 bytes per node of the requested paths on the workspace,
+ * counted in workspace_device_bytes.  A request whose paths hold more than 2^32 - 1 nodes together is GBWT_HIP_UNSUPPORTED (positions are
+ * indexed in 32 bits inside); scratch or results that do not fit in free device memory are GBWT_HIP_CAPACITY.  GBWT_HIP_UNSUPPORTED for a
+ * bare GBWT (no node labels), GBWT_HIP_BAD_ARGUMENT for a handle opened without GBWT_HIP_OPEN_GFA; GBWT_HIP_DEVICE_ERROR when a walker
+ * met another node than the extracted row holds (an inconsistent index). */
+typedef struct { uint64_t path_id, len, first, count; } gbwt_hip_reference_path;   /* its positions: [first, first + count) of the request's */
+typedef struct { uint64_t offset; gbwt_hip_pos pos; } gbwt_hip_reference_position; /* 24 bytes */
+/* GBZ::reference_sample_names (src/gbz.rs:183-196): the names of the GBWT tag `reference_samples`, split at ' ', then (also_generic != 0)
+ * `_gbwt_ref`, those that the metadata's sample dictionary holds, each followed by '\n', in out[0 .. *total).  Host only.  out == NULL is a
+ * size query; capacity < *total -> GBWT_HIP_CAPACITY.  Without metadata: nothing (*total = 0). */
+gbwt_hip_status gbwt_hip_reference_sample_names(const gbwt_hip_index *index, int also_generic, char *out, uint64_t capacity, uint64_t *total);
+/* The reference paths (src/gbz.rs:609-629): the ids, ascending, of the paths whose sample is one of those names.  Host only.  *count always
+ * receives their number; out_ids == NULL is a size query; capacity < *count -> GBWT_HIP_CAPACITY.  No reference samples, or no path names:
+ * no paths, GBWT_HIP_OK.  No metadata: GBWT_HIP_BAD_ARGUMENT (the reference unwraps it). */
+gbwt_hip_status gbwt_hip_reference_paths(const gbwt_hip_index *index, int also_generic, uint64_t *out_ids, uint64_t capacity, uint64_t *count);
+/* The general form: any forward path ids, in the order given; a duplicate gets a row of its own; an id >= paths is GBWT_HIP_BAD_ARGUMENT.
+ * d_paths[n] and d_positions[*total] stay in HBM on the workspace, valid until the next request for positions on it. */
+gbwt_hip_status gbwt_hip_path_positions_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, uint64_t interval,
+                                               const gbwt_hip_reference_path **d_paths, const gbwt_hip_reference_position **d_positions, uint64_t *total);
+/* The same copied to host buffers: out_paths[n] (may be NULL), out_positions[*total]; out_positions == NULL is a size query,
+ * positions_capacity < *total -> GBWT_HIP_CAPACITY (out_paths is filled all the same).  The fill call that repeats the request of a size
+ * query does not compute again. */
+gbwt_hip_status gbwt_hip_path_positions(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, uint64_t interval,
+                                        gbwt_hip_reference_path *out_paths, gbwt_hip_reference_position *out_positions, uint64_t positions_capacity, uint64_t *total);
+/* GBZ::reference_positions(interval): gbwt_hip_reference_paths(also_generic = 1) followed by gbwt_hip_path_positions.  *n_paths and *total
+ * always receive the counts; out_paths == NULL and out_positions == NULL is a size query; paths_capacity < *n_paths or
+ * positions_capacity < *total -> GBWT_HIP_CAPACITY. */
+gbwt_hip_status gbwt_hip_reference_positions(const gbwt_hip_index *index, gbwt_hip_workspace *ws, uint64_t interval, gbwt_hip_reference_path *out_paths,
+                                             uint64_t paths_capacity, uint64_t *n_paths, gbwt_hip_reference_position *out_positions, uint64_t positions_capacity,
+                                             uint64_t *total);
+/* Device time of the last request for positions on `ws` (HIP events): *walk_ms = the walk kernel of its extraction, *select_ms = label
+ * lengths, scans, successors and the pointer-doubling rounds up to the host's wait for the total, *offsets_ms = the LF walk that carries the
+ * in-record offsets and writes the positions. */
+gbwt_hip_status gbwt_hip_last_positions_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *select_ms, float *offsets_ms);
+/* Of the same request: the pointer-doubling rounds that marked something, and the kernels and scans it launched behind its extraction. */
+gbwt_hip_status gbwt_hip_last_positions_rounds(const gbwt_hip_workspace *ws, uint32_t *rounds, uint32_t *launches);
+
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex
  * (src/bin/gbunzip.rs:27, 421-434).  Sharded over GPUs -- one process per GPU, the index replicated, path p on rank p mod world

@@ -51,6 +51,12 @@ struct Rows {
     std::vector<uint32_t> row(size_t k) const { return std::vector<uint32_t>(nodes.begin() + offsets[k], nodes.begin() + offsets[k + 1]); }
 };
 
+// gbz::ReferencePath (src/gbz.rs:1255-1266): a reference path, its length in bases, and (base offset of a node start, GBWT position of that visit) pairs
+struct ReferencePath {
+    size_t id, len;
+    std::vector<std::pair<size_t, Pos>> positions;
+};
+
 class GBWT {
 public:
     // serialize::load_from::<GBWT | GBZ>(path)
@@ -310,6 +316,34 @@ public:
     // gbz-extract -c contig -o path
     void write_sequences(const std::string &path, const std::string &contig, int endmarker) const {
         check(gbwt_hip_write_sequences_contig(index_.get(), ws_.get(), path.c_str(), contig.c_str(), endmarker));
+    }
+    // GBZ::reference_sample_ids' paths (src/gbz.rs:167-176, 609-629): the ids of the paths of the reference samples, ascending
+    std::vector<size_t> reference_paths(bool also_generic = true) const {
+        uint64_t count = 0;
+        check(gbwt_hip_reference_paths(index_.get(), also_generic ? 1 : 0, nullptr, 0, &count));
+        std::vector<uint64_t> ids(std::max<uint64_t>(count, 1));
+        check(gbwt_hip_reference_paths(index_.get(), also_generic ? 1 : 0, ids.data(), ids.size(), &count));
+        return std::vector<size_t>(ids.begin(), ids.begin() + count);
+    }
+    // The rule of GBZ::reference_positions for any forward paths, in the order given (gbwt_hip_path_positions)
+    std::vector<ReferencePath> path_positions(const std::vector<uint64_t> &path_ids, size_t interval) const {
+        uint64_t total = 0;
+        std::vector<gbwt_hip_reference_path> rows(std::max<size_t>(path_ids.size(), 1));
+        check(gbwt_hip_path_positions(index_.get(), ws_.get(), path_ids.data(), path_ids.size(), interval, rows.data(), nullptr, 0, &total));
+        std::vector<gbwt_hip_reference_position> positions(std::max<uint64_t>(total, 1));
+        check(gbwt_hip_path_positions(index_.get(), ws_.get(), path_ids.data(), path_ids.size(), interval, nullptr, positions.data(), positions.size(), &total));
+        std::vector<ReferencePath> out(path_ids.size());
+        for (size_t k = 0; k < path_ids.size(); k++) {
+            out[k].id = rows[k].path_id; out[k].len = rows[k].len;
+            for (uint64_t q = rows[k].first; q < rows[k].first + rows[k].count; q++) out[k].positions.emplace_back(positions[q].offset, positions[q].pos);
+        }
+        return out;
+    }
+    // GBZ::reference_positions(interval, _) (src/gbz.rs:600-657): every reference and generic path, a position about every `interval` bases
+    // at the start of a node.  Throws Error without metadata (the reference unwraps it).
+    std::vector<ReferencePath> reference_positions(size_t interval) const {
+        const std::vector<size_t> ids = reference_paths(true);
+        return path_positions(std::vector<uint64_t>(ids.begin(), ids.end()), interval);
     }
     // the lines gbunzip writes for these paths (mode 0 = P-lines, 1 = W-lines) and the whole GFA file
     std::string path_lines(const std::vector<uint64_t> &path_ids, int mode) const {
