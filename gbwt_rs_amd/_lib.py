@@ -79,6 +79,15 @@ class ComponentsTimes(C.Structure):
                 ("jump_launches", C.c_uint32), ("shape_launches", C.c_uint32)]
 
 
+class EdgeRows(C.Structure):
+    _fields_ = [("d_offsets", C.c_void_p), ("d_edges", C.c_void_p), ("d_valid", C.c_void_p), ("total", C.c_uint64), ("n", C.c_uint64)]
+
+
+class GraphText(C.Structure):
+    _fields_ = [("d_text", C.c_void_p), ("header_bytes", C.c_uint64), ("segment_bytes", C.c_uint64), ("link_bytes", C.c_uint64),
+                ("segments", C.c_uint64), ("links", C.c_uint64)]
+
+
 class ReferencePath(C.Structure):
     _fields_ = [("path_id", C.c_uint64), ("len", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64)]
 
@@ -144,6 +153,16 @@ SIGNATURES = {
     "gbwt_hip_last_components_ms": (_int, [_p, C.POINTER(ComponentsTimes)]),
     "gbwt_hip_select_paths": (_int, [_p, _p, C.c_char_p, _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_write_sequences_contig": (_int, [_p, _p, C.c_char_p, C.c_char_p, _int]),
+    "gbwt_hip_node_ids": (_int, [_p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_edges": (_int, [_p, _p, _p, _p, _u64, _int, _p, _p, _u64, C.POINTER(_u64), _p]),
+    "gbwt_hip_edges_device": (_int, [_p, _p, _p, _p, _u64, _int, C.POINTER(EdgeRows)]),
+    "gbwt_hip_segments": (_int, [_p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_node_segments": (_int, [_p, _p, _u64, _p, _p]),
+    "gbwt_hip_links": (_int, [_p, _p, _p, _p, _u64, _int, _p, _p, _u64, C.POINTER(_u64), _p]),
+    "gbwt_hip_links_device": (_int, [_p, _p, _p, _p, _u64, _int, C.POINTER(EdgeRows)]),
+    "gbwt_hip_graph_lines_device": (_int, [_p, _p, C.POINTER(GraphText)]),
+    "gbwt_hip_graph_lines": (_int, [_p, _p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_last_graph_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gbwt_hip_reference_sample_names": (_int, [_p, _int, _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_reference_paths": (_int, [_p, _int, _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_path_positions_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(_p), C.POINTER(_p), C.POINTER(_u64)]),

@@ -16,6 +16,9 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBZ.select_paths(contig)         gbz-extract's select_paths, src/bin/gbz-extract.rs:196-264
   GBZ.tag_array(ids, sa)           gbz-extract's extract_tag_array, src/bin/gbz-extract.rs:346-371, 408-482 (tags of a suffix array)
   GBZ.reference_positions(interval)   GBZ::reference_positions   src/gbz.rs:600-657   (reference_sample_names / reference_paths: 146-196)
+  GBWT.node_iter / successors / predecessors        GBZ::node_iter, successors, predecessors   src/gbz.rs:312-353 (EdgeIter 819-892)
+  GBZ.node_to_segment / segment_iter / segment_successors / segment_predecessors   src/gbz.rs:370-440 (SegmentIter, LinkIter 896-1016)
+  GBZ.graph_lines()                gbunzip's H-, S- and L-lines   src/bin/gbunzip.rs:193-332
 
 Every call goes through the C ABI of libgbwt_hip.so (hand-written HIP); "not found" is reported as
 None / a False entry of the validity mask, never as an exception.
@@ -26,7 +29,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BdState, Components, GbwtHipError, Lines, Memory, OpenTimes, Paths, Pos, State, Stats, check
+from ._lib import BdState, Components, EdgeRows, GbwtHipError, GraphText, Lines, Memory, OpenTimes, Paths, Pos, State, Stats, check
 
 FORWARD, REVERSE = 0, 1  # support::Orientation, src/support.rs:30-47
 PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY = 0, 1, 2  # gbunzip's PathMode, src/bin/gbunzip.rs:63-76
@@ -340,6 +343,72 @@ class GBWT:
         check(self._L.gbwt_hip_last_components_ms(self._h, C.byref(t)))
         return {name: getattr(t, name) for name, _ in _lib.ComponentsTimes._fields_}
 
+    # ---- the graph: nodes and edges (any handle) --------------------------------------------------
+    def node_iter(self):
+        """GBZ::node_iter (src/gbz.rs:312-317): the ids of the nodes that exist (GBZ::has_node), ascending, as a numpy uint64 array."""
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_node_ids(self._h, None, 0, C.byref(total)))
+        out = np.zeros(max(1, total.value), dtype=np.uint64)
+        check(self._L.gbwt_hip_node_ids(self._h, _ptr(out), out.size, C.byref(total)))
+        return out[: total.value]
+
+    @staticmethod
+    def _queries(ids, orientations):
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        orient = np.ascontiguousarray(np.broadcast_to(np.asarray(orientations), ids.shape), dtype=np.uint8)
+        if ids.ndim != 1:
+            raise ValueError("ids must be one-dimensional")
+        return ids, orient
+
+    def _rows_csr(self, fn, ids, orientations, predecessors):
+        ids, orient = self._queries(ids, orientations)
+        offsets = np.zeros(ids.size + 1, dtype=np.uint64)
+        valid = np.zeros(ids.size, dtype=np.uint8)
+        total = C.c_uint64(0)
+        check(fn(self._h, self._ws, _ptr(ids), _ptr(orient), ids.size, int(bool(predecessors)), _ptr(offsets), None, 0, C.byref(total), _ptr(valid)))
+        out = np.zeros(max(1, total.value), dtype=np.uint64)
+        check(fn(self._h, self._ws, _ptr(ids), _ptr(orient), ids.size, int(bool(predecessors)), _ptr(offsets), _ptr(out), out.size, C.byref(total), _ptr(valid)))
+        return offsets, out[: total.value], valid.astype(bool)
+
+    def _rows_device(self, fn, ids, orientations, predecessors):
+        ids, orient = self._queries(ids, orientations)
+        out = EdgeRows()
+        check(fn(self._h, self._ws, _ptr(ids), _ptr(orient), ids.size, int(bool(predecessors)), C.byref(out)))
+        return out
+
+    def _one_row(self, rows):
+        offsets, out, valid = rows
+        return [(int(x) >> 1, int(x) & 1) for x in out] if valid[0] else None
+
+    def edges_csr(self, node_ids, orientations, predecessors=False):
+        """GBZ::successors / predecessors (src/gbz.rs:327-353) for a batch of (node id, orientation): (offsets[u64, n + 1], edges[u64], valid[bool]);
+        an edge is 2 * id + orientation; valid[k] is False, with an empty row, where the reference returns None.  `orientations`: an array, or
+        one value for all."""
+        return self._rows_csr(self._L.gbwt_hip_edges, node_ids, orientations, predecessors)
+
+    def edges_device(self, node_ids, orientations, predecessors=False):
+        """The same rows left in HBM: an EdgeRows struct (d_offsets u64[n + 1], d_edges u64[total], d_valid u8[n]), valid until the next edges /
+        links request on this workspace.  rows_to_host() copies them out."""
+        return self._rows_device(self._L.gbwt_hip_edges_device, node_ids, orientations, predecessors)
+
+    def rows_to_host(self, rows):
+        """(offsets, edges, valid) of an edges_device() / links_device() result (through torch views of the workspace's memory)."""
+        import torch
+        from . import dist as D
+        device = torch.device("cuda", self._device)
+        offsets = D.device_view(rows.d_offsets, (rows.n + 1) * 8, torch.uint8, device).cpu().numpy().view(np.uint64)
+        edges = D.device_view(rows.d_edges, rows.total * 8, torch.uint8, device).cpu().numpy().view(np.uint64) if rows.total else np.zeros(0, np.uint64)
+        valid = D.device_view(rows.d_valid, rows.n, torch.uint8, device).cpu().numpy() if rows.n else np.zeros(0, np.uint8)
+        return offsets.copy(), edges.copy(), valid.astype(bool)
+
+    def successors(self, node_id, orientation):
+        """GBZ::successors(node_id, orientation): a list of (id, orientation), or None (src/gbz.rs:327-335)."""
+        return self._one_row(self.edges_csr([node_id], [orientation], False))
+
+    def predecessors(self, node_id, orientation):
+        """GBZ::predecessors(node_id, orientation): a list of (id, orientation), or None (src/gbz.rs:345-353)."""
+        return self._one_row(self.edges_csr([node_id], [orientation], True))
+
     # ---- search -------------------------------------------------------------------------------
     def find(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
@@ -641,6 +710,72 @@ class GBZ(GBWT):
         check(self._L.gbwt_hip_last_tags_ms(self._ws, C.byref(walk), C.byref(plan), C.byref(gather)))
         return walk.value, plan.value, gather.value
 
+    # ---- the graph: segments, links, GFA lines -----------------------------------------------------
+    def has_translation(self):
+        """GBZ::has_translation (src/gbz.rs:362-364)."""
+        return bool(self._stats.has_translation)
+
+    def node_to_segments(self, node_ids):
+        """GBZ::node_to_segment (src/gbz.rs:370-376) for a batch: (segment ids[u64], valid[bool])."""
+        ids = np.ascontiguousarray(node_ids, dtype=np.uint64)
+        out = np.zeros(ids.size, dtype=np.uint64)
+        valid = np.zeros(ids.size, dtype=np.uint8)
+        check(self._L.gbwt_hip_node_segments(self._h, _ptr(ids), ids.size, _ptr(out), _ptr(valid)))
+        return out, valid.astype(bool)
+
+    def node_to_segment(self, node_id):
+        """The id of the segment that holds the node, or None without a translation or without the node."""
+        out, valid = self.node_to_segments([node_id])
+        return int(out[0]) if valid[0] else None
+
+    def segment_iter(self):
+        """GBZ::segment_iter (src/gbz.rs:381-390): the ids of the segments whose first node exists (numpy uint64), or None without a translation."""
+        if not self.has_translation():
+            return None
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_segments(self._h, None, 0, C.byref(total)))
+        out = np.zeros(max(1, total.value), dtype=np.uint64)
+        check(self._L.gbwt_hip_segments(self._h, _ptr(out), out.size, C.byref(total)))
+        return out[: total.value]
+
+    def links_csr(self, segment_ids, orientations, predecessors=False):
+        """GBZ::segment_successors / segment_predecessors (src/gbz.rs:402-440) for a batch of (segment id, orientation): (offsets, links, valid);
+        a link is 2 * segment id + orientation."""
+        return self._rows_csr(self._L.gbwt_hip_links, segment_ids, orientations, predecessors)
+
+    def links_device(self, segment_ids, orientations, predecessors=False):
+        """The same rows left in HBM (an EdgeRows struct; rows_to_host() copies them out)."""
+        return self._rows_device(self._L.gbwt_hip_links_device, segment_ids, orientations, predecessors)
+
+    def segment_successors(self, segment_id, orientation):
+        """A list of (segment id, orientation), or None (GBZ::segment_successors, src/gbz.rs:402-415)."""
+        return self._one_row(self.links_csr([segment_id], [orientation], False))
+
+    def segment_predecessors(self, segment_id, orientation):
+        """A list of (segment id, orientation), or None (GBZ::segment_predecessors, src/gbz.rs:427-440)."""
+        return self._one_row(self.links_csr([segment_id], [orientation], True))
+
+    def graph_lines(self):
+        """The H-line, the S-lines and the L-lines gbunzip writes for this graph (src/bin/gbunzip.rs:193-332), formatted on the device, as bytes."""
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_graph_lines(self._h, self._ws, None, 0, C.byref(total)))
+        buf = np.empty(max(1, total.value), dtype=np.uint8)
+        check(self._L.gbwt_hip_graph_lines(self._h, self._ws, buf.ctypes.data, buf.size, C.byref(total)))
+        return buf[: total.value].tobytes()
+
+    def graph_lines_device(self):
+        """The same text left in HBM: a GraphText struct (d_text; header_bytes, segment_bytes, link_bytes; segments, links = the line counts).
+        Every call formats again; the sizes are kept from the first one."""
+        out = GraphText()
+        check(self._L.gbwt_hip_graph_lines_device(self._h, self._ws, C.byref(out)))
+        return out
+
+    def last_graph_ms(self):
+        """(sizing ms, S-lines ms, L-lines ms) of the last graph lines request (HIP events; sizing is 0 where the kept sizes were used)."""
+        sizes, segments, links = C.c_float(0), C.c_float(0), C.c_float(0)
+        check(self._L.gbwt_hip_last_graph_ms(self._ws, C.byref(sizes), C.byref(segments), C.byref(links)))
+        return sizes.value, segments.value, links.value
+
     # ---- reference positions ---------------------------------------------------------------------
     def reference_sample_names(self, also_generic):
         """GBZ::reference_sample_names (src/gbz.rs:183-196): the names of the GBWT tag `reference_samples` (split at ' ') and, with
@@ -725,5 +860,5 @@ class GBZ(GBWT):
         return out
 
 
-__all__ = ["GBWT", "GBZ", "GbwtHipError", "Components", "Lines", "Paths", "FORWARD", "REVERSE", "PATHS_DEFAULT", "PATHS_PAN_SN", "PATHS_REF_ONLY", "POS_DTYPE", "STATE_DTYPE", "BD_DTYPE", "REFPATH_DTYPE", "REFPOS_DTYPE", "encode_node",
+__all__ = ["GBWT", "GBZ", "GbwtHipError", "Components", "EdgeRows", "GraphText", "Lines", "Paths", "FORWARD", "REVERSE", "PATHS_DEFAULT", "PATHS_PAN_SN", "PATHS_REF_ONLY", "POS_DTYPE", "STATE_DTYPE", "BD_DTYPE", "REFPATH_DTYPE", "REFPOS_DTYPE", "encode_node",
            "decode_node", "flip_node", "encode_path", "device_count", "device_memory", "parse_file", "Pos", "State", "BdState"]

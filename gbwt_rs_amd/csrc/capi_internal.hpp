@@ -1,4 +1,4 @@
-// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, gfa.hip, comm.hip).
+// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, capi_topology.hip, gfa.hip, comm.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -425,6 +425,22 @@ struct gbwt_hip_workspace {
     uint32_t rp_rounds = 0, rp_launches = 0;
     float rp_walk_ms = 0, rp_select_ms = 0, rp_offsets_ms = 0;
     hipEvent_t rev[3] = {nullptr, nullptr, nullptr};
+    // The graph API (topology.hip, capi_topology.hip).  Edge / link rows of the last request: its queries (tp_ids u64, tp_orient u8; tp_seg: the
+    // segment ids of a links request), counts, offsets, edges, the query of every edge (tp_rows, links only), valid bytes and the list of long
+    // rows (tp_big); for links the cuts, the link offsets and the links.  tp_key: the request they answer (the fill call after a size query).
+    gbwt_hip::DeviceBuffer tp_ids, tp_orient, tp_seg, tp_counts, tp_off, tp_edges, tp_rows, tp_valid, tp_big, tp_cut, tp_loff, tp_links;
+    bool tp_cached = false;
+    std::vector<uint8_t> tp_key;
+    int tp_links_request = 0, tp_predecessors = 0;
+    uint64_t tp_n = 0, tp_total = 0;
+    // Graph lines: the items of the S-lines (node or segment ids) and their line offsets, the edge rows of all (node | segment, orientation)
+    // pairs with the query of every edge and the offsets of their L-lines -- kept from the first request (gt_sized), so that a later one only
+    // formats -- and the text.  Events: gt_ev[0] .. [1] sizing, [1] .. [2] S-lines, [2] .. [3] L-lines.
+    gbwt_hip::DeviceBuffer gt_items, gt_soff, gt_edges, gt_rows, gt_loff, gt_text;
+    bool gt_sized = false, gt_text_valid = false, gt_timed = false, gt_translated = false, gt_sized_now = false;   // gt_sized_now: the last request sized
+    uint64_t gt_item_count = 0, gt_edge_count = 0, gt_sbytes = 0, gt_lbytes = 0, gt_links = 0;
+    std::string gt_header;
+    hipEvent_t gt_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     gbwt_hip::HostCopier copier;     // pinned staging of the large device-to-host copies
     uint64_t follow_total = 0, lines_total = 0;
     ~gbwt_hip_workspace() {
@@ -434,6 +450,7 @@ struct gbwt_hip_workspace {
         for (auto &e : sev) if (e) (void)hipEventDestroy(e);
         for (auto &e : tev) if (e) (void)hipEventDestroy(e);
         for (auto &e : rev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : gt_ev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (pinned_words) (void)hipHostFree(pinned_words);
     }

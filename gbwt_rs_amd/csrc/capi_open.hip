@@ -866,10 +866,12 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
                                            &ws->out_valid, &ws->follow_off, &ws->gfa_a, &ws->gfa_b, &ws->gfa_c, &ws->gfa_text, &ws->gfa_text2, &ws->gfa_valid, &ws->gfa_chunk_first,
                                            &ws->gfa_chunks, &ws->gfa_plan, &ws->seq_text, &ws->seq_text2, &ws->seq_offsets, &ws->tag_node, &ws->tag_off, &ws->tag_top, &ws->tag_state,
                                            &ws->tag_sa, &ws->tag_sa2, &ws->tag_out, &ws->tag_out2, &ws->rp_off, &ws->rp_mark, &ws->rp_jump, &ws->rp_rows, &ws->rp_flags,
-                                           &ws->rp_paths, &ws->rp_positions});
+                                           &ws->rp_paths, &ws->rp_positions, &ws->tp_ids, &ws->tp_orient, &ws->tp_seg, &ws->tp_counts, &ws->tp_off, &ws->tp_edges, &ws->tp_rows,
+                                           &ws->tp_valid, &ws->tp_big, &ws->tp_cut, &ws->tp_loff, &ws->tp_links, &ws->gt_items, &ws->gt_soff, &ws->gt_edges, &ws->gt_rows,
+                                           &ws->gt_loff, &ws->gt_text});
         out->rows_bytes = ws->nodes.bytes;
         out->rows_chunks = ws->nodes.chunks.size();
-        out->text_bytes = ws->gfa_text.bytes + ws->gfa_text2.bytes + ws->seq_text.bytes + ws->seq_text2.bytes;
+        out->text_bytes = ws->gfa_text.bytes + ws->gfa_text2.bytes + ws->seq_text.bytes + ws->seq_text2.bytes + ws->gt_text.bytes;
     }
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END

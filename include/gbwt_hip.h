@@ -437,6 +437,56 @@ gbwt_hip_status gbwt_hip_select_paths(const gbwt_hip_index *index, gbwt_hip_work
  * gbwt_hip_select_paths selects, byte for byte. */
 gbwt_hip_status gbwt_hip_write_sequences_contig(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *path, const char *contig, int endmarker);
 
+/* ---- the graph: nodes, edges, segments, links, and the H-/S-/L-lines of a GFA file ----------------------------------------------------
+ * An EDGE or LINK is reported as 2 * id + orientation (support::encode_node, src/support.rs:155-157; orientation 0 = forward), as uint64_t.
+ * Batched requests give a CSR: row k = out[out_offsets[k] .. out_offsets[k + 1]), valid[k] = 1 where the reference returns an iterator
+ * (an empty one included) and 0, with an empty row, where it returns None.  A request is never refused for an id it does not know.
+ * The size query and GBWT_HIP_CAPACITY work as in gbwt_hip_follow: out_offsets[n + 1], valid[n] and *total are always filled; the rows are
+ * copied when out_edges != NULL and capacity >= *total.  The device-resident forms leave the CSR in the workspace, valid until the next
+ * edges / links request on it.
+ *
+ * gbwt_hip_node_ids: GBZ::node_iter (src/gbz.rs:312-317): the ids of the nodes for which GBZ::has_node holds (src/gbz.rs:286-289: the
+ * forward record is non-empty and holds an edge), ascending.  Any handle.  out == NULL is a size query. */
+gbwt_hip_status gbwt_hip_node_ids(const gbwt_hip_index *index, uint64_t *out, uint64_t capacity, uint64_t *total);
+/* GBZ::successors (predecessors == 0, src/gbz.rs:327-335) / GBZ::predecessors (src/gbz.rs:345-353) of node_ids[k] in orientations[k]
+ * (EdgeIter, src/gbz.rs:819-870): the edges of the record of the oriented node -- of the flipped node for predecessors, every edge then
+ * flipped -- in record order, a leading ENDMARKER edge left out.  valid[k] = 0 where !has_node(node_id) -- id 0, below min_node and at or
+ * above alphabet_size / 2 included -- or the record of the oriented node is absent or empty (BWT::record -> None, src/bwt.rs:124-131; the
+ * reverse records of a unidirectional index).  Any handle, whatever its GBWT_HIP_OPEN_* flags, a bare GBWT included. */
+typedef struct { const uint64_t *d_offsets; const uint64_t *d_edges; const uint8_t *d_valid; uint64_t total; uint64_t n; } gbwt_hip_edge_rows;
+gbwt_hip_status gbwt_hip_edges(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *node_ids, const uint8_t *orientations, uint64_t n,
+                               int predecessors, uint64_t *out_offsets, uint64_t *out_edges, uint64_t capacity, uint64_t *total, uint8_t *valid);
+gbwt_hip_status gbwt_hip_edges_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *node_ids, const uint8_t *orientations,
+                                      uint64_t n, int predecessors, gbwt_hip_edge_rows *out);
+/* GBZ::segment_iter (src/gbz.rs:381-390, SegmentIter 919-935): the ids of the segments whose first node exists, ascending.  *total = 0
+ * without a node-to-segment translation (the reference: None).  A GBZ handle; out_ids == NULL is a size query. */
+gbwt_hip_status gbwt_hip_segments(const gbwt_hip_index *index, uint64_t *out_ids, uint64_t capacity, uint64_t *total);
+/* GBZ::node_to_segment (src/gbz.rs:370-376): out_segments[k] = the id of the segment that holds node_ids[k]; valid[k] = 0 without a
+ * translation or without the node. */
+gbwt_hip_status gbwt_hip_node_segments(const gbwt_hip_index *index, const uint64_t *node_ids, uint64_t n, uint64_t *out_segments, uint8_t *valid);
+/* GBZ::segment_successors / segment_predecessors (src/gbz.rs:402-440, LinkIter 988-1005) of segment_ids[k] in orientations[k]: the edges of
+ * the boundary node -- nodes.end - 1 for forward successors and reverse predecessors, nodes.start otherwise -- each node replaced by its
+ * segment (Graph::node_to_segment, src/graph.rs:186-198); the row ends in front of the first listed node without a segment, where
+ * LinkIter::next returns None.  valid[k] = 0 without a translation, for a segment id out of range, and where successors / predecessors of
+ * the boundary node is None.  A GBZ opened with GBWT_HIP_OPEN_GFA (the translation tables in HBM); otherwise GBWT_HIP_BAD_ARGUMENT. */
+gbwt_hip_status gbwt_hip_links(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *segment_ids, const uint8_t *orientations, uint64_t n,
+                               int predecessors, uint64_t *out_offsets, uint64_t *out_links, uint64_t capacity, uint64_t *total, uint8_t *valid);
+gbwt_hip_status gbwt_hip_links_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *segment_ids, const uint8_t *orientations,
+                                      uint64_t n, int predecessors, gbwt_hip_edge_rows *out);
+/* The graph of a GFA file as gbunzip writes it (write_gfa_header, write_segments, write_links, src/bin/gbunzip.rs:193-332), formatted on the
+ * device: d_text = the H-line (header_bytes; with RS:Z: when the GBWT has the tag reference_samples), the S-lines (segment_bytes,
+ * `segments` lines) and the L-lines (link_bytes, `links` lines; the canonical ones: from a forward node to >= its id, from a reverse node
+ * to > its id or to the same id forward), byte for byte; node ids in decimal, or segment names with a translation.  A GBZ opened with
+ * GBWT_HIP_OPEN_GFA; otherwise GBWT_HIP_BAD_ARGUMENT.  The first request of a handle uploads the node labels, as the first request for
+ * bases does.  Sizes and offsets stay in the workspace: a later request formats again without sizing.  The text is valid until the next
+ * graph lines request on the workspace. */
+typedef struct { const char *d_text; uint64_t header_bytes, segment_bytes, link_bytes, segments, links; } gbwt_hip_graph_text;
+gbwt_hip_status gbwt_hip_graph_lines_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, gbwt_hip_graph_text *out);
+/* The same text in host memory; *total = its bytes; out == NULL is a size query; capacity < *total -> GBWT_HIP_CAPACITY. */
+gbwt_hip_status gbwt_hip_graph_lines(const gbwt_hip_index *index, gbwt_hip_workspace *ws, char *out, uint64_t capacity, uint64_t *total);
+/* Device time (HIP events) of the last graph lines request: sizing (0 where the kept sizes were used), S-line fill, L-line fill. */
+gbwt_hip_status gbwt_hip_last_graph_ms(const gbwt_hip_workspace *ws, float *size_ms, float *segments_ms, float *links_ms);
+
 /* ---- reference positions (GBZ handles opened with GBWT_HIP_OPEN_GFA) --------------------------------------------------------------------
  * GBZ::reference_positions (src/gbz.rs:600-657, result type ReferencePath :1255-1266; known answer src/gbz/tests.rs:521-567): for a forward
  * path p (sequence 2 p) with nodes v_0 .. v_{m-1}, off_0 = 0 and off_{k+1} = off_k + sequence_len(node_id(v_k)), the path's length in bases

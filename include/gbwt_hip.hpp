@@ -187,10 +187,51 @@ public:
         return out;
     }
 
+    // GBZ::node_iter (src/gbz.rs:312-317): the ids of the nodes that exist, ascending
+    std::vector<size_t> node_iter() const {
+        uint64_t total = 0;
+        check(gbwt_hip_node_ids(index_.get(), nullptr, 0, &total));
+        std::vector<uint64_t> ids(std::max<uint64_t>(total, 1));
+        check(gbwt_hip_node_ids(index_.get(), ids.data(), ids.size(), &total));
+        return std::vector<size_t>(ids.begin(), ids.begin() + total);
+    }
+    // GBZ::successors / predecessors collected (src/gbz.rs:327-353; EdgeIter 819-870): (node id, orientation) pairs, or nullopt
+    std::optional<std::vector<std::pair<uint64_t, Orientation>>> successors(uint64_t node_id, Orientation orientation) const {
+        return row(gbwt_hip_edges, node_id, orientation, false);
+    }
+    std::optional<std::vector<std::pair<uint64_t, Orientation>>> predecessors(uint64_t node_id, Orientation orientation) const {
+        return row(gbwt_hip_edges, node_id, orientation, true);
+    }
+    // the batched form: rows of 2 * id + orientation (gbwt_hip_edges)
+    struct EdgeRows { std::vector<uint64_t> offsets, edges; std::vector<uint8_t> valid; };
+    EdgeRows edges(const std::vector<uint64_t> &node_ids, const std::vector<uint8_t> &orientations, bool predecessors = false) const {
+        return rows(gbwt_hip_edges, node_ids, orientations, predecessors);
+    }
+
     const gbwt_hip_index *handle() const { return index_.get(); }
     gbwt_hip_workspace *workspace() const { return ws_.get(); }
 
 protected:
+    template <class F>
+    EdgeRows rows(F fn, const std::vector<uint64_t> &ids, const std::vector<uint8_t> &orientations, bool predecessors) const {
+        if (orientations.size() != ids.size()) throw Error(GBWT_HIP_BAD_ARGUMENT, "one orientation per id");
+        EdgeRows out;
+        out.offsets.assign(ids.size() + 1, 0);
+        out.valid.assign(ids.size(), 0);
+        uint64_t total = 0;
+        check(fn(index_.get(), ws_.get(), ids.data(), orientations.data(), ids.size(), predecessors ? 1 : 0, out.offsets.data(), nullptr, 0, &total, out.valid.data()));
+        out.edges.resize(total);
+        if (total) check(fn(index_.get(), ws_.get(), ids.data(), orientations.data(), ids.size(), predecessors ? 1 : 0, out.offsets.data(), out.edges.data(), total, &total, out.valid.data()));
+        return out;
+    }
+    template <class F>
+    std::optional<std::vector<std::pair<uint64_t, Orientation>>> row(F fn, uint64_t id, Orientation orientation, bool predecessors) const {
+        const EdgeRows r = rows(fn, {id}, {static_cast<uint8_t>(orientation == Orientation::Reverse ? 1 : 0)}, predecessors);
+        if (!r.valid[0]) return std::nullopt;
+        std::vector<std::pair<uint64_t, Orientation>> out;
+        for (uint64_t e : r.edges) out.emplace_back(e >> 1, (e & 1) ? Orientation::Reverse : Orientation::Forward);
+        return out;
+    }
     GBWT(const GBWT &other, int) : index_(other.index_), stats_(other.stats_) { make_workspace(); }
     void init() {
         check(gbwt_hip_get_stats(index_.get(), &stats_));
@@ -252,6 +293,48 @@ public:
         if (total) check(gbwt_hip_segment_paths(index_.get(), ws_.get(), &id, 1, offsets, tokens.data(), total, &total));
         std::vector<std::pair<uint64_t, Orientation>> out;
         for (uint64_t t : tokens) out.emplace_back(t >> 1, (t & 1) ? Orientation::Reverse : Orientation::Forward);
+        return out;
+    }
+    // GBZ::has_translation (src/gbz.rs:362-364)
+    bool has_translation() const { return stats().has_translation != 0; }
+    // GBZ::node_to_segment (src/gbz.rs:370-376): the id of the segment that holds the node, or nullopt
+    std::optional<uint64_t> node_to_segment(uint64_t node_id) const {
+        uint64_t segment = 0;
+        uint8_t valid = 0;
+        check(gbwt_hip_node_segments(index_.get(), &node_id, 1, &segment, &valid));
+        return valid ? std::optional<uint64_t>(segment) : std::nullopt;
+    }
+    // GBZ::segment_iter (src/gbz.rs:381-390): the ids of the segments whose first node exists, or nullopt without a translation
+    std::optional<std::vector<size_t>> segment_iter() const {
+        if (!has_translation()) return std::nullopt;
+        uint64_t total = 0;
+        check(gbwt_hip_segments(index_.get(), nullptr, 0, &total));
+        std::vector<uint64_t> ids(std::max<uint64_t>(total, 1));
+        check(gbwt_hip_segments(index_.get(), ids.data(), ids.size(), &total));
+        return std::vector<size_t>(ids.begin(), ids.begin() + total);
+    }
+    // GBZ::segment_successors / segment_predecessors collected (src/gbz.rs:402-440; LinkIter 988-1005): (segment id, orientation) pairs
+    std::optional<std::vector<std::pair<uint64_t, Orientation>>> segment_successors(uint64_t segment_id, Orientation orientation) const {
+        return row(gbwt_hip_links, segment_id, orientation, false);
+    }
+    std::optional<std::vector<std::pair<uint64_t, Orientation>>> segment_predecessors(uint64_t segment_id, Orientation orientation) const {
+        return row(gbwt_hip_links, segment_id, orientation, true);
+    }
+    EdgeRows links(const std::vector<uint64_t> &segment_ids, const std::vector<uint8_t> &orientations, bool predecessors = false) const {
+        return rows(gbwt_hip_links, segment_ids, orientations, predecessors);
+    }
+    // the H-, S- and L-lines gbunzip writes (src/bin/gbunzip.rs:193-332), formatted on the device
+    std::string graph_lines() const {
+        uint64_t total = 0;
+        check(gbwt_hip_graph_lines(index_.get(), ws_.get(), nullptr, 0, &total));
+        std::string text(total, '\0');
+        if (total) check(gbwt_hip_graph_lines(index_.get(), ws_.get(), text.data(), total, &total));
+        return text;
+    }
+    // the same text left in HBM (gbwt_hip_graph_lines_device) and the device times of the last request
+    gbwt_hip_graph_text graph_lines_device() const {
+        gbwt_hip_graph_text out{};
+        check(gbwt_hip_graph_lines_device(index_.get(), ws_.get(), &out));
         return out;
     }
     // GBZ::search_state, src/gbz.rs:508-510
