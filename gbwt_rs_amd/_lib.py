@@ -96,6 +96,16 @@ class ReferencePosition(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("pos", Pos)]
 
 
+class Located(C.Structure):
+    _fields_ = [("d_offsets", C.c_void_p), ("d_ids", C.c_void_p), ("d_valid", C.c_void_p), ("total", C.c_uint64), ("n", C.c_uint64)]
+
+
+class LocateInfo(C.Structure):
+    _fields_ = [("built", C.c_uint32), ("interval", C.c_uint32), ("sampled_records", C.c_uint64), ("table_positions", C.c_uint64),
+                ("end_entries", C.c_uint64), ("device_bytes", C.c_uint64), ("build_ms", C.c_double), ("build_launches", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -170,6 +180,13 @@ SIGNATURES = {
     "gbwt_hip_reference_positions": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_last_positions_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gbwt_hip_last_positions_rounds": (_int, [_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "gbwt_hip_locate": (_int, [_p, _p, _p, _u64, _int, _p, _p, _u64, C.POINTER(_u64), _p]),
+    "gbwt_hip_locate_device": (_int, [_p, _p, _p, _u64, _int, C.POINTER(Located)]),
+    "gbwt_hip_locate_states_device": (_int, [_p, _p, _p, _p, _u64, _int, C.POINTER(Located)]),
+    "gbwt_hip_locate_positions": (_int, [_p, _p, _p, _u64, _p, _p]),
+    "gbwt_hip_last_locate_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gbwt_hip_locate_count_steps": (_int, [_p, _p, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gbwt_hip_locate_index_info": (_int, [_p, C.POINTER(LocateInfo)]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_copy_path": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64)]),

@@ -19,6 +19,8 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBWT.node_iter / successors / predecessors        GBZ::node_iter, successors, predecessors   src/gbz.rs:312-353 (EdgeIter 819-892)
   GBZ.node_to_segment / segment_iter / segment_successors / segment_predecessors   src/gbz.rs:370-440 (SegmentIter, LinkIter 896-1016)
   GBZ.graph_lines()                gbunzip's H-, S- and L-lines   src/bin/gbunzip.rs:193-332
+  GBWT.locate / locate_csr / locate_positions      the C++ GBWT's locate(SearchState) / locate(node, i): the sequences behind a search state
+                                   (the reference has no counterpart: "Locate queries" is the open box of its README's scope list)
 
 Every call goes through the C ABI of libgbwt_hip.so (hand-written HIP); "not found" is reported as
 None / a False entry of the validity mask, never as an exception.
@@ -29,7 +31,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BdState, Components, EdgeRows, GbwtHipError, GraphText, Lines, Memory, OpenTimes, Paths, Pos, State, Stats, check
+from ._lib import BdState, Components, EdgeRows, GbwtHipError, GraphText, Lines, Located, LocateInfo, Memory, OpenTimes, Paths, Pos, State, Stats, check
 
 FORWARD, REVERSE = 0, 1  # support::Orientation, src/support.rs:30-47
 PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY = 0, 1, 2  # gbunzip's PathMode, src/bin/gbunzip.rs:63-76
@@ -508,6 +510,111 @@ class GBWT:
         out, valid = self._results(q.shape[0], BD_DTYPE, out)
         check(self._L.gbwt_hip_bd_search(self._h, self._ws, _ptr(q), q.shape[0], q.shape[1], first, _ptr(out), _ptr(valid)))
         return out, valid.astype(bool)
+
+
+    # ---- locate: the sequences behind a search state (any handle) -----------------------------------
+    @staticmethod
+    def _structured(values, dtype, what):
+        """A one-dimensional contiguous array of `dtype` (STATE_DTYPE / POS_DTYPE) from such an array, an (n, fields) unsigned integer matrix
+        or a list of tuples."""
+        if isinstance(values, np.ndarray) and values.dtype == dtype:
+            a = values
+        else:
+            try:
+                raw = np.asarray(values)
+            except Exception as e:  # noqa: BLE001
+                raise TypeError(f"{what} must be an array of {dtype} or an (n, {len(dtype.names)}) integer matrix") from e
+            if raw.dtype.names is not None:
+                raise TypeError(f"{what} have dtype {raw.dtype}, expected {dtype}")
+            if raw.size == 0:
+                raw = np.zeros((0, len(dtype.names)), dtype=np.uint64)
+            if raw.dtype.kind not in "ui":
+                raise TypeError(f"{what} must hold integers, not {raw.dtype}")
+            if raw.ndim != 2 or raw.shape[1] != len(dtype.names):
+                raise ValueError(f"{what} must have shape (n, {len(dtype.names)}), not {raw.shape}")
+            if raw.dtype.kind == "i" and raw.size and raw.min() < 0:
+                raise ValueError(f"{what} must not be negative")
+            a = np.ascontiguousarray(raw, dtype=np.uint64).view(dtype).reshape(-1)
+        if a.ndim != 1:
+            raise ValueError(f"{what} must be one-dimensional, not of shape {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def locate_csr(self, states, unique=False):
+        """The sequences behind a batch of search states (node, start, end): (offsets[u64, n + 1], ids[u64], valid[bool]).  Row k holds the
+        id of the sequence that owns offset start, start + 1, ... of the node's record in that order (unique=False), or the same ids ascending
+        without duplicates (unique=True, the C++ GBWT's locate(SearchState)).  valid[k] is False, with an empty row, where the node has no
+        record, start >= end or end exceeds the record's length.  The first call on a handle builds its locate index."""
+        st = self._structured(states, STATE_DTYPE, "states")
+        offsets = np.zeros(st.size + 1, dtype=np.uint64)
+        valid = np.zeros(st.size, dtype=np.uint8)
+        total = C.c_uint64(0)
+        check(self._L.gbwt_hip_locate(self._h, self._ws, _ptr(st), st.size, int(bool(unique)), _ptr(offsets), None, 0, C.byref(total), _ptr(valid)))
+        ids = np.zeros(max(1, total.value), dtype=np.uint64)
+        check(self._L.gbwt_hip_locate(self._h, self._ws, _ptr(st), st.size, int(bool(unique)), _ptr(offsets), _ptr(ids), ids.size, C.byref(total), _ptr(valid)))
+        return offsets, ids[: total.value], valid.astype(bool)
+
+    def locate(self, state, unique=True):
+        """The sequence ids of one state (node, start, end) as a numpy uint64 array, or None for a state that is no range of a record."""
+        state = tuple(int(x) for x in state)
+        if len(state) != 3:
+            raise ValueError("a state is (node, start, end)")
+        offsets, ids, valid = self.locate_csr(np.array([state], dtype=STATE_DTYPE), unique)
+        return ids.copy() if valid[0] else None
+
+    def locate_device(self, states, unique=False):
+        """The rows of locate_csr left in HBM: a _lib.Located struct (d_offsets u64[n + 1], d_ids u64[total], d_valid u8[n]), valid until the next
+        locate request on this workspace; edges / links requests leave it alone.  located_to_host() copies it out."""
+        st = self._structured(states, STATE_DTYPE, "states")
+        out = Located()
+        check(self._L.gbwt_hip_locate_device(self._h, self._ws, _ptr(st), st.size, int(bool(unique)), C.byref(out)))
+        return out
+
+    def locate_states_device(self, states_struct, unique=False):
+        """locate_device for states that are in HBM already: the _lib.States of search_device() (failed searches, d_valid == 0, are invalid
+        rows).  Search -> locate never leaves the device."""
+        if not isinstance(states_struct, _lib.States):
+            raise TypeError("locate_states_device takes the _lib.States struct of search_device()")
+        out = Located()
+        check(self._L.gbwt_hip_locate_states_device(self._h, self._ws, states_struct.d_states, states_struct.d_valid, states_struct.n, int(bool(unique)), C.byref(out)))
+        return out
+
+    def located_to_host(self, rows):
+        """(offsets, ids, valid) of a locate_device() / locate_states_device() result (through torch views of the workspace's memory)."""
+        import torch
+        from . import dist as D
+        device = torch.device("cuda", self._device)
+        offsets = D.device_view(rows.d_offsets, (rows.n + 1) * 8, torch.uint8, device).cpu().numpy().view(np.uint64)
+        ids = D.device_view(rows.d_ids, rows.total * 8, torch.uint8, device).cpu().numpy().view(np.uint64) if rows.total else np.zeros(0, np.uint64)
+        valid = D.device_view(rows.d_valid, rows.n, torch.uint8, device).cpu().numpy() if rows.n else np.zeros(0, np.uint8)
+        return offsets.copy(), ids.copy(), valid.astype(bool)
+
+    def locate_positions(self, positions):
+        """The C++ GBWT's locate(node, i) for a batch of positions (node, offset): (ids[u64], valid[bool]); valid[k] is False, with id 0, where
+        the node has no record (the endmarker included) or the offset is past the record."""
+        pos = self._structured(positions, POS_DTYPE, "positions")
+        ids = np.zeros(pos.size, dtype=np.uint64)
+        valid = np.zeros(pos.size, dtype=np.uint8)
+        check(self._L.gbwt_hip_locate_positions(self._h, self._ws, _ptr(pos), pos.size, _ptr(ids), _ptr(valid)))
+        return ids, valid.astype(bool)
+
+    def last_locate_ms(self):
+        """(walk_ms, sort_ms) of the last locate request for states on this workspace (HIP events); sort_ms is 0 unless it was unique."""
+        walk, sort = C.c_float(0), C.c_float(0)
+        check(self._L.gbwt_hip_last_locate_ms(self._ws, C.byref(walk), C.byref(sort)))
+        return walk.value, sort.value
+
+    def locate_count_steps(self, states):
+        """(LF steps, located positions) of the plain rows of `states`: the locate kernel launched once more with a counter (a measurement)."""
+        st = self._structured(states, STATE_DTYPE, "states")
+        steps, positions = C.c_uint64(0), C.c_uint64(0)
+        check(self._L.gbwt_hip_locate_count_steps(self._h, self._ws, _ptr(st), st.size, C.byref(steps), C.byref(positions)))
+        return steps.value, positions.value
+
+    def locate_index_info(self):
+        """The locate index of the handle (gbwt_hip_locate_index_info) as a dict; all zeros before the first locate call."""
+        info = LocateInfo()
+        check(self._L.gbwt_hip_locate_index_info(self._h, C.byref(info)))
+        return {name: getattr(info, name) for name, _ in LocateInfo._fields_ if name != "reserved"}
 
 
 class GBZ(GBWT):

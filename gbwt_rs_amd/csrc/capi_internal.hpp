@@ -240,6 +240,7 @@ struct OpenKnobs {
     bool walk_tables = true, deep_tables = true, compact_tables = true;   // GBWT_HIP_WALK_TABLES / _DEEP_TABLES / _COMPACT_TABLES (0 switches off)
     std::optional<uint64_t> table_bytes;               // GBWT_HIP_TABLE_BYTES (unset: by the device's memory)
     bool line_cache = true;                            // GBWT_HIP_LINE_CACHE (0: requests size their lines themselves)
+    uint32_t locate_interval = 64;                     // GBWT_HIP_LOCATE_INTERVAL: expected records between two sampled ones of the locate index (1: every record, 0: none)
     bool trace = false;                                // GBWT_HIP_TRACE_OPEN set (any value): phase timings on stderr
     static OpenKnobs from_env() {
         OpenKnobs k;
@@ -259,6 +260,7 @@ struct OpenKnobs {
         k.walk_tables = on("GBWT_HIP_WALK_TABLES"); k.deep_tables = on("GBWT_HIP_DEEP_TABLES"); k.compact_tables = on("GBWT_HIP_COMPACT_TABLES");
         if (const char *v = std::getenv("GBWT_HIP_TABLE_BYTES")) k.table_bytes = std::strtoull(v, nullptr, 10);
         k.line_cache = on("GBWT_HIP_LINE_CACHE");
+        if (const char *v = std::getenv("GBWT_HIP_LOCATE_INTERVAL")) k.locate_interval = static_cast<uint32_t>(std::min<long>(1l << 30, std::max<long>(0, std::atol(v))));
         k.trace = std::getenv("GBWT_HIP_TRACE_OPEN") != nullptr;
         return k;
     }
@@ -283,6 +285,7 @@ struct ExtractKnobs {
     bool wide_addresses = false;                              // GBWT_HIP_WIDE_ADDRESSES set (any value)
     uint32_t debug = 0;                                       // GBWT_HIP_DEBUG_DRY_ROWS (measurement switches, WalkArgs::debug)
     unsigned copy_threads = 8;                                // GBWT_HIP_COPY_THREADS
+    uint64_t locate_sort_piece = 0x7FFFFFFFull;               // GBWT_HIP_LOCATE_SORT_PIECE: items of one radix sort of a unique locate request (hipcub counts in int; tests lower it)
     static ExtractKnobs from_env() {
         ExtractKnobs k;
         const auto num = [](const char *name, int unset) { const char *v = std::getenv(name); return v ? std::atoi(v) : unset; };
@@ -301,6 +304,7 @@ struct ExtractKnobs {
         k.wide_addresses = std::getenv("GBWT_HIP_WIDE_ADDRESSES") != nullptr;
         k.debug = static_cast<uint32_t>(num("GBWT_HIP_DEBUG_DRY_ROWS", 0));
         k.copy_threads = static_cast<unsigned>(std::min(64, std::max(1, num("GBWT_HIP_COPY_THREADS", 8))));
+        k.locate_sort_piece = static_cast<uint64_t>(std::max(1, num("GBWT_HIP_LOCATE_SORT_PIECE", 0x7FFFFFFF)));
         return k;
     }
 };
@@ -353,6 +357,15 @@ struct gbwt_hip_index {
     mutable uint64_t comp_count = 0, comp_node_count = 0;
     mutable std::vector<uint32_t> host_path_component;
     mutable gbwt_hip_components_times comp_times{};
+    // THE LOCATE INDEX IN HBM (locate.hip, capi_locate.hip: ensure_locate), made by the first locate call, never by an open: the table base of
+    // every record (u64, LOCATE_NONE where the record is not sampled), the sequence id of every position of a sampled record (u32) and the
+    // sorted end entries of the sequences.  Once per handle whichever thread and workspace asks first; a build that fails keeps nothing.
+    mutable gbwt_hip::LazyBuild locate_built;
+    mutable gbwt_hip::DeviceBuffer loc_base, loc_table, loc_end_keys, loc_end_ids;
+    mutable gbwt_hip::LocateIndex loc{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    mutable uint64_t loc_sampled_records = 0;
+    mutable float loc_build_ms = 0;
+    mutable uint32_t loc_build_launches = 0;
     gbwt_hip::DeviceIndex dev{};
     // The full-width two-step blocks (cblocks, as large as gblocks: 1.7 GB on the headline index) are only read by the loops for records
     // whose counts do not fit the packed half-blocks, by the pool-output kernel and by the serial walks at open: built at open when one of
@@ -441,6 +454,18 @@ struct gbwt_hip_workspace {
     uint64_t gt_item_count = 0, gt_edge_count = 0, gt_sbytes = 0, gt_lbytes = 0, gt_links = 0;
     std::string gt_header;
     hipEvent_t gt_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // Locate (locate.hip, capi_locate.hip).  The rows of the last request -- lo_off / lo_ids / lo_valid, for a unique request lo_uoff and the
+    // compacted ids -- live in buffers of their own: an edges / links request leaves them alone.  lo_states: the states of a request given on the
+    // host; lo_counts, lo_keys, lo_sorted, lo_flag, lo_rank, lo_temp: scratch; lo_words: the flag word, a scan carry and the step counter;
+    // lo_pos / lo_pos_ids / lo_pos_valid: a positions request.  lo_key: the request the rows answer (the fill call after a size query).
+    // Events: lev[0] .. lev[1] the locate kernel, lev[1] .. lev[2] sort and compaction of a unique request.
+    gbwt_hip::DeviceBuffer lo_states, lo_counts, lo_off, lo_ids, lo_valid, lo_keys, lo_sorted, lo_flag, lo_rank, lo_uoff, lo_temp, lo_words, lo_pos, lo_pos_ids, lo_pos_valid;
+    bool lo_cached = false, lo_timed = false, lo_compacted = false;   // lo_compacted: lo_uoff holds the offsets of the rows (a unique request with ids)
+    std::vector<uint8_t> lo_key;
+    int lo_unique = 0;
+    uint64_t lo_n = 0, lo_total = 0, lo_steps = 0;
+    float lo_walk_ms = 0, lo_sort_ms = 0;
+    hipEvent_t lev[3] = {nullptr, nullptr, nullptr};
     gbwt_hip::HostCopier copier;     // pinned staging of the large device-to-host copies
     uint64_t follow_total = 0, lines_total = 0;
     ~gbwt_hip_workspace() {
@@ -450,6 +475,7 @@ struct gbwt_hip_workspace {
         for (auto &e : sev) if (e) (void)hipEventDestroy(e);
         for (auto &e : tev) if (e) (void)hipEventDestroy(e);
         for (auto &e : rev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : lev) if (e) (void)hipEventDestroy(e);
         for (auto &e : gt_ev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (pinned_words) (void)hipHostFree(pinned_words);

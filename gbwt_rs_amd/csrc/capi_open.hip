@@ -855,6 +855,8 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
     if (ix.labels_built.made()) out->index_device_bytes += ix.label_bytes.bytes + ix.label_off.bytes;
     // (the weakly connected components: by the first call for them)
     if (ix.components_built.made()) out->index_device_bytes += ix.comp_of.bytes + ix.comp_offsets.bytes + ix.comp_nodes.bytes + ix.comp_paths.bytes;
+    // (the locate index: by the first locate call)
+    if (ix.locate_built.made()) out->index_device_bytes += ix.loc_base.bytes + ix.loc_table.bytes + ix.loc_end_keys.bytes + ix.loc_end_ids.bytes;
     const HostIndex &h = ix.host;
     out->index_host_bytes = (h.records_made() ? h.data.size() + h.starts.size() * sizeof(uint64_t) : 0) + h.da_samples.size() * sizeof(uint64_t) + h.path_names.size() * sizeof(PathName) +
                             h.sample_names.bytes.size() + h.contig_names.bytes.size() + h.sequences_labels.bytes.size() + h.sequences_labels.offsets.size() * sizeof(uint64_t) +
@@ -868,7 +870,8 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
                                            &ws->tag_sa, &ws->tag_sa2, &ws->tag_out, &ws->tag_out2, &ws->rp_off, &ws->rp_mark, &ws->rp_jump, &ws->rp_rows, &ws->rp_flags,
                                            &ws->rp_paths, &ws->rp_positions, &ws->tp_ids, &ws->tp_orient, &ws->tp_seg, &ws->tp_counts, &ws->tp_off, &ws->tp_edges, &ws->tp_rows,
                                            &ws->tp_valid, &ws->tp_big, &ws->tp_cut, &ws->tp_loff, &ws->tp_links, &ws->gt_items, &ws->gt_soff, &ws->gt_edges, &ws->gt_rows,
-                                           &ws->gt_loff, &ws->gt_text});
+                                           &ws->gt_loff, &ws->gt_text, &ws->lo_states, &ws->lo_counts, &ws->lo_off, &ws->lo_ids, &ws->lo_valid, &ws->lo_keys, &ws->lo_sorted, &ws->lo_flag,
+                                           &ws->lo_rank, &ws->lo_uoff, &ws->lo_temp, &ws->lo_words, &ws->lo_pos, &ws->lo_pos_ids, &ws->lo_pos_valid});
         out->rows_bytes = ws->nodes.bytes;
         out->rows_chunks = ws->nodes.chunks.size();
         out->text_bytes = ws->gfa_text.bytes + ws->gfa_text2.bytes + ws->seq_text.bytes + ws->seq_text2.bytes + ws->gt_text.bytes;

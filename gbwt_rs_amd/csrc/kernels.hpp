@@ -224,4 +224,47 @@ void launch_path_components(const DeviceIndex &ix, const ComponentGeometry &g, c
 size_t scan_temp_bytes(uint64_t n);
 void launch_scan(const uint64_t *d_lengths, uint64_t *d_offsets, uint64_t n, void *d_temp, size_t temp_bytes, hipStream_t s);
 
+// ---- locate (locate.hip) ------------------------------------------------------------------------
+// The locate index of a handle as the kernels see it.  rec_base[r] = slot of offset 0 of record r in `table` when r is SAMPLED, LOCATE_NONE
+// otherwise; table[rec_base[r] + i] = the id of the sequence whose visit BWT position (r, i) is.  ends: for the last position of every
+// non-empty sequence the key (record << 32) | offset, ascending, with the sequence id next to it.
+constexpr uint64_t LOCATE_NONE = ~uint64_t(0);
+constexpr uint32_t LOCATE_EMPTY = 0xFFFFFFFFu;        // a table slot nobody has written (sequence ids are below it)
+constexpr uint32_t LOCATE_FLAG_WIDE = 1u, LOCATE_FLAG_WALK = 2u, LOCATE_FLAG_TWICE = 4u, LOCATE_FLAG_LOST = 8u;   // bits of the flag word
+struct LocateIndex {
+    uint64_t *rec_base;        // [n_records + 1]
+    uint32_t *table;           // [table_positions]
+    uint64_t *end_keys;        // [end_entries] (the build sorts n_sequences entries; the unused ones, all ones, come last)
+    uint32_t *end_ids;
+    uint64_t table_positions, end_entries;
+};
+// threshold of the sampling rule for GBWT_HIP_LOCATE_INTERVAL (a record r != 0 is sampled when its hashed index is below it; 2^32: every one)
+uint64_t locate_threshold(uint32_t interval);
+// d_lens[r] = Record::len of a sampled record r, 0 of any other; flags |= LOCATE_FLAG_WIDE when any record's length does not fit 32 bits
+void launch_locate_lengths(const DeviceIndex &ix, uint64_t threshold, uint64_t *d_lens, uint32_t *d_flags, hipStream_t s);
+// after the scan of d_lens into d_base: LOCATE_NONE for the records that are not sampled; *d_sampled += the sampled records that hold positions
+void launch_locate_bases(const uint64_t *d_lens, uint64_t *d_base, uint64_t n_records, uint64_t *d_sampled, hipStream_t s);
+// The build walk: one lane per sample segment of every sequence (d_seg_first[id] = lanes in front of sequence id, [n_sequences + 1];
+// segmented = 0: one lane per sequence).  table slots are LOCATE_EMPTY, end keys all ones before.  d_counts: [0] = slots written,
+// [1] = end entries written.  flags: LOCATE_FLAG_WALK (a lane lost its way), LOCATE_FLAG_TWICE (a slot written twice).
+void launch_locate_build(const DeviceIndex &ix, const LocateIndex &L, const uint64_t *d_seg_first, uint64_t walkers, bool segmented, uint64_t step_limit, uint64_t *d_counts,
+                         uint32_t *d_flags, bool fast, hipStream_t s);
+size_t locate_sort_temp_bytes(uint64_t n);
+void launch_locate_sort_ends(const uint64_t *d_keys_in, uint64_t *d_keys_out, const uint32_t *d_ids_in, uint32_t *d_ids_out, uint64_t n, void *d_temp, size_t temp_bytes, hipStream_t s);
+// valid[k] / counts[k] = end - start of state k where it is a range of a record (include/gbwt_hip.h), 0 otherwise; d_given (may be null): states
+// with d_given[k] == 0 are invalid as they are
+void launch_locate_valid(const DeviceIndex &ix, const gbwt_hip_state *d_states, const uint8_t *d_given, uint64_t n, uint64_t *d_counts, uint8_t *d_valid, hipStream_t s);
+// item t < total = offset start + (t - offsets[row]) of the state of its row: d_out[t] = the sequence id, | row << 32 with keyed != 0.
+// d_steps (may be null): the LF steps taken are added to it (a measurement launch).  flags: LOCATE_FLAG_LOST (no table entry and no end entry)
+void launch_locate(const DeviceIndex &ix, const LocateIndex &L, const gbwt_hip_state *d_states, const uint64_t *d_offsets, uint64_t n, uint64_t total, bool keyed,
+                   uint64_t step_limit, uint64_t *d_out, uint64_t *d_steps, uint32_t *d_flags, bool fast, hipStream_t s);
+void launch_locate_positions(const DeviceIndex &ix, const LocateIndex &L, const gbwt_hip_pos *d_pos, uint64_t n, uint64_t step_limit, uint64_t *d_ids, uint8_t *d_valid,
+                             uint32_t *d_flags, bool fast, hipStream_t s);
+// unique rows: sort of the keys (row << 32) | id over `bits` bits, a flag at the first of every run, and -- behind the scan of the flags into
+// d_rank[total + 1] -- the compacted ids and offsets
+void launch_locate_sort_keys(const uint64_t *d_in, uint64_t *d_out, uint64_t n, int bits, void *d_temp, size_t temp_bytes, hipStream_t s);
+void launch_locate_run_flags(const uint64_t *d_sorted, uint64_t total, uint64_t *d_flag, hipStream_t s);
+void launch_locate_compact(const uint64_t *d_sorted, const uint64_t *d_rank, uint64_t total, const uint64_t *d_offsets, uint64_t n, uint64_t *d_ids, uint64_t *d_new_offsets,
+                           hipStream_t s);
+
 }  // namespace gbwt_hip

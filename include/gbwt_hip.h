@@ -532,6 +532,61 @@ gbwt_hip_status gbwt_hip_last_positions_ms(const gbwt_hip_workspace *ws, float *
 /* Of the same request: the pointer-doubling rounds that marked something, and the kernels and scans it launched behind its extraction. */
 gbwt_hip_status gbwt_hip_last_positions_rounds(const gbwt_hip_workspace *ws, uint32_t *rounds, uint32_t *launches);
 
+/* ---- locate: the sequences behind a search state (any handle) ---------------------------------------------------------------------------
+ * The C++ GBWT's locate(node, i) and locate(SearchState).  The reference has no counterpart: its README leaves "Locate queries" open and it
+ * passes the document array samples through uninterpreted (src/gbwt.rs:416), so the contract is stated here.  A SEQUENCE ID is a GBWT
+ * sequence id (2 * path + orientation in a bidirectional index).  Every BWT position (node, offset), offset < the length of the node's
+ * record, is the visit of exactly one sequence: GBWT::start(id) followed by GBWT::forward meets every position once.
+ *
+ * gbwt_hip_locate_positions: ids[k] = the id of the sequence whose visit positions[k] is.  valid[k] = 0 and ids[k] = 0 where the node has no
+ * record (node <= alphabet_offset -- the endmarker, node 0, included --, node >= alphabet_size, a node without a record) or the offset is
+ * >= the record's length.
+ * gbwt_hip_locate: for states[k] = (node, start, end), end exclusive, a CSR like the edge rows: row k = ids[offsets[k] .. offsets[k + 1]).
+ *   unique == 0: end - start ids, the owner of offset start, start + 1, ... in that order; a sequence that visits the node several times
+ *                appears several times.
+ *   unique == 1: the same ids ascending, duplicates removed (what the C++ GBWT returns for locate(SearchState)).
+ *   valid[k] = 0, with an empty row, where the node has no record, start >= end, or end exceeds the record's length; such a state never fails
+ *   the batch.  unique other than 0 / 1 is GBWT_HIP_BAD_ARGUMENT.
+ * The size query and GBWT_HIP_CAPACITY work as in gbwt_hip_edges: offsets[n + 1], valid[n] and *total are always filled; the ids are copied
+ * when ids != NULL and capacity >= *total; the fill call that repeats the request of a size query does not compute again.
+ *
+ * The first locate call on a handle builds its LOCATE INDEX in HBM, from whichever workspace asks (once; other threads wait for it; it lives
+ * as long as the handle and is counted in index_device_bytes): the sequence id of every position of the SAMPLED records -- a record is
+ * sampled when a hash of its index falls below a threshold; GBWT_HIP_LOCATE_INTERVAL, read at open, is the expected number of records
+ * between two sampled ones: default 64, 1 = every record, 0 = none -- and the last position of every sequence.  A query steps with LF from
+ * its position until it stands on a sampled record or its sequence ends.  Limits, checked at the build: the sequences and every record's
+ * length fit 32 bits (more than 2^31 - 1 sequences, or a record of 2^32 - 1 positions or more: GBWT_HIP_UNSUPPORTED).  A walk of the build
+ * that does not fill every slot of the table exactly once is GBWT_HIP_INVALID_DATA, and nothing is kept.  A unique request is sorted in
+ * pieces of at most 2^31 - 1 ids cut at row boundaries; a single row longer than that is GBWT_HIP_UNSUPPORTED.  A request waits for the
+ * host once, for its total (a unique one a second time, for the total after the duplicates are gone). */
+typedef struct { const uint64_t *d_offsets; const uint64_t *d_ids; const uint8_t *d_valid; uint64_t total; uint64_t n; } gbwt_hip_located;
+gbwt_hip_status gbwt_hip_locate(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const gbwt_hip_state *states, uint64_t n, int unique, uint64_t *offsets,
+                                uint64_t *ids, uint64_t capacity, uint64_t *total, uint8_t *valid);
+/* The same rows left in HBM: d_offsets u64[n + 1], d_ids u64[total], d_valid u8[n], in buffers of the workspace that only locate requests
+ * write: valid until the next locate request on it, untouched by edges / links requests. */
+gbwt_hip_status gbwt_hip_locate_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const gbwt_hip_state *states, uint64_t n, int unique, gbwt_hip_located *out);
+/* ... for states that are in HBM already -- the d_states of a gbwt_hip_search_device result: search -> locate without leaving the device.
+ * d_valid (may be NULL): states with d_valid[k] == 0, the failed searches, are invalid as they are. */
+gbwt_hip_status gbwt_hip_locate_states_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const gbwt_hip_state *d_states, const uint8_t *d_valid, uint64_t n,
+                                              int unique, gbwt_hip_located *out);
+gbwt_hip_status gbwt_hip_locate_positions(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const gbwt_hip_pos *positions, uint64_t n, uint64_t *ids, uint8_t *valid);
+/* Device time (HIP events) of the last locate request for states on `ws`: the locate kernel; sort, flags, scan and compaction of a unique
+ * request (0 otherwise). */
+gbwt_hip_status gbwt_hip_last_locate_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *sort_ms);
+/* The LF steps the lanes of a states request take: the same kernel launched once more with a counter, outside any timing.  *steps / *positions
+ * = steps per located position. */
+gbwt_hip_status gbwt_hip_locate_count_steps(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const gbwt_hip_state *states, uint64_t n, uint64_t *steps,
+                                            uint64_t *positions);
+/* The locate index of a handle; all zeros before the first locate call has built it.  interval = GBWT_HIP_LOCATE_INTERVAL as read at open;
+ * device_bytes = what the index adds to index_device_bytes; build_launches = kernels, scans and sorts of the build. */
+typedef struct {
+    uint32_t built, interval;
+    uint64_t sampled_records, table_positions, end_entries, device_bytes;
+    double build_ms;
+    uint32_t build_launches, reserved;
+} gbwt_hip_locate_info;
+gbwt_hip_status gbwt_hip_locate_index_info(const gbwt_hip_index *index, gbwt_hip_locate_info *out);
+
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex
  * (src/bin/gbunzip.rs:27, 421-434).  Sharded over GPUs -- one process per GPU, the index replicated, path p on rank p mod world

@@ -208,6 +208,40 @@ public:
         return rows(gbwt_hip_edges, node_ids, orientations, predecessors);
     }
 
+    // ---- locate: the sequences behind a search state (the C++ GBWT's locate; the reference has no counterpart, include/gbwt_hip.h)
+    // the batched form: row k = the ids of the sequences that own offsets start .. end - 1 of states[k] in that order, or (unique) the same
+    // ids ascending without duplicates; valid[k] = 0, with an empty row, for a state that is no range of a record (gbwt_hip_locate)
+    struct LocatedRows { std::vector<uint64_t> offsets, ids; std::vector<uint8_t> valid; };
+    LocatedRows locate(const std::vector<SearchState> &states, bool unique = false) const {
+        LocatedRows out;
+        out.offsets.assign(states.size() + 1, 0);
+        out.valid.assign(states.size(), 0);
+        uint64_t total = 0;
+        check(gbwt_hip_locate(index_.get(), ws_.get(), states.data(), states.size(), unique ? 1 : 0, out.offsets.data(), nullptr, 0, &total, out.valid.data()));
+        out.ids.resize(total);
+        if (total) check(gbwt_hip_locate(index_.get(), ws_.get(), states.data(), states.size(), unique ? 1 : 0, out.offsets.data(), out.ids.data(), total, &total, out.valid.data()));
+        return out;
+    }
+    // locate(SearchState): the distinct sequence ids, ascending, or nullopt
+    std::optional<std::vector<uint64_t>> locate(const SearchState &state, bool unique = true) const {
+        LocatedRows r = locate(std::vector<SearchState>{state}, unique);
+        if (!r.valid[0]) return std::nullopt;
+        return std::move(r.ids);
+    }
+    // locate(node, i): the sequence whose visit the position is, or nullopt
+    std::vector<std::optional<uint64_t>> locate(const std::vector<Pos> &positions) const {
+        std::vector<uint64_t> ids(positions.size());
+        std::vector<uint8_t> valid(positions.size());
+        check(gbwt_hip_locate_positions(index_.get(), ws_.get(), positions.data(), positions.size(), ids.data(), valid.data()));
+        return options(ids, valid);
+    }
+    std::optional<uint64_t> locate(const Pos &position) const { return locate(std::vector<Pos>{position})[0]; }
+    gbwt_hip_locate_info locate_index_info() const {
+        gbwt_hip_locate_info info{};
+        check(gbwt_hip_locate_index_info(index_.get(), &info));
+        return info;
+    }
+
     const gbwt_hip_index *handle() const { return index_.get(); }
     gbwt_hip_workspace *workspace() const { return ws_.get(); }
 
