@@ -106,6 +106,12 @@ class LocateInfo(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class BuildInfo(C.Structure):
+    _fields_ = [("visits", C.c_uint64), ("sequences", C.c_uint64), ("records", C.c_uint64), ("data_bytes", C.c_uint64), ("peak_scratch_bytes", C.c_uint64),
+                ("rounds", C.c_uint32), ("built", C.c_uint32), ("expand_ms", C.c_float), ("rank_ms", C.c_float), ("edges_ms", C.c_float),
+                ("encode_ms", C.c_float), ("open_ms", C.c_double)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -187,6 +193,11 @@ SIGNATURES = {
     "gbwt_hip_last_locate_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gbwt_hip_locate_count_steps": (_int, [_p, _p, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_locate_index_info": (_int, [_p, C.POINTER(LocateInfo)]),
+    "gbwt_hip_build_from_paths": (_int, [_p, _p, _u64, _int, _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_build_from_rows_device": (_int, [_p, _p, _u64, _int, _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_records": (_int, [_p, _p, _u64, C.POINTER(_u64), _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_save": (_int, [_p, C.c_char_p]),
+    "gbwt_hip_last_build_info": (_int, [_p, C.POINTER(BuildInfo)]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_copy_path": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64)]),

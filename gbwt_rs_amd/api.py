@@ -21,6 +21,8 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBZ.graph_lines()                gbunzip's H-, S- and L-lines   src/bin/gbunzip.rs:193-332
   GBWT.locate / locate_csr / locate_positions      the C++ GBWT's locate(SearchState) / locate(node, i): the sequences behind a search state
                                    (the reference has no counterpart: "Locate queries" is the open box of its README's scope list)
+  GBWT.from_paths / from_rows_device               the C++ GBWT's construction: the index of a set of paths, made on the device ("GBWT
+                                   construction" in the same list); GBWT.records / save give the result back
 
 Every call goes through the C ABI of libgbwt_hip.so (hand-written HIP); "not found" is reported as
 None / a False entry of the validity mask, never as an exception.
@@ -31,7 +33,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BdState, Components, EdgeRows, GbwtHipError, GraphText, Lines, Located, LocateInfo, Memory, OpenTimes, Paths, Pos, State, Stats, check
+from ._lib import BdState, BuildInfo, Components, EdgeRows, GbwtHipError, GraphText, Lines, Located, LocateInfo, Memory, OpenTimes, Paths, Pos, State, Stats, check
 
 FORWARD, REVERSE = 0, 1  # support::Orientation, src/support.rs:30-47
 PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY = 0, 1, 2  # gbunzip's PathMode, src/bin/gbunzip.rs:63-76
@@ -112,6 +114,63 @@ class GBWT:
         check(_lib.lib().gbwt_hip_open_records_flags(_ptr(d), d.size, _ptr(s), s.size, alphabet_offset, alphabet_size,
                                                      sequences, size, int(bidirectional), device, flags, C.byref(h)))
         return cls(h, device=device)
+
+    @staticmethod
+    def _path_set(paths):
+        """(offsets u64[n + 1], nodes u64) of a list of paths; every path one-dimensional, of integers, none of them negative."""
+        rows = []
+        for k, p in enumerate(paths):
+            a = np.asarray(p)
+            if a.ndim != 1:
+                raise ValueError(f"path {k} is not one-dimensional")
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError(f"path {k} does not hold integers")
+            if a.size and a.dtype.kind == "i" and int(a.min()) < 0:
+                raise ValueError(f"path {k} holds a negative node")
+            rows.append(a.astype(np.uint64))
+        offsets = np.zeros(len(rows) + 1, dtype=np.uint64)
+        if rows:
+            np.cumsum([r.size for r in rows], out=offsets[1:])
+        nodes = np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint64)
+        return offsets, np.ascontiguousarray(nodes, dtype=np.uint64)
+
+    @classmethod
+    def from_paths(cls, paths, bidirectional=True, device=0, flags=_lib.OPEN_ALL):
+        """The GBWT of a set of paths, constructed on the device (gbwt_hip_build_from_paths).  paths: a list of lists or numpy arrays of
+        GBWT-encoded nodes (2 * id + orientation, id >= 1); bidirectional: sequence 2p is path p, sequence 2p + 1 its reverse."""
+        offsets, nodes = cls._path_set(paths)
+        h = C.c_void_p()
+        check(_lib.lib().gbwt_hip_build_from_paths(offsets.ctypes.data, _ptr(nodes), offsets.size - 1, int(bool(bidirectional)), device, flags, C.byref(h)))
+        return cls(h, device=device)
+
+    @classmethod
+    def from_rows_device(cls, paths_struct, n, bidirectional=True, device=0, flags=_lib.OPEN_ALL):
+        """The same for the first n rows of a device-resident extraction (the Paths struct of extract_device): the rows are only read."""
+        if not isinstance(paths_struct, Paths):
+            raise TypeError("from_rows_device takes the Paths struct of extract_device")
+        if n < 0 or n > paths_struct.n:
+            raise ValueError(f"n = {n} rows of a struct that holds {paths_struct.n}")
+        h = C.c_void_p()
+        check(_lib.lib().gbwt_hip_build_from_rows_device(paths_struct.d_offsets, paths_struct.d_nodes, n, int(bool(bidirectional)), device, flags, C.byref(h)))
+        return cls(h, device=device)
+
+    def records(self):
+        """(data u8[], starts u64[records]) of the handle: its record stream and dense record starts (gbwt_hip_records)."""
+        data_len, records = C.c_uint64(0), C.c_uint64(0)
+        check(self._L.gbwt_hip_records(self._h, None, 0, C.byref(data_len), None, 0, C.byref(records)))
+        data, starts = np.zeros(data_len.value, dtype=np.uint8), np.zeros(records.value, dtype=np.uint64)
+        check(self._L.gbwt_hip_records(self._h, _ptr(data), data.size, C.byref(data_len), _ptr(starts), starts.size, C.byref(records)))
+        return data, starts
+
+    def save(self, path):
+        """Writes the index in the simple-sds format (gbwt_hip_save): a GBZ handle as a GBZ v1 container, a GBWT handle as a GBWT file."""
+        check(self._L.gbwt_hip_save(self._h, os.fsencode(path)))
+
+    def last_build_info(self):
+        """The construction behind the handle (gbwt_hip_last_build_info): a dict; all zeros for a handle that was not built."""
+        b = BuildInfo()
+        check(self._L.gbwt_hip_last_build_info(self._h, C.byref(b)))
+        return {name: getattr(b, name) for name, _ in BuildInfo._fields_}
 
     def close(self):
         if getattr(self, "_ws", None):

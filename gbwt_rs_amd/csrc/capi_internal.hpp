@@ -1,4 +1,4 @@
-// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, capi_topology.hip, gfa.hip, comm.hip).
+// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, capi_topology.hip, capi_build.hip, gfa.hip, comm.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -380,6 +380,7 @@ struct gbwt_hip_index {
     bool starts_uploaded = false;         // ... and the record starts
     bool record_bytes_uploaded = false;   // gbwt_hip_open_file has copied the record bytes to `data` while the loader was still decoding
     gbwt_hip_open_times times{};      // where the time of the open went (gbwt_hip_get_open_times)
+    gbwt_hip_build_info build_info{}; // the construction behind the handle (capi_build.hip); zeros for a handle that was opened from a file or from records
     uint32_t uniform_len = 0;         // every sequence has this many nodes (0: lengths differ, or unknown): an extraction then knows its offsets without asking the device
     bool orientation_pairs = false;   // verified at open: sequence 2k + 1 is sequence 2k reversed (rows can be filled from both ends)
     gbwt_hip_stats stats{};

@@ -587,6 +587,55 @@ typedef struct {
 } gbwt_hip_locate_info;
 gbwt_hip_status gbwt_hip_locate_index_info(const gbwt_hip_index *index, gbwt_hip_locate_info *out);
 
+/* ---- construction: an index from a set of paths ------------------------------------------------------------------------------------------
+ * What the C++ GBWT's builder does and the reference lacks ("GBWT construction" leads the list of what its README leaves open): the GBWT of
+ * a set of paths, made on the device.  The result is a handle like any other -- a bare GBWT: no metadata, no graph -- opened the way
+ * gbwt_hip_open_records_flags opens one (`flags` as there).
+ *
+ * A path set is a CSR over GBWT-encoded nodes (2 * id + orientation, id >= 1, so every node is >= 2): path p = nodes[offsets[p] ..
+ * offsets[p + 1]), offsets[0] = 0.  bidirectional != 0: sequence 2p is path p and sequence 2p + 1 its reverse with every node flipped
+ * (support::reverse_path); bidirectional == 0: sequence p is path p.  Zero paths, and paths without nodes, are valid.
+ *
+ * The index: alphabet_offset = smallest node - 1 and alphabet_size = largest node + 1 over the SEQUENCES (0 and 1 when nobody visits a
+ * node); record r is node r + alphabet_offset, record 0 the endmarker's, a node nobody visits the one byte 0.  A record lists the successor
+ * (0 at the end of the sequence) of every visit of its node, the visits ordered by reverse prefix: the nodes before the visit read
+ * backwards, node by node; the start of a sequence is below every node, two visits whose prefixes reach the start together are ordered by
+ * sequence id.  The endmarker's record lists the first node of every sequence (0 for an empty one) in sequence order.  Edge v -> w carries
+ * the number of visits of w whose predecessor is smaller than v (0 for w = 0 and in the endmarker's record).  Bytes as BWTBuilder::append
+ * writes them (src/bwt.rs:241-253; ByteCode src/support.rs:1063-1070, RLE src/support.rs:1238-1248).
+ *
+ * Widths.  The construction counts in 32 bits: every node, the number of sequences, and visits + sequences (over the sequences, so twice
+ * the paths' for a bidirectional index) must fit 32 bits -- at most 2^32 - 1 --, and the alphabet must hold fewer than 2^30 records; beyond that:
+ * GBWT_HIP_UNSUPPORTED, as at an open.  GBWT_HIP_BAD_ARGUMENT, before the device is touched: a null pointer (nodes may be NULL when
+ * offsets[n_paths] = 0, offsets when n_paths = 0 as well), bidirectional other than 0 / 1, bad flags, offsets that do not start at 0 or
+ * that decrease, a node below 2.  The nodes of gbwt_hip_build_from_rows_device are checked on the device (same status).
+ *
+ * gbwt_hip_build_from_rows_device: the same for rows that lie in HBM of `device` already, in the layout gbwt_hip_extract_device leaves in a
+ * gbwt_hip_paths: d_offsets u64[n_paths + 1], d_nodes u32.  The rows are only read; the call returns when the handle is open. */
+gbwt_hip_status gbwt_hip_build_from_paths(const uint64_t *offsets, const uint64_t *nodes, uint64_t n_paths, int bidirectional, int device, uint32_t flags,
+                                          gbwt_hip_index **out);
+gbwt_hip_status gbwt_hip_build_from_rows_device(const uint64_t *d_offsets, const uint32_t *d_nodes, uint64_t n_paths, int bidirectional, int device, uint32_t flags,
+                                                gbwt_hip_index **out);
+/* The record stream and the dense record starts of any handle, from its host image: record r = data[starts[r] .. starts[r + 1]), the last
+ * one ends at *data_len (the inputs of gbwt_hip_open_records).  *data_len and *n_records are always filled; the bytes are copied when
+ * out_data != NULL and out_starts != NULL and both capacities suffice (else GBWT_HIP_CAPACITY; both NULL is a size query). */
+gbwt_hip_status gbwt_hip_records(const gbwt_hip_index *index, uint8_t *out_data, uint64_t data_capacity, uint64_t *data_len, uint64_t *out_starts,
+                                 uint64_t starts_capacity, uint64_t *n_records);
+/* Writes the handle in the simple-sds format (Serialize for GBWT, src/gbwt.rs:389-400; for GBZ, src/gbz.rs:662-672): a GBZ handle as a
+ * GBZ v1 container, a GBWT handle as a GBWT file.  A file that was loaded is written back as it was. */
+gbwt_hip_status gbwt_hip_save(const gbwt_hip_index *index, const char *path);
+/* The construction behind a handle; all zeros (built = 0) for a handle that was not built.  visits / sequences: over the sequences;
+ * rounds: doubling rounds of the ranking, at most ceil(log2(longest sequence + 1)); peak_scratch_bytes: the most HBM the construction
+ * held at once besides the caller's rows (all given back before the open); *_ms: HIP events around the four phases; open_ms: host
+ * clock around the open behind them. */
+typedef struct {
+    uint64_t visits, sequences, records, data_bytes, peak_scratch_bytes;
+    uint32_t rounds, built;
+    float expand_ms, rank_ms, edges_ms, encode_ms;
+    double open_ms;
+} gbwt_hip_build_info;
+gbwt_hip_status gbwt_hip_last_build_info(const gbwt_hip_index *index, gbwt_hip_build_info *out);
+
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex
  * (src/bin/gbunzip.rs:27, 421-434).  Sharded over GPUs -- one process per GPU, the index replicated, path p on rank p mod world

@@ -76,6 +76,37 @@ public:
         index_.reset(h, gbwt_hip_close);
         init();
     }
+    // ---- construction on the device (gbwt_hip.h, "construction"): the index of a set of paths of GBWT-encoded nodes (2 * id + orientation)
+    static GBWT from_paths(const std::vector<std::vector<uint64_t>> &paths, bool bidirectional = true, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
+        std::vector<uint64_t> offsets(1, 0), nodes;
+        for (const auto &p : paths) { nodes.insert(nodes.end(), p.begin(), p.end()); offsets.push_back(nodes.size()); }
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_build_from_paths(offsets.data(), nodes.data(), paths.size(), bidirectional ? 1 : 0, device, flags, &h));
+        return GBWT(h);
+    }
+    // ... of the first n rows of a device-resident extraction (gbwt_hip_extract_device); the rows are only read
+    static GBWT from_rows_device(const gbwt_hip_paths &rows, uint64_t n, bool bidirectional = true, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
+        if (n > rows.n) throw Error(GBWT_HIP_BAD_ARGUMENT, "more rows than the extraction holds");
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_build_from_rows_device(rows.d_offsets, rows.d_nodes, n, bidirectional ? 1 : 0, device, flags, &h));
+        return GBWT(h);
+    }
+    // the record stream and the dense record starts of the handle (gbwt_hip_records)
+    std::pair<std::vector<uint8_t>, std::vector<uint64_t>> records() const {
+        uint64_t data_len = 0, n = 0;
+        check(gbwt_hip_records(index_.get(), nullptr, 0, &data_len, nullptr, 0, &n));
+        std::vector<uint8_t> data(data_len);
+        std::vector<uint64_t> starts(n);
+        check(gbwt_hip_records(index_.get(), data.data(), data.size(), &data_len, starts.data(), starts.size(), &n));
+        return {std::move(data), std::move(starts)};
+    }
+    // a GBZ handle as a GBZ v1 container, a GBWT handle as a GBWT file
+    void save(const std::string &path) const { check(gbwt_hip_save(index_.get(), path.c_str())); }
+    gbwt_hip_build_info last_build_info() const {
+        gbwt_hip_build_info info{};
+        check(gbwt_hip_last_build_info(index_.get(), &info));
+        return info;
+    }
     GBWT clone_workspace() const { GBWT other(*this, 0); return other; }
 
     // ---- statistics, src/gbwt.rs:108-182
@@ -267,6 +298,7 @@ protected:
         return out;
     }
     GBWT(const GBWT &other, int) : index_(other.index_), stats_(other.stats_) { make_workspace(); }
+    explicit GBWT(gbwt_hip_index *built) { index_.reset(built, gbwt_hip_close); init(); }
     void init() {
         check(gbwt_hip_get_stats(index_.get(), &stats_));
         make_workspace();
