@@ -7,7 +7,7 @@ jltsiren/gbwt-rs: batched path extraction (SequenceIter) and find/extend/bidirec
 """
 from ._lib import OPEN_ALL, OPEN_EXTRACT, OPEN_GFA, OPEN_SEARCH
 from .api import (BD_DTYPE, FORWARD, GBWT, GBZ, PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY, POS_DTYPE, REVERSE, STATE_DTYPE, GbwtHipError, decode_node, device_count, device_memory,
-                  encode_node, encode_path, flip_node, parse_file)
+                  encode_node, encode_path, flip_node, parse_file, parse_gfa)
 
 __all__ = ["OPEN_ALL", "OPEN_EXTRACT", "OPEN_GFA", "OPEN_SEARCH", "GBWT", "GBZ", "GbwtHipError", "FORWARD", "REVERSE", "PATHS_DEFAULT", "PATHS_PAN_SN", "PATHS_REF_ONLY", "POS_DTYPE", "STATE_DTYPE", "BD_DTYPE", "encode_node",
-           "decode_node", "flip_node", "encode_path", "device_count", "device_memory", "parse_file"]
+           "decode_node", "flip_node", "encode_path", "device_count", "device_memory", "parse_file", "parse_gfa"]

@@ -112,6 +112,13 @@ class BuildInfo(C.Structure):
                 ("encode_ms", C.c_float), ("open_ms", C.c_double)]
 
 
+class GfaInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("bytes", "lines", "headers", "segments", "links", "p_lines", "w_lines", "ignored_lines", "steps", "label_bytes",
+                                                "tile_bytes", "peak_parse_bytes")] + \
+               [("structure_ms", C.c_float), ("steps_ms", C.c_float), ("labels_ms", C.c_float), ("reserved", C.c_float),
+                ("read_ms", C.c_double), ("upload_ms", C.c_double), ("metadata_ms", C.c_double)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -198,6 +205,10 @@ SIGNATURES = {
     "gbwt_hip_records": (_int, [_p, _p, _u64, C.POINTER(_u64), _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_save": (_int, [_p, C.c_char_p]),
     "gbwt_hip_last_build_info": (_int, [_p, C.POINTER(BuildInfo)]),
+    "gbwt_hip_build_from_gfa": (_int, [C.c_char_p, _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_build_from_gfa_text": (_int, [_p, _u64, _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_last_gfa_info": (_int, [_p, C.POINTER(GfaInfo)]),
+    "gbwt_hip_parse_gfa": (_int, [C.c_char_p, C.POINTER(GfaInfo)]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_copy_path": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64)]),

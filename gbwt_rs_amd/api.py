@@ -33,7 +33,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BdState, BuildInfo, Components, EdgeRows, GbwtHipError, GraphText, Lines, Located, LocateInfo, Memory, OpenTimes, Paths, Pos, State, Stats, check
+from ._lib import BdState, BuildInfo, Components, EdgeRows, GbwtHipError, GfaInfo, GraphText, Lines, Located, LocateInfo, Memory, OpenTimes, Paths, Pos, State, Stats, check
 
 FORWARD, REVERSE = 0, 1  # support::Orientation, src/support.rs:30-47
 PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY = 0, 1, 2  # gbunzip's PathMode, src/bin/gbunzip.rs:63-76
@@ -77,6 +77,13 @@ def parse_file(path):
     st = Stats()
     check(_lib.lib().gbwt_hip_parse_file(os.fsencode(path), C.byref(st)))
     return st
+
+
+def parse_gfa(path):
+    """Host-only counts of a GFA file (gbwt_hip_parse_gfa, no GPU): a dict with the fields of gbwt_hip_gfa_info."""
+    g = GfaInfo()
+    check(_lib.lib().gbwt_hip_parse_gfa(os.fsencode(path), C.byref(g)))
+    return {name: getattr(g, name) for name, _ in GfaInfo._fields_}
 
 
 def _ptr(a):
@@ -678,6 +685,30 @@ class GBWT:
 
 class GBZ(GBWT):
     """gbz::GBZ for the hot path: GBZ::path / paths (src/gbz.rs:446-466)."""
+
+    @classmethod
+    def from_gfa(cls, path, device=0, flags=_lib.OPEN_ALL):
+        """The GBZ of a GFA file, parsed and constructed on the device (gbwt_hip_build_from_gfa): gbunzip's inverse.  What is accepted:
+        include/gbwt_hip.h, "construction from GFA"."""
+        h = C.c_void_p()
+        check(_lib.lib().gbwt_hip_build_from_gfa(os.fsencode(path), device, flags, C.byref(h)))
+        return cls(h, device=device)
+
+    @classmethod
+    def from_gfa_text(cls, data, device=0, flags=_lib.OPEN_ALL):
+        """The same for a GFA text in memory: bytes, a bytearray, or a str (encoded as UTF-8)."""
+        if isinstance(data, str):
+            data = data.encode()
+        text = np.frombuffer(bytes(data), dtype=np.uint8)
+        h = C.c_void_p()
+        check(_lib.lib().gbwt_hip_build_from_gfa_text(_ptr(text), text.size, device, flags, C.byref(h)))
+        return cls(h, device=device)
+
+    def last_gfa_info(self):
+        """The parse behind a handle made from GFA (gbwt_hip_last_gfa_info): a dict; all zeros for every other handle."""
+        g = GfaInfo()
+        check(self._L.gbwt_hip_last_gfa_info(self._h, C.byref(g)))
+        return {name: getattr(g, name) for name, _ in GfaInfo._fields_}
 
     def paths(self):
         return self.sequences() // 2

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "../../include/gbwt_hip.h"
 #include "host_index.hpp"
 
 namespace gbwt_hip {
@@ -38,5 +39,11 @@ void build_records_on_device(const BuildInput &in, BuildOutput &out, hipStream_t
 
 // min and max of n > 0 nodes in HBM (the caller of a device-resident input checks and sizes with them)
 void build_node_range(const uint32_t *d_nodes, uint64_t n, uint32_t &min_node, uint32_t &max_node, hipStream_t s);
+
+// capi_build.hip, shared with the construction from GFA (capi_gfa_build.hip): the widths of the construction as statuses (the message
+// in the thread's error slot), and the records of a set of paths without visits
+gbwt_hip_status check_build_sizes(uint64_t n_paths, uint64_t path_visits, int bidirectional);
+gbwt_hip_status check_build_range(uint64_t min_node, uint64_t max_node);
+void build_without_visits(uint64_t sequences, BuildOutput &out);
 
 }  // namespace gbwt_hip

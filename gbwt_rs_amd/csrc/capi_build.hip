@@ -30,14 +30,12 @@ gbwt_hip_status check_call(const void *offsets, uint64_t n_paths, int bidirectio
     return GBWT_HIP_OK;
 }
 
-// offsets on the host: a CSR, and sizes the construction counts in 32 bits
-gbwt_hip_status check_offsets(const uint64_t *offsets, uint64_t n_paths, int bidirectional, uint64_t &path_visits) {
-    path_visits = 0;
-    if (n_paths == 0) return GBWT_HIP_OK;
-    if (offsets[0] != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "offsets must start at 0 (offsets[0] = " + std::to_string(offsets[0]) + ")");
-    for (uint64_t p = 0; p < n_paths; p++)
-        if (offsets[p + 1] < offsets[p]) return fail(GBWT_HIP_BAD_ARGUMENT, "offsets decrease at path " + std::to_string(p));
-    path_visits = offsets[n_paths];
+}  // namespace
+
+namespace gbwt_hip {
+
+// sizes the construction counts in 32 bits (also the check of a construction from GFA, capi_gfa_build.hip)
+gbwt_hip_status check_build_sizes(uint64_t n_paths, uint64_t path_visits, int bidirectional) {
     const uint64_t limit = BUILD_MAX_SLOTS >> bidirectional;
     if (n_paths > limit || path_visits > limit || n_paths + path_visits > limit)
         return fail(GBWT_HIP_UNSUPPORTED, std::to_string(path_visits) + " visits + " + std::to_string(n_paths) + " sequences" + (bidirectional ? ", twice in a bidirectional index" : "") +
@@ -45,7 +43,7 @@ gbwt_hip_status check_offsets(const uint64_t *offsets, uint64_t n_paths, int bid
     return GBWT_HIP_OK;
 }
 
-gbwt_hip_status check_range(uint64_t min_node, uint64_t max_node) {
+gbwt_hip_status check_build_range(uint64_t min_node, uint64_t max_node) {
     if (max_node > 0xFFFFFFFFull) return fail(GBWT_HIP_UNSUPPORTED, "alphabet_size > 2^32 is not supported (u32 node ids on device)");
     if (max_node + 1 - (min_node - 1) >= BUILD_MAX_RECORDS) return fail(GBWT_HIP_UNSUPPORTED, "more than 2^30 records are not supported");
     return GBWT_HIP_OK;
@@ -60,6 +58,23 @@ void build_without_visits(uint64_t sequences, BuildOutput &o) {
     o.data.assign(bytes, p);
     o.starts.assign(1, 0);
 }
+
+}  // namespace gbwt_hip
+
+namespace {
+
+// offsets on the host: a CSR, and sizes the construction counts in 32 bits
+gbwt_hip_status check_offsets(const uint64_t *offsets, uint64_t n_paths, int bidirectional, uint64_t &path_visits) {
+    path_visits = 0;
+    if (n_paths == 0) return GBWT_HIP_OK;
+    if (offsets[0] != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "offsets must start at 0 (offsets[0] = " + std::to_string(offsets[0]) + ")");
+    for (uint64_t p = 0; p < n_paths; p++)
+        if (offsets[p + 1] < offsets[p]) return fail(GBWT_HIP_BAD_ARGUMENT, "offsets decrease at path " + std::to_string(p));
+    path_visits = offsets[n_paths];
+    return check_build_sizes(n_paths, path_visits, bidirectional);
+}
+
+gbwt_hip_status check_range(uint64_t min_node, uint64_t max_node) { return check_build_range(min_node, max_node); }
 
 // d_offsets / d_nodes in HBM of `device` (made current by the caller), the range of the nodes over the sequences known
 gbwt_hip_status build_and_open(const uint64_t *d_offsets, const uint32_t *d_nodes, uint64_t n_paths, uint64_t path_visits, uint64_t min_node, uint64_t max_node, int bidirectional,

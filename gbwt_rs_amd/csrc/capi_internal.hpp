@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <memory>
 #include <mutex>
 #include <cstdio>
@@ -381,6 +382,7 @@ struct gbwt_hip_index {
     bool record_bytes_uploaded = false;   // gbwt_hip_open_file has copied the record bytes to `data` while the loader was still decoding
     gbwt_hip_open_times times{};      // where the time of the open went (gbwt_hip_get_open_times)
     gbwt_hip_build_info build_info{}; // the construction behind the handle (capi_build.hip); zeros for a handle that was opened from a file or from records
+    gbwt_hip_gfa_info gfa_info{};     // the parse behind a handle made from GFA (capi_gfa_build.hip); zeros for every other handle
     uint32_t uniform_len = 0;         // every sequence has this many nodes (0: lengths differ, or unknown): an extraction then knows its offsets without asking the device
     bool orientation_pairs = false;   // verified at open: sequence 2k + 1 is sequence 2k reversed (rows can be filled from both ends)
     gbwt_hip_stats stats{};
@@ -484,6 +486,10 @@ struct gbwt_hip_workspace {
 };
 
 namespace gbwt_hip {
+// capi_open.hip: the open behind every handle -- device passes, GFA tables, line cache -- for a host image that is already filled (takes
+// ownership; t_open: when the caller started, for the handle's open times).  Settings (knobs, caps, device) are the caller's to set.
+gbwt_hip_status open_host_index(std::unique_ptr<gbwt_hip_index> ix, gbwt_hip_index **out, std::chrono::steady_clock::time_point t_open);
+
 // The labels of a handle as the kernels see them (sequences.hip, tags.hip): node v (GBWT-encoded, 2 id + o) has label bytes[off[s] .. off[s + 1])
 // with s = (v & ~1 - first_node) / 2 (GBZ::graph_node_to_sequence, src/gbz.rs:246-255); a node outside [first_node, first_node + 2 n) has none.
 struct Labels { const uint8_t *bytes; const uint64_t *off; uint64_t n; uint32_t first_node; };

@@ -692,6 +692,11 @@ gbwt_hip_status open_common(std::unique_ptr<gbwt_hip_index> ix, gbwt_hip_index *
 
 }  // namespace
 
+namespace gbwt_hip {
+// (capi_gfa_build.hip: a host image made from a GFA text is opened like one read from a file)
+gbwt_hip_status open_host_index(std::unique_ptr<gbwt_hip_index> ix, gbwt_hip_index **out, std::chrono::steady_clock::time_point t_open) { return open_common(std::move(ix), out, t_open); }
+}  // namespace gbwt_hip
+
 extern "C" {
 
 const char *gbwt_hip_last_error(void) { return last_error_slot().c_str(); }

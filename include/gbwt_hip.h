@@ -636,6 +636,50 @@ typedef struct {
 } gbwt_hip_build_info;
 gbwt_hip_status gbwt_hip_last_build_info(const gbwt_hip_index *index, gbwt_hip_build_info *out);
 
+/* ---- construction from GFA: gbunzip's inverse ------------------------------------------------------------------------------------------------
+ * A GFA file, or a GFA text in host memory, becomes a GBZ handle like any loaded one -- records, metadata, tags and node labels --, parsed
+ * and built on the device.  The rows of the paths go from the parse to the construction above without leaving HBM; the index is
+ * bidirectional and is exactly that construction over the rows.
+ *
+ * Accepted input.
+ *   Lines end in '\n'; the last one may lack it; empty lines are skipped.  A '\r' anywhere: GBWT_HIP_INVALID_DATA.  A line whose first byte
+ *   is not H, S, L, P or W is ignored (and counted).
+ *   H: the value of an RS:Z: field (of the first H-line that has one) becomes the tag reference_samples of the GBWT and of the GBZ, verbatim.
+ *   S <name> <sequence> [...]: name is a decimal node id in 1 .. 2^31 - 1 without sign or leading zero; sequence is one or more bytes
+ *     ("*" is refused); later fields are ignored.  A name that is not such an integer: GBWT_HIP_UNSUPPORTED -- it needs a node-to-segment
+ *     translation, which is not built.  A second S-line of an id: INVALID_DATA.  Nothing is chopped: a label has any length.
+ *   L: at least five fields, and not otherwise read.  The edges of the result are those the paths use, as in a GBWTGraph: a link that no
+ *     path crosses is not in the result, and gbwt_hip_write_gfa will not print it.
+ *   P <name> <steps> [...]: steps = id+ / id- joined by ','; an empty field or "*" = no steps.  The name is NOT parsed as PanSN: every
+ *     P-line is a generic path (sample _gbwt_ref, the whole name as contig, haplotype 0, fragment 0).
+ *   W <sample> <hap> <contig> <start> <end> <walk>: walk = >id / <id; empty or "*" = no steps; hap a decimal number below 2^32 - 1; start
+ *     a decimal number below 2^32, or "*" = 0; end is not read.  The path is (sample, contig, hap, start).
+ *   Every step names a segment with an S-line anywhere in the file (else INVALID_DATA); line order is free.
+ *   Path order: the P-lines in file order, then the W-lines in file order -- what gbunzip writes, so a file it wrote keeps its path ids.
+ *   Metadata: sample names "_gbwt_ref" (iff there is a P-line), then the W samples by first appearance; contig names by first appearance
+ *     over the paths in path order; haplotypes = distinct (sample, haplotype).  Two paths with the same four fields: INVALID_DATA.
+ *   Graph: no translation; a segment that no path visits has no node in a GBZ, and its label is dropped.
+ *   A refusal names the 1-based number of the FIRST offending line in file order, and nothing is constructed.  Sizes beyond the widths of
+ *   the construction above: GBWT_HIP_UNSUPPORTED, in its wording; more than 2^31 - 1 lines likewise.
+ * GBWT_HIP_BAD_ARGUMENT (null path / text with len > 0 / out, bad flags) and GBWT_HIP_IO_ERROR (a file that cannot be read) answer before
+ * the device is touched.  `flags` as in gbwt_hip_open_file_flags. */
+gbwt_hip_status gbwt_hip_build_from_gfa(const char *path, int device, uint32_t flags, gbwt_hip_index **out);
+gbwt_hip_status gbwt_hip_build_from_gfa_text(const char *text, uint64_t len, int device, uint32_t flags, gbwt_hip_index **out);
+/* The parse behind a handle made from GFA; all zeros for every other handle (gbwt_hip_last_build_info answers for the construction).
+ * lines: the non-empty ones, of which headers + segments + links + p_lines + w_lines + ignored_lines; steps: of all paths; label_bytes:
+ * the sequences of all S-lines; tile_bytes: the text a wave reads at once; peak_parse_bytes: the most HBM the parse held at once (text
+ * and tables, without the rows; all given back before the construction starts); structure / steps / labels: HIP events around the three
+ * phases; read / upload / metadata: host clock around the mapping of the file, the copy of the text to the device, and the metadata. */
+typedef struct {
+    uint64_t bytes, lines, headers, segments, links, p_lines, w_lines, ignored_lines, steps, label_bytes, tile_bytes, peak_parse_bytes;
+    float structure_ms, steps_ms, labels_ms, reserved;
+    double read_ms, upload_ms, metadata_ms;
+} gbwt_hip_gfa_info;
+gbwt_hip_status gbwt_hip_last_gfa_info(const gbwt_hip_index *index, gbwt_hip_gfa_info *out);
+/* The counts of a GFA file without a device and without the checks of a construction (only a '\r' is refused): bytes .. label_bytes and
+ * tile_bytes are filled, steps = the orientation marks of the step fields. */
+gbwt_hip_status gbwt_hip_parse_gfa(const char *path, gbwt_hip_gfa_info *out);
+
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex
  * (src/bin/gbunzip.rs:27, 421-434).  Sharded over GPUs -- one process per GPU, the index replicated, path p on rank p mod world

@@ -339,6 +339,27 @@ class GBZ : public GBWT {
 public:
     explicit GBZ(const std::string &path, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) : GBWT(path, device, flags) {}
 
+private:
+    explicit GBZ(gbwt_hip_index *built) : GBWT(built) {}
+
+public:
+    // ---- construction from GFA on the device (gbwt_hip.h, "construction from GFA"): a GBZ like a loaded one, from a file or a text in memory
+    static GBZ from_gfa(const std::string &path, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_build_from_gfa(path.c_str(), device, flags, &h));
+        return GBZ(h);
+    }
+    static GBZ from_gfa_text(const char *text, uint64_t len, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_build_from_gfa_text(text, len, device, flags, &h));
+        return GBZ(h);
+    }
+    gbwt_hip_gfa_info last_gfa_info() const {
+        gbwt_hip_gfa_info info{};
+        check(gbwt_hip_last_gfa_info(index_.get(), &info));
+        return info;
+    }
+
     uint64_t paths() const { return sequences() / 2; }   // GBZ::paths, src/gbz.rs:446-452
     // GBZ::path(path_id, orientation).collect(): (node id, orientation) pairs, or nullopt (src/gbz.rs:461-466)
     std::optional<std::vector<std::pair<uint64_t, Orientation>>> path(uint64_t path_id, Orientation orientation) const {
