@@ -119,6 +119,18 @@ class GfaInfo(C.Structure):
                 ("read_ms", C.c_double), ("upload_ms", C.c_double), ("metadata_ms", C.c_double)]
 
 
+GFA_TRANSLATE_NEVER, GFA_TRANSLATE_AUTO, GFA_TRANSLATE_ALWAYS = 0, 1, 2     # gbwt_hip_gfa_options.translate
+
+
+class GfaOptions(C.Structure):
+    _fields_ = [("max_node_length", C.c_uint32), ("translate", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+class GfaTranslationInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("translated", "segments", "nodes", "chopped_segments", "unvisited_segments", "name_bytes", "table_bytes")] + \
+               [("names_ms", C.c_float), ("expand_ms", C.c_float), ("reserved", C.c_float * 2)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -208,6 +220,9 @@ SIGNATURES = {
     "gbwt_hip_build_from_gfa": (_int, [C.c_char_p, _int, C.c_uint32, C.POINTER(_p)]),
     "gbwt_hip_build_from_gfa_text": (_int, [_p, _u64, _int, C.c_uint32, C.POINTER(_p)]),
     "gbwt_hip_last_gfa_info": (_int, [_p, C.POINTER(GfaInfo)]),
+    "gbwt_hip_build_from_gfa_opts": (_int, [C.c_char_p, C.POINTER(GfaOptions), _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_build_from_gfa_text_opts": (_int, [_p, _u64, C.POINTER(GfaOptions), _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_last_gfa_translation_info": (_int, [_p, C.POINTER(GfaTranslationInfo)]),
     "gbwt_hip_parse_gfa": (_int, [C.c_char_p, C.POINTER(GfaInfo)]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),

@@ -686,23 +686,49 @@ class GBWT:
 class GBZ(GBWT):
     """gbz::GBZ for the hot path: GBZ::path / paths (src/gbz.rs:446-466)."""
 
+    @staticmethod
+    def _gfa_options(max_node, translate):
+        """gbwt_hip_gfa_options of the two keywords, or None for the call without options.  max_node alone chops where a segment is longer
+        (translate = AUTO); translate alone chops nothing."""
+        if max_node is None and translate is None:
+            return None
+        if translate is None:
+            translate = _lib.GFA_TRANSLATE_AUTO
+        return _lib.GfaOptions(int(max_node or 0), int(translate))
+
     @classmethod
-    def from_gfa(cls, path, device=0, flags=_lib.OPEN_ALL):
+    def from_gfa(cls, path, device=0, flags=_lib.OPEN_ALL, max_node=None, translate=None):
         """The GBZ of a GFA file, parsed and constructed on the device (gbwt_hip_build_from_gfa): gbunzip's inverse.  What is accepted:
-        include/gbwt_hip.h, "construction from GFA"."""
+        include/gbwt_hip.h, "construction from GFA".  max_node (segments longer than that many bases are chopped into nodes; gfa2gbwt's
+        default is 1024) and translate (GFA_TRANSLATE_NEVER | _AUTO | _ALWAYS) build a node-to-segment translation, for segment names that
+        are no node ids (gbwt_hip_build_from_gfa_opts); both None is the call without options."""
         h = C.c_void_p()
-        check(_lib.lib().gbwt_hip_build_from_gfa(os.fsencode(path), device, flags, C.byref(h)))
+        opts = cls._gfa_options(max_node, translate)
+        if opts is None:
+            check(_lib.lib().gbwt_hip_build_from_gfa(os.fsencode(path), device, flags, C.byref(h)))
+        else:
+            check(_lib.lib().gbwt_hip_build_from_gfa_opts(os.fsencode(path), C.byref(opts), device, flags, C.byref(h)))
         return cls(h, device=device)
 
     @classmethod
-    def from_gfa_text(cls, data, device=0, flags=_lib.OPEN_ALL):
+    def from_gfa_text(cls, data, device=0, flags=_lib.OPEN_ALL, max_node=None, translate=None):
         """The same for a GFA text in memory: bytes, a bytearray, or a str (encoded as UTF-8)."""
         if isinstance(data, str):
             data = data.encode()
         text = np.frombuffer(bytes(data), dtype=np.uint8)
         h = C.c_void_p()
-        check(_lib.lib().gbwt_hip_build_from_gfa_text(_ptr(text), text.size, device, flags, C.byref(h)))
+        opts = cls._gfa_options(max_node, translate)
+        if opts is None:
+            check(_lib.lib().gbwt_hip_build_from_gfa_text(_ptr(text), text.size, device, flags, C.byref(h)))
+        else:
+            check(_lib.lib().gbwt_hip_build_from_gfa_text_opts(_ptr(text), text.size, C.byref(opts), device, flags, C.byref(h)))
         return cls(h, device=device)
+
+    def last_gfa_translation_info(self):
+        """The translation behind a handle made from GFA (gbwt_hip_last_gfa_translation_info): a dict; all zeros for every other handle."""
+        g = _lib.GfaTranslationInfo()
+        check(self._L.gbwt_hip_last_gfa_translation_info(self._h, C.byref(g)))
+        return {name: getattr(g, name) for name, _ in _lib.GfaTranslationInfo._fields_ if name != "reserved"}
 
     def last_gfa_info(self):
         """The parse behind a handle made from GFA (gbwt_hip_last_gfa_info): a dict; all zeros for every other handle."""

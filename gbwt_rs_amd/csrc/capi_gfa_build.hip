@@ -44,17 +44,33 @@ gbwt_hip_status refuse(uint64_t line, uint32_t code) {
         case GFA_ERR_STEP: return fail(GBWT_HIP_INVALID_DATA, at + "a step that is not a node id (1 .. 2^31 - 1, no leading zero) with its orientation");
         case GFA_ERR_UNKNOWN_SEGMENT: return fail(GBWT_HIP_INVALID_DATA, at + "a step names a segment without an S-line");
         case GFA_ERR_DUPLICATE: return fail(GBWT_HIP_INVALID_DATA, at + "the second S-line of its segment");
+        case GFA_ERR_EMPTY_NAME: return fail(GBWT_HIP_INVALID_DATA, at + "a segment with an empty name");
+        case GFA_ERR_LONG_NAME: return fail(GBWT_HIP_UNSUPPORTED, at + "a segment name of more than 255 bytes is not supported");
+        case GFA_ERR_NAMED_STEP: return fail(GBWT_HIP_INVALID_DATA, at + "a step that is not a segment name with its orientation");
+        case GFA_ERR_DUPLICATE_NAME: return fail(GBWT_HIP_INVALID_DATA, at + "a later S-line of its segment name");
         default: return fail(GBWT_HIP_INVALID_DATA, at + "refused");
     }
 }
 
-gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, int device, uint32_t flags, gbwt_hip_index **out) {
+// NULL: the call without options
+gbwt_hip_status check_options(const gbwt_hip_gfa_options *opts, GfaParseOptions &parsed) {
+    parsed = GfaParseOptions();
+    if (!opts) return GBWT_HIP_OK;
+    if (opts->reserved[0] != 0 || opts->reserved[1] != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "options: reserved must be 0");
+    if (opts->translate > GBWT_HIP_GFA_TRANSLATE_ALWAYS) return fail(GBWT_HIP_BAD_ARGUMENT, "options: translate is one of GBWT_HIP_GFA_TRANSLATE_NEVER | _AUTO | _ALWAYS");
+    if (opts->translate == GBWT_HIP_GFA_TRANSLATE_NEVER && opts->max_node_length != 0)
+        return fail(GBWT_HIP_BAD_ARGUMENT, "options: max_node_length > 0 chops segments, which needs a translation (GBWT_HIP_GFA_TRANSLATE_AUTO or _ALWAYS)");
+    parsed.max_node_length = opts->max_node_length; parsed.translate = opts->translate;
+    return GBWT_HIP_OK;
+}
+
+gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, const GfaParseOptions &options, int device, uint32_t flags, gbwt_hip_index **out) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)"); }
     try {
         HIP_CHECK(hipSetDevice(device));
         Stream stream;
-        GfaDeviceParse parse(text, len, stream.s);
+        GfaDeviceParse parse(text, len, stream.s, options);
         parse.rows();
 
         // metadata, from the few bytes of the name fields; its refusals and the device's are one list in file order
@@ -73,7 +89,7 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
         if (bad && (!parse.refusal || bad.line < parse.refusal.line)) return fail(GBWT_HIP_INVALID_DATA, "GFA line " + std::to_string(bad.line) + ": " + bad.what);
         if (parse.refusal) return refuse(parse.refusal.line, parse.refusal.code);
 
-        const uint64_t n_paths = parse.n_paths, steps = parse.counts.steps;
+        const uint64_t n_paths = parse.n_paths, steps = parse.row_nodes;      // (translated: the nodes of the steps)
         gbwt_hip_status st = static_cast<gbwt_hip_status>(check_build_sizes(n_paths, steps, 1));
         if (st != GBWT_HIP_OK) return st;
         const uint64_t min_node = parse.min_node & ~uint64_t(1), max_node = parse.max_node | uint64_t(1);
@@ -84,6 +100,8 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
         Strings labels;
         uint64_t graph_nodes = 0;
         parse.labels(labels, graph_nodes);
+        GfaTranslation translation;
+        parse.translation(translation);
         parse.release_all_but_rows();             // the ranking holds 40 B per slot: the text and the tables of the parse are gone before it starts
 
         BuildOutput o;
@@ -102,7 +120,9 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
         h.path_names = std::move(meta.path_names); h.sample_names = std::move(meta.sample_names); h.contig_names = std::move(meta.contig_names);
         h.generic_phase_on_disk = meta.generic_phase_on_disk;
         if (have_reference_samples) { h.tags.emplace_back("reference_samples", reference_samples); h.gbz_tags.emplace_back("reference_samples", reference_samples); }
-        fill_gfa_graph(h, std::move(labels), graph_nodes);
+        const bool translated = parse.translated && steps != 0;             // (without visits there are no nodes to map)
+        if (translated) fill_gfa_translated_graph(h, std::move(labels), graph_nodes, std::move(translation.names), std::move(translation.starts), translation.mapping_len);
+        else fill_gfa_graph(h, std::move(labels), graph_nodes);
 
         gbwt_hip_build_info b{};
         b.visits = o.visits; b.sequences = o.sequences; b.records = o.records; b.data_bytes = o.data.size(); b.peak_scratch_bytes = o.peak_scratch;
@@ -115,11 +135,19 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
         g.structure_ms = parse.structure_ms; g.steps_ms = parse.steps_ms; g.labels_ms = parse.labels_ms;
         g.read_ms = read_ms; g.upload_ms = parse.upload_ms; g.metadata_ms = metadata_ms;
 
+        gbwt_hip_gfa_translation_info tr{};
+        tr.segments = c.segments;
+        if (translated) {
+            tr.translated = 1; tr.nodes = parse.total_nodes; tr.chopped_segments = parse.chopped_segments; tr.unvisited_segments = parse.unvisited_segments;
+            tr.name_bytes = parse.name_bytes; tr.table_bytes = parse.table_bytes; tr.names_ms = parse.names_ms; tr.expand_ms = parse.expand_ms;
+        }
+
         st = open_host_index(std::move(ix), out, t_open);
         if (st != GBWT_HIP_OK) return st;
         b.open_ms = ms_since(t_open);
         (*out)->build_info = b;
         (*out)->gfa_info = g;
+        (*out)->gfa_translation_info = tr;
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the construction does not fit in device memory: ") + e.what); }
@@ -135,7 +163,39 @@ gbwt_hip_status gbwt_hip_build_from_gfa_text(const char *text, uint64_t len, int
     GBWT_HIP_GUARD_BEGIN
     const gbwt_hip_status st = check_call(len ? static_cast<const void *>(text) : static_cast<const void *>(""), "text", flags, out);
     if (st != GBWT_HIP_OK) return st;
-    return build_from_text(text, len, 0.0, device, flags, out);
+    return build_from_text(text, len, 0.0, GfaParseOptions(), device, flags, out);
+    GBWT_HIP_GUARD_END
+}
+
+gbwt_hip_status gbwt_hip_build_from_gfa_text_opts(const char *text, uint64_t len, const gbwt_hip_gfa_options *opts, int device, uint32_t flags, gbwt_hip_index **out) {
+    GBWT_HIP_GUARD_BEGIN
+    gbwt_hip_status st = check_call(len ? static_cast<const void *>(text) : static_cast<const void *>(""), "text", flags, out);
+    if (st != GBWT_HIP_OK) return st;
+    GfaParseOptions options;
+    st = check_options(opts, options);
+    if (st != GBWT_HIP_OK) return st;
+    return build_from_text(text, len, 0.0, options, device, flags, out);
+    GBWT_HIP_GUARD_END
+}
+
+gbwt_hip_status gbwt_hip_build_from_gfa_opts(const char *path, const gbwt_hip_gfa_options *opts, int device, uint32_t flags, gbwt_hip_index **out) {
+    GBWT_HIP_GUARD_BEGIN
+    gbwt_hip_status st = check_call(path, "path", flags, out);
+    if (st != GBWT_HIP_OK) return st;
+    GfaParseOptions options;
+    st = check_options(opts, options);
+    if (st != GBWT_HIP_OK) return st;
+    const auto t0 = Clock::now();
+    const GfaFile file(path);                     // (IoError: before the device is touched)
+    return build_from_text(file.data(), file.size(), ms_since(t0), options, device, flags, out);
+    GBWT_HIP_GUARD_END
+}
+
+gbwt_hip_status gbwt_hip_last_gfa_translation_info(const gbwt_hip_index *ix, gbwt_hip_gfa_translation_info *out) {
+    GBWT_HIP_GUARD_BEGIN
+    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
+    *out = ix->gfa_translation_info;
+    return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
 
@@ -145,7 +205,7 @@ gbwt_hip_status gbwt_hip_build_from_gfa(const char *path, int device, uint32_t f
     if (st != GBWT_HIP_OK) return st;
     const auto t0 = Clock::now();
     const GfaFile file(path);                     // (IoError: before the device is touched)
-    return build_from_text(file.data(), file.size(), ms_since(t0), device, flags, out);
+    return build_from_text(file.data(), file.size(), ms_since(t0), GfaParseOptions(), device, flags, out);
     GBWT_HIP_GUARD_END
 }
 

@@ -383,6 +383,7 @@ struct gbwt_hip_index {
     gbwt_hip_open_times times{};      // where the time of the open went (gbwt_hip_get_open_times)
     gbwt_hip_build_info build_info{}; // the construction behind the handle (capi_build.hip); zeros for a handle that was opened from a file or from records
     gbwt_hip_gfa_info gfa_info{};     // the parse behind a handle made from GFA (capi_gfa_build.hip); zeros for every other handle
+    gbwt_hip_gfa_translation_info gfa_translation_info{};   // its translation, if it made one
     uint32_t uniform_len = 0;         // every sequence has this many nodes (0: lengths differ, or unknown): an extraction then knows its offsets without asking the device
     bool orientation_pairs = false;   // verified at open: sequence 2k + 1 is sequence 2k reversed (rows can be filled from both ends)
     gbwt_hip_stats stats{};

@@ -141,6 +141,15 @@ inline void fill_gfa_graph(HostIndex &h, Strings &&labels, uint64_t graph_nodes)
     h.segment_names = Strings(); h.segment_starts.clear(); h.mapping_len = 0;
 }
 
+// The graph of a GBZ with a translation, as the loader leaves it: one label per node 1 .. mapping_len - 1 (empty where no path goes), the
+// names of the segments (empty likewise) and the first node of each
+inline void fill_gfa_translated_graph(HostIndex &h, Strings &&labels, uint64_t graph_nodes, Strings &&names, Words &&starts, uint64_t mapping_len) {
+    h.is_gbz = true; h.has_translation = true;
+    h.graph_nodes = graph_nodes;
+    h.sequences_labels = std::move(labels);
+    h.segment_names = std::move(names); h.segment_starts = std::move(starts); h.mapping_len = mapping_len;
+}
+
 // The counts of a text, without a device and without the checks of a construction (only a carriage return is refused): what
 // gbwt_hip_parse_gfa answers.  steps: the orientation marks of the step fields; label_bytes: the sequences of all S-lines.
 inline GfaCounts count_gfa_on_host(const char *text, uint64_t len) {

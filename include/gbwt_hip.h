@@ -676,6 +676,50 @@ typedef struct {
     double read_ms, upload_ms, metadata_ms;
 } gbwt_hip_gfa_info;
 gbwt_hip_status gbwt_hip_last_gfa_info(const gbwt_hip_index *index, gbwt_hip_gfa_info *out);
+/* ---- construction from GFA with a node-to-segment translation: segment names of any kind, long segments chopped --------------------------------
+ * The calls above with options.  opts == NULL or {0, GBWT_HIP_GFA_TRANSLATE_NEVER} IS the call above, byte for byte and message for message.
+ * NEVER with max_node_length > 0, an unknown `translate` or a nonzero `reserved`: GBWT_HIP_BAD_ARGUMENT before the device is touched.
+ * AUTO translates iff the name of an S-line (with its three fields) is not a node id under the rule above, or max_node_length > 0 and a
+ * sequence is longer; over a text that needs neither it gives the handle NEVER gives (translated == 0).  A text without S-lines, or one
+ * whose paths visit nothing, has no nodes and gets no translation under any option.
+ *
+ * A translated build (what gfa2gbwt --max-node makes; pinned by tests/golden/translation.gbz):
+ *   Segments are ALL S-lines in file order.  Segment k with a sequence of L bytes owns max(1, ceil(L / max_node_length)) consecutive node
+ *     ids (one if max_node_length == 0); the first segment starts at node 1.  The mapping has a one at the first node of every segment
+ *     and its universe is the number of nodes + 1.  Every node but the last of its segment carries exactly max_node_length bytes.
+ *   A segment that no path visits keeps its node range; its stored name is empty and its nodes have neither labels nor records.
+ *   A name is any 1 .. 255 bytes without tab or newline.  An empty name: INVALID_DATA; a longer one: UNSUPPORTED; a second S-line of a
+ *     name: INVALID_DATA on the LATER line.
+ *   P steps are split at ','; a token is a name followed by one byte '+' or '-' (the name may hold those bytes).  A W walk is split at
+ *     '>' and '<'.  An empty token, a token without its orientation, a trailing ',' or a walk that does not start with a mark:
+ *     INVALID_DATA.  A name without an S-line: INVALID_DATA.  The empty field and "*" are no steps, as above.
+ *   A forward step on segment k becomes its nodes ascending, each forward; a reverse step its nodes descending, each reverse.
+ *   Path order, metadata, RS:Z:, L-lines, ignored lines and the rule of the first offending line are those above.  More than 2^31 - 1
+ *     nodes: UNSUPPORTED; the visits counted against the widths of the construction are the NODES of the steps.
+ *   The handle has stats.has_translation == 1 and the dense labels of a loaded translated GBZ (one per node 1 .. nodes);
+ *   gbwt_hip_save writes the translation, and every segment or link query and gbwt_hip_write_gfa answer as for a loaded file.
+ *   gbwt_hip_gfa_info.steps counts the steps of the text, gbwt_hip_build_info.visits the nodes they became (twice: bidirectional). */
+#define GBWT_HIP_GFA_TRANSLATE_NEVER  0   /* the rules of gbwt_hip_build_from_gfa */
+#define GBWT_HIP_GFA_TRANSLATE_AUTO   1   /* translate iff a name is not a node id under those rules, or a sequence is longer than max_node_length */
+#define GBWT_HIP_GFA_TRANSLATE_ALWAYS 2
+typedef struct {
+    uint32_t max_node_length;   /* 0: never chop; gfa2gbwt's default is 1024 */
+    uint32_t translate;
+    uint64_t reserved[2];       /* must be 0 */
+} gbwt_hip_gfa_options;
+gbwt_hip_status gbwt_hip_build_from_gfa_opts(const char *path, const gbwt_hip_gfa_options *opts, int device, uint32_t flags, gbwt_hip_index **out);
+gbwt_hip_status gbwt_hip_build_from_gfa_text_opts(const char *text, uint64_t len, const gbwt_hip_gfa_options *opts, int device, uint32_t flags, gbwt_hip_index **out);
+/* The translation behind a handle made from GFA; all zeros for every other handle, and all but `segments` for an untranslated build.
+ * nodes: all node ids, visited or not; chopped_segments: those with more than one node; name_bytes: the stored names (of the visited
+ * segments); table_bytes: the name table in HBM (positions, lengths, sorted hashes, ranks, buckets); names_ms: hashing, sort, duplicate
+ * check and buckets; expand_ms: steps to nodes.  Both are HIP events and lie inside gbwt_hip_gfa_info.steps_ms. */
+typedef struct {
+    uint64_t translated, segments, nodes, chopped_segments, unvisited_segments, name_bytes, table_bytes;
+    float names_ms, expand_ms;
+    float reserved[2];
+} gbwt_hip_gfa_translation_info;
+gbwt_hip_status gbwt_hip_last_gfa_translation_info(const gbwt_hip_index *index, gbwt_hip_gfa_translation_info *out);
+
 /* The counts of a GFA file without a device and without the checks of a construction (only a '\r' is refused): bytes .. label_bytes and
  * tile_bytes are filled, steps = the orientation marks of the step fields. */
 gbwt_hip_status gbwt_hip_parse_gfa(const char *path, gbwt_hip_gfa_info *out);

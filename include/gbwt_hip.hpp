@@ -354,6 +354,22 @@ public:
         check(gbwt_hip_build_from_gfa_text(text, len, device, flags, &h));
         return GBZ(h);
     }
+    // ... with a node-to-segment translation (gbwt_hip.h, gbwt_hip_gfa_options): segment names of any kind, segments chopped to max_node_length
+    static GBZ from_gfa(const std::string &path, const gbwt_hip_gfa_options &options, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_build_from_gfa_opts(path.c_str(), &options, device, flags, &h));
+        return GBZ(h);
+    }
+    static GBZ from_gfa_text(const char *text, uint64_t len, const gbwt_hip_gfa_options &options, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_build_from_gfa_text_opts(text, len, &options, device, flags, &h));
+        return GBZ(h);
+    }
+    gbwt_hip_gfa_translation_info last_gfa_translation_info() const {
+        gbwt_hip_gfa_translation_info info{};
+        check(gbwt_hip_last_gfa_translation_info(index_.get(), &info));
+        return info;
+    }
     gbwt_hip_gfa_info last_gfa_info() const {
         gbwt_hip_gfa_info info{};
         check(gbwt_hip_last_gfa_info(index_.get(), &info));
