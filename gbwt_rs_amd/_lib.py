@@ -131,6 +131,20 @@ class GfaTranslationInfo(C.Structure):
                [("names_ms", C.c_float), ("expand_ms", C.c_float), ("reserved", C.c_float * 2)]
 
 
+MERGE_AUTO, MERGE_REBUILD, MERGE_INSERT = 0, 1, 2     # gbwt_hip_merge_options.algorithm
+
+
+class MergeOptions(C.Structure):
+    _fields_ = [("algorithm", C.c_uint32), ("reserved32", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+class MergeInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("visits", "sequences", "records", "data_bytes", "peak_scratch_bytes", "walked_sequences", "walked_steps")] + \
+               [(name, C.c_uint32) for name in ("algorithm_used", "walked_input", "merged", "rounds")] + \
+               [(name, C.c_float) for name in ("walk_ms", "decode_ms", "interleave_ms", "edges_ms", "encode_ms")] + \
+               [("metadata_ms", C.c_double), ("open_ms", C.c_double)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -224,6 +238,8 @@ SIGNATURES = {
     "gbwt_hip_build_from_gfa_text_opts": (_int, [_p, _u64, C.POINTER(GfaOptions), _int, C.c_uint32, C.POINTER(_p)]),
     "gbwt_hip_last_gfa_translation_info": (_int, [_p, C.POINTER(GfaTranslationInfo)]),
     "gbwt_hip_parse_gfa": (_int, [C.c_char_p, C.POINTER(GfaInfo)]),
+    "gbwt_hip_merge": (_int, [_p, _p, C.POINTER(MergeOptions), C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_last_merge_info": (_int, [_p, C.POINTER(MergeInfo)]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_copy_path": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64)]),

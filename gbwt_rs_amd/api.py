@@ -161,6 +161,38 @@ class GBWT:
         check(_lib.lib().gbwt_hip_build_from_rows_device(paths_struct.d_offsets, paths_struct.d_nodes, n, int(bool(bidirectional)), device, flags, C.byref(h)))
         return cls(h, device=device)
 
+    @classmethod
+    def merge(cls, a, b=None, algorithm=None, device=None, flags=_lib.OPEN_ALL):
+        """The index of a's sequences followed by b's, merged on the device (gbwt_hip_merge): what from_paths gives for the paths of a, then
+        those of b, with the metadata, tags and -- for two GBZ -- node labels of both.  algorithm: None (the library chooses: the
+        rebuild where both inputs are open for extraction, else the insertion) or _lib.MERGE_AUTO | MERGE_REBUILD | MERGE_INSERT.  a may be a list of handles (b None): more than two fold left.  The inputs are
+        only read.  device: None, or the device the inputs are on."""
+        handles = list(a) if b is None else [a, b]
+        if len(handles) < 2:
+            raise ValueError("merge takes two handles, or a list of at least two")
+        for x in handles:
+            if not isinstance(x, GBWT) or not getattr(x, "_h", None):
+                raise TypeError("merge takes open GBWT / GBZ handles")
+            if device is not None and x._device != device:
+                raise ValueError(f"a handle is on device {x._device}, not on {device}")
+        opts = None if algorithm is None else _lib.MergeOptions(int(algorithm), 0)
+        result = None
+        for k, nxt in enumerate(handles[1:]):
+            left = handles[0] if result is None else result
+            h = C.c_void_p()
+            check(_lib.lib().gbwt_hip_merge(left._h, nxt._h, C.byref(opts) if opts is not None else None, flags if k == len(handles) - 2 else _lib.OPEN_ALL, C.byref(h)))
+            merged = cls(h, device=left._device)
+            if result is not None:
+                result.close()
+            result = merged
+        return result
+
+    def last_merge_info(self):
+        """The merge behind the handle (gbwt_hip_last_merge_info): a dict; all zeros for a handle that was not merged."""
+        m = _lib.MergeInfo()
+        check(self._L.gbwt_hip_last_merge_info(self._h, C.byref(m)))
+        return {name: getattr(m, name) for name, _ in _lib.MergeInfo._fields_}
+
     def records(self):
         """(data u8[], starts u64[records]) of the handle: its record stream and dense record starts (gbwt_hip_records)."""
         data_len, records = C.c_uint64(0), C.c_uint64(0)

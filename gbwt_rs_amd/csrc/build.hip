@@ -38,34 +38,8 @@ __device__ __forceinline__ uint64_t lower_bound(const T *a, uint64_t n, T x) {
     return lo;
 }
 
-// HBM of the construction, counted: what it holds now and the most it ever held
-struct Scratch {
-    size_t now = 0, peak = 0;
-};
-struct Buf {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    Scratch *owner = nullptr;
-    Buf() = default;
-    Buf(Scratch &sc, size_t need) { alloc(sc, need); }
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-    void alloc(Scratch &sc, size_t need) {
-        release();
-        const size_t want = std::max<size_t>(need, 256);
-        HIP_CHECK(hipMalloc(&ptr, want));
-        bytes = want; owner = &sc;
-        sc.now += want; sc.peak = std::max(sc.peak, sc.now);
-    }
-    void release() noexcept {
-        if (!ptr) return;
-        (void)hipFree(ptr);
-        owner->now -= bytes;
-        ptr = nullptr; bytes = 0;
-    }
-    template <class T> T *as() const { return static_cast<T *>(ptr); }
-};
+using Scratch = BuildScratch;
+using Buf = BuildBuf;
 
 // ---- 1. expand ---------------------------------------------------------------------------------------------------------------------
 // Slot t: the path that owns it by bisection over first(p) = (off[p] + p) << bidir (a path owns one start and its visits, twice with
@@ -297,6 +271,91 @@ void build_node_range(const uint32_t *d_nodes, uint64_t n, uint32_t &min_node, u
     min_node = both[0]; max_node = both[1];
 }
 
+// From the sorted slots as record bodies -- rec[i] the node of position i's record (0: the endmarker's), succ[i] its successor -- to the
+// record stream on the host: run heads, edge lists, offsets (the caller's: BodyOffsets), sizes, scans, bytes.  The construction and the
+// merge (merge.hip) both enter here.  rec and succ are given back on the way, temp (any size) is the scratch of the library calls; `begin` is an event the caller has recorded on s.
+void encode_sorted_bodies(BuildBuf &rec, BuildBuf &succ, uint64_t slots, uint64_t records, uint64_t alphabet_offset, const BodyOffsets &offsets, BuildScratch &sc, BuildBuf &temp,
+                          BuildOutput &out, hipEvent_t begin, hipStream_t s) {
+    Events ev;
+    Buf head(sc, slots * sizeof(uint32_t)), count(sc, sizeof(uint64_t));
+    uint64_t runs = 0;
+    {
+        Buf flag(sc, slots);
+        k_build_run_flags<<<blocks_for(slots), THREADS, 0, s>>>(rec.as<uint32_t>(), succ.as<uint32_t>(), slots, flag.as<uint8_t>());
+        hipcub::CountingInputIterator<uint32_t> positions(0);
+        size_t bytes = 0;
+        HIP_CHECK(hipcub::DeviceSelect::Flagged(nullptr, bytes, positions, flag.as<uint8_t>(), head.as<uint32_t>(), count.as<uint64_t>(), static_cast<int64_t>(slots), s));
+        if (bytes > temp.bytes) temp.alloc(sc, bytes);
+        HIP_CHECK(hipcub::DeviceSelect::Flagged(temp.ptr, bytes, positions, flag.as<uint8_t>(), head.as<uint32_t>(), count.as<uint64_t>(), static_cast<int64_t>(slots), s));
+        HIP_CHECK(hipGetLastError());
+        runs = read_value(count.as<uint64_t>(), s);
+    }
+
+    // 4. the edge lists: the distinct (record, successor) pairs of the run heads, sorted
+    Buf run_key(sc, runs * sizeof(uint64_t)), edge(sc, runs * sizeof(uint64_t));
+    uint64_t edges = 0;
+    {
+        Buf key_sorted(sc, runs * sizeof(uint64_t));
+        k_build_run_keys<<<blocks_for(runs), THREADS, 0, s>>>(head.as<uint32_t>(), runs, rec.as<uint32_t>(), succ.as<uint32_t>(), run_key.as<uint64_t>());
+        size_t sort_bytes = 0, unique_bytes = 0;
+        HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, run_key.as<uint64_t>(), key_sorted.as<uint64_t>(), runs, 0, 64, s));
+        HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, unique_bytes, key_sorted.as<uint64_t>(), edge.as<uint64_t>(), count.as<uint64_t>(), static_cast<int64_t>(runs), s));
+        if (std::max(sort_bytes, unique_bytes) > temp.bytes) temp.alloc(sc, std::max(sort_bytes, unique_bytes));
+        HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(temp.ptr, sort_bytes, run_key.as<uint64_t>(), key_sorted.as<uint64_t>(), runs, 0, 64, s));
+        HIP_CHECK(hipcub::DeviceSelect::Unique(temp.ptr, unique_bytes, key_sorted.as<uint64_t>(), edge.as<uint64_t>(), count.as<uint64_t>(), static_cast<int64_t>(runs), s));
+        HIP_CHECK(hipGetLastError());
+        edges = read_value(count.as<uint64_t>(), s);
+    }
+    succ.release();
+    Buf edge_first(sc, (records + 1) * sizeof(uint32_t)), run_first(sc, (records + 1) * sizeof(uint32_t)), visit_first(sc, (records + 1) * sizeof(uint32_t));
+    k_build_record_bounds<<<blocks_for(records + 1), THREADS, 0, s>>>(edge.as<uint64_t>(), edges, run_key.as<uint64_t>(), runs, rec.as<uint32_t>(), slots, records, alphabet_offset,
+                                                                      edge_first.as<uint32_t>(), run_first.as<uint32_t>(), visit_first.as<uint32_t>());
+
+    // 5. the edge offsets
+    Buf edge_offset(sc, edges * sizeof(uint32_t));
+    HIP_CHECK(hipMemsetAsync(edge_offset.ptr, 0, edge_offset.bytes, s));
+    offsets.launch(BodyEdges{edge.as<uint64_t>(), edges, edge_first.as<uint32_t>(), visit_first.as<uint32_t>(), edge_offset.as<uint32_t>()});
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[0], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    rec.release(); visit_first.release();
+    if (offsets.release) offsets.release();
+
+    // 6. sizes, scans, starts, bytes
+    Buf run_rank(sc, runs * sizeof(uint32_t)), sizes(sc, (std::max({edges, runs, records}) + 1) * sizeof(uint64_t));
+    Buf edge_at(sc, (edges + 1) * sizeof(uint64_t)), run_at(sc, (runs + 1) * sizeof(uint64_t)), hdr_at(sc, (records + 1) * sizeof(uint64_t));
+    Buf starts(sc, (records + 1) * sizeof(uint64_t));
+    k_build_edge_sizes<<<blocks_for(edges + 1), THREADS, 0, s>>>(edge.as<uint64_t>(), edges, edge_first.as<uint32_t>(), edge_offset.as<uint32_t>(), alphabet_offset, sizes.as<uint64_t>());
+    exclusive_sum(sizes.as<uint64_t>(), edge_at.as<uint64_t>(), edges + 1, sc, temp, s);
+    k_build_run_sizes<<<blocks_for(runs + 1), THREADS, 0, s>>>(run_key.as<uint64_t>(), head.as<uint32_t>(), runs, slots, edge.as<uint64_t>(), edge_first.as<uint32_t>(), alphabet_offset,
+                                                               run_rank.as<uint32_t>(), sizes.as<uint64_t>());
+    exclusive_sum(sizes.as<uint64_t>(), run_at.as<uint64_t>(), runs + 1, sc, temp, s);
+    k_build_header_sizes<<<blocks_for(records + 1), THREADS, 0, s>>>(edge_first.as<uint32_t>(), records, sizes.as<uint64_t>());
+    exclusive_sum(sizes.as<uint64_t>(), hdr_at.as<uint64_t>(), records + 1, sc, temp, s);
+    k_build_starts<<<blocks_for(records + 1), THREADS, 0, s>>>(hdr_at.as<uint64_t>(), edge_at.as<uint64_t>(), run_at.as<uint64_t>(), edge_first.as<uint32_t>(), run_first.as<uint32_t>(),
+                                                               records, starts.as<uint64_t>());
+    HIP_CHECK(hipGetLastError());
+    const uint64_t data_bytes = read_value(starts.as<uint64_t>() + records, s);
+    Buf data(sc, data_bytes);
+    k_build_fill_headers<<<blocks_for(records), THREADS, 0, s>>>(starts.as<uint64_t>(), edge_first.as<uint32_t>(), records, data.as<uint8_t>());
+    k_build_fill_edges<<<blocks_for(edges), THREADS, 0, s>>>(edge.as<uint64_t>(), edges, edge_first.as<uint32_t>(), run_first.as<uint32_t>(), edge_offset.as<uint32_t>(),
+                                                             hdr_at.as<uint64_t>(), edge_at.as<uint64_t>(), run_at.as<uint64_t>(), alphabet_offset, data.as<uint8_t>());
+    k_build_fill_runs<<<blocks_for(runs), THREADS, 0, s>>>(run_key.as<uint64_t>(), head.as<uint32_t>(), run_rank.as<uint32_t>(), runs, slots, edge_first.as<uint32_t>(),
+                                                           hdr_at.as<uint64_t>(), edge_at.as<uint64_t>(), run_at.as<uint64_t>(), alphabet_offset, data.as<uint8_t>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[1], s));
+
+    // 7. to the host
+    out.data.resize(data_bytes);
+    out.starts.resize(records);
+    HIP_CHECK(hipMemcpyAsync(out.data.data(), data.ptr, data_bytes, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(out.starts.data(), starts.ptr, records * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventElapsedTime(&out.edges_ms, begin, ev.e[0]));
+    HIP_CHECK(hipEventElapsedTime(&out.encode_ms, ev.e[0], ev.e[1]));
+}
+
 void build_records_on_device(const BuildInput &in, BuildOutput &out, hipStream_t s) {
     const uint64_t sequences = in.bidirectional ? 2 * in.n_paths : in.n_paths;
     const uint64_t visits = in.bidirectional ? 2 * in.path_visits : in.path_visits;
@@ -356,85 +415,17 @@ void build_records_on_device(const BuildInput &in, BuildOutput &out, hipStream_t
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));
     node.release(); first_slot.release(); sorted.release();
-    Buf head(sc, slots * sizeof(uint32_t)), count(sc, sizeof(uint64_t));
-    uint64_t runs = 0;
-    {
-        Buf flag(sc, slots);
-        k_build_run_flags<<<blocks_for(slots), THREADS, 0, s>>>(rec.as<uint32_t>(), succ.as<uint32_t>(), slots, flag.as<uint8_t>());
-        hipcub::CountingInputIterator<uint32_t> positions(0);
-        size_t bytes = 0;
-        HIP_CHECK(hipcub::DeviceSelect::Flagged(nullptr, bytes, positions, flag.as<uint8_t>(), head.as<uint32_t>(), count.as<uint64_t>(), static_cast<int64_t>(slots), s));
-        if (bytes > temp.bytes) temp.alloc(sc, bytes);
-        HIP_CHECK(hipcub::DeviceSelect::Flagged(temp.ptr, bytes, positions, flag.as<uint8_t>(), head.as<uint32_t>(), count.as<uint64_t>(), static_cast<int64_t>(slots), s));
-        HIP_CHECK(hipGetLastError());
-        runs = read_value(count.as<uint64_t>(), s);
-    }
 
-    // 4. the edge lists: the distinct (record, successor) pairs of the run heads, sorted
-    Buf run_key(sc, runs * sizeof(uint64_t)), edge(sc, runs * sizeof(uint64_t));
-    uint64_t edges = 0;
-    {
-        Buf key_sorted(sc, runs * sizeof(uint64_t));
-        k_build_run_keys<<<blocks_for(runs), THREADS, 0, s>>>(head.as<uint32_t>(), runs, rec.as<uint32_t>(), succ.as<uint32_t>(), run_key.as<uint64_t>());
-        size_t sort_bytes = 0, unique_bytes = 0;
-        HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, run_key.as<uint64_t>(), key_sorted.as<uint64_t>(), runs, 0, 64, s));
-        HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, unique_bytes, key_sorted.as<uint64_t>(), edge.as<uint64_t>(), count.as<uint64_t>(), static_cast<int64_t>(runs), s));
-        if (std::max(sort_bytes, unique_bytes) > temp.bytes) temp.alloc(sc, std::max(sort_bytes, unique_bytes));
-        HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(temp.ptr, sort_bytes, run_key.as<uint64_t>(), key_sorted.as<uint64_t>(), runs, 0, 64, s));
-        HIP_CHECK(hipcub::DeviceSelect::Unique(temp.ptr, unique_bytes, key_sorted.as<uint64_t>(), edge.as<uint64_t>(), count.as<uint64_t>(), static_cast<int64_t>(runs), s));
-        HIP_CHECK(hipGetLastError());
-        edges = read_value(count.as<uint64_t>(), s);
-    }
-    succ.release();
-    Buf edge_first(sc, (records + 1) * sizeof(uint32_t)), run_first(sc, (records + 1) * sizeof(uint32_t)), visit_first(sc, (records + 1) * sizeof(uint32_t));
-    k_build_record_bounds<<<blocks_for(records + 1), THREADS, 0, s>>>(edge.as<uint64_t>(), edges, run_key.as<uint64_t>(), runs, rec.as<uint32_t>(), slots, records, alphabet_offset,
-                                                                      edge_first.as<uint32_t>(), run_first.as<uint32_t>(), visit_first.as<uint32_t>());
-
-    // 5. the edge offsets
-    Buf edge_offset(sc, edges * sizeof(uint32_t));
-    HIP_CHECK(hipMemsetAsync(edge_offset.ptr, 0, edge_offset.bytes, s));
-    if (visits) k_build_edge_offsets<<<blocks_for(visits), THREADS, 0, s>>>(rec.as<uint32_t>(), pred.as<uint32_t>(), sequences, slots, edge.as<uint64_t>(), edge_first.as<uint32_t>(),
-                                                                            visit_first.as<uint32_t>(), alphabet_offset, edge_offset.as<uint32_t>());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[3], s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    rec.release(); pred.release(); visit_first.release();
-
-    // 6. sizes, scans, starts, bytes
-    Buf run_rank(sc, runs * sizeof(uint32_t)), sizes(sc, (std::max({edges, runs, records}) + 1) * sizeof(uint64_t));
-    Buf edge_at(sc, (edges + 1) * sizeof(uint64_t)), run_at(sc, (runs + 1) * sizeof(uint64_t)), hdr_at(sc, (records + 1) * sizeof(uint64_t));
-    Buf starts(sc, (records + 1) * sizeof(uint64_t));
-    k_build_edge_sizes<<<blocks_for(edges + 1), THREADS, 0, s>>>(edge.as<uint64_t>(), edges, edge_first.as<uint32_t>(), edge_offset.as<uint32_t>(), alphabet_offset, sizes.as<uint64_t>());
-    exclusive_sum(sizes.as<uint64_t>(), edge_at.as<uint64_t>(), edges + 1, sc, temp, s);
-    k_build_run_sizes<<<blocks_for(runs + 1), THREADS, 0, s>>>(run_key.as<uint64_t>(), head.as<uint32_t>(), runs, slots, edge.as<uint64_t>(), edge_first.as<uint32_t>(), alphabet_offset,
-                                                               run_rank.as<uint32_t>(), sizes.as<uint64_t>());
-    exclusive_sum(sizes.as<uint64_t>(), run_at.as<uint64_t>(), runs + 1, sc, temp, s);
-    k_build_header_sizes<<<blocks_for(records + 1), THREADS, 0, s>>>(edge_first.as<uint32_t>(), records, sizes.as<uint64_t>());
-    exclusive_sum(sizes.as<uint64_t>(), hdr_at.as<uint64_t>(), records + 1, sc, temp, s);
-    k_build_starts<<<blocks_for(records + 1), THREADS, 0, s>>>(hdr_at.as<uint64_t>(), edge_at.as<uint64_t>(), run_at.as<uint64_t>(), edge_first.as<uint32_t>(), run_first.as<uint32_t>(),
-                                                               records, starts.as<uint64_t>());
-    HIP_CHECK(hipGetLastError());
-    const uint64_t data_bytes = read_value(starts.as<uint64_t>() + records, s);
-    Buf data(sc, data_bytes);
-    k_build_fill_headers<<<blocks_for(records), THREADS, 0, s>>>(starts.as<uint64_t>(), edge_first.as<uint32_t>(), records, data.as<uint8_t>());
-    k_build_fill_edges<<<blocks_for(edges), THREADS, 0, s>>>(edge.as<uint64_t>(), edges, edge_first.as<uint32_t>(), run_first.as<uint32_t>(), edge_offset.as<uint32_t>(),
-                                                             hdr_at.as<uint64_t>(), edge_at.as<uint64_t>(), run_at.as<uint64_t>(), alphabet_offset, data.as<uint8_t>());
-    k_build_fill_runs<<<blocks_for(runs), THREADS, 0, s>>>(run_key.as<uint64_t>(), head.as<uint32_t>(), run_rank.as<uint32_t>(), runs, slots, edge_first.as<uint32_t>(),
-                                                           hdr_at.as<uint64_t>(), edge_at.as<uint64_t>(), run_at.as<uint64_t>(), alphabet_offset, data.as<uint8_t>());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[4], s));
-
-    // 7. to the host
-    out.data.resize(data_bytes);
-    out.starts.resize(records);
-    HIP_CHECK(hipMemcpyAsync(out.data.data(), data.ptr, data_bytes, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(out.starts.data(), starts.ptr, records * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipGetLastError());
+    // 4. - 7. from the sorted bodies to the bytes; the offset of edge v -> w is where the block of v starts in w's record
+    BodyOffsets offsets;
+    offsets.launch = [&](const BodyEdges &e) {
+        if (visits) k_build_edge_offsets<<<blocks_for(visits), THREADS, 0, s>>>(rec.as<uint32_t>(), pred.as<uint32_t>(), sequences, slots, e.edge, e.edge_first, e.visit_first, alphabet_offset,
+                                                                                e.edge_offset);
+    };
+    offsets.release = [&] { pred.release(); };
+    encode_sorted_bodies(rec, succ, slots, records, alphabet_offset, offsets, sc, temp, out, ev.e[2], s);
     HIP_CHECK(hipEventElapsedTime(&out.expand_ms, ev.e[0], ev.e[1]));
     HIP_CHECK(hipEventElapsedTime(&out.rank_ms, ev.e[1], ev.e[2]));
-    HIP_CHECK(hipEventElapsedTime(&out.edges_ms, ev.e[2], ev.e[3]));
-    HIP_CHECK(hipEventElapsedTime(&out.encode_ms, ev.e[3], ev.e[4]));
     out.peak_scratch = sc.peak;
 }
 

@@ -724,6 +724,53 @@ gbwt_hip_status gbwt_hip_last_gfa_translation_info(const gbwt_hip_index *index, 
  * tile_bytes are filled, steps = the orientation marks of the step fields. */
 gbwt_hip_status gbwt_hip_parse_gfa(const char *path, gbwt_hip_gfa_info *out);
 
+/* ---- merging: one index from two ---------------------------------------------------------------------------------------------------------
+ * The index of the sequences of `a` in order, then the sequences of `b` in order: byte for byte what gbwt_hip_build_from_paths returns for
+ * that input -- record stream, record starts, sequences, size, alphabet_offset, alphabet_size, bidirectional.  The inputs are taken as
+ * SEQUENCES: in bidirectional inputs the pairs 2p / 2p + 1 stay as they are, path p of b becomes path paths(a) + p.  The result is opened
+ * with `flags` as by gbwt_hip_open_records_flags; a and b are only read and stay usable.  The alphabet of the result is the union of the
+ * alphabets the headers of the inputs state (an input without visits has none).
+ *
+ * GBWT_HIP_BAD_ARGUMENT, before the device is touched: a null a, b or out; bad flags; an unknown algorithm; a nonzero reserved field;
+ * handles on different devices; one input bidirectional and the other not; one input a GBZ and the other a bare GBWT; _INSERT for
+ * unidirectional inputs.  *out is cleared by a call that fails.  Widths: those of the construction over the merged set (visits +
+ * sequences at most 2^32 - 1, fewer than 2^30 records), else GBWT_HIP_UNSUPPORTED in its wording.
+ *
+ * Algorithms.  INSERT (bidirectional inputs only): the input with fewer visits (b on a tie) is walked, one lane per
+ * sequence, through itself and -- with the successor forced -- through the other input, which gives every visit its rank among the
+ * other's; the record bodies of both are interleaved by those ranks and encoded by the construction's own phases.  Nothing is ranked or
+ * sorted by prefix.  It reads the record bytes, the record starts and the endmarker of the inputs, which every handle keeps, whatever
+ * it was opened for.  REBUILD: gbwt_hip_extract_device of all sequences of both (the inputs must be open for extraction), the rows
+ * behind one another, and the construction over them.  AUTO: REBUILD where both inputs are open for extraction or unidirectional, else
+ * INSERT.  (The walk of INSERT is one dependent chain per sequence of the smaller input; on 100 000 sites x 1 000 haplotypes REBUILD took
+ * 0.66 s against 2.36 s for 500 + 500 haplotypes and 0.63 s against 1.72 s for 990 + 10: profiles/r16_merge_halves.json, _insert.json.)
+ *
+ * Metadata (assembled on the host).  Neither input has it: none.  Exactly one has it, or one lacks path, sample or contig names:
+ * GBWT_HIP_UNSUPPORTED.  Else sample names are a's in order, then those of b that a lacks, in b's order; contig names likewise; path
+ * names are a's, then b's with sample and contig ids remapped.  A path of b whose four fields equal those of an earlier path:
+ * GBWT_HIP_INVALID_DATA, naming the path id in b.  haplotype_count = distinct (sample, phase) over the merged path names.  Tags of the
+ * GBWT and of the GBZ: a's, then the keys only b has; reference_samples is a's names, then those of b's that are not among them, joined
+ * by one space (absent when both lack it).  Document-array samples are dropped.
+ * Graph (two GBZ): the union of the node labels; a node labelled differently in the two: GBWT_HIP_INVALID_DATA, naming the node; an
+ * input with a node-to-segment translation: GBWT_HIP_UNSUPPORTED.  The result answers every call as a loaded file does. */
+#define GBWT_HIP_MERGE_AUTO    0   /* rebuild where it can run (both inputs open for extraction, or unidirectional), else insertion */
+#define GBWT_HIP_MERGE_REBUILD 1   /* extract both to rows in HBM, concatenate, run the construction */
+#define GBWT_HIP_MERGE_INSERT  2   /* insertion, asked for by name */
+typedef struct { uint32_t algorithm; uint32_t reserved32; uint64_t reserved[2]; } gbwt_hip_merge_options;   /* reserved: 0; NULL: AUTO */
+gbwt_hip_status gbwt_hip_merge(const gbwt_hip_index *a, const gbwt_hip_index *b, const gbwt_hip_merge_options *opts,
+                               uint32_t flags, gbwt_hip_index **out);
+/* The merge behind a handle; all zeros for a handle that was not merged.  visits .. data_bytes: of the result; peak_scratch_bytes: the
+ * most HBM the merge held at once (without the inputs); walked_input: 0 = a, 1 = b, with its sequences and visits (INSERT only);
+ * algorithm_used: _INSERT or _REBUILD; rounds: the doubling rounds of a REBUILD; walk .. encode: HIP events around the phases (a REBUILD
+ * fills edges and encode only); metadata / open: host clock. */
+typedef struct {
+    uint64_t visits, sequences, records, data_bytes, peak_scratch_bytes, walked_sequences, walked_steps;
+    uint32_t algorithm_used, walked_input /* 0 = a, 1 = b */, merged, rounds;
+    float walk_ms, decode_ms, interleave_ms, edges_ms, encode_ms;
+    double metadata_ms, open_ms;
+} gbwt_hip_merge_info;
+gbwt_hip_status gbwt_hip_last_merge_info(const gbwt_hip_index *index, gbwt_hip_merge_info *out);
+
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex
  * (src/bin/gbunzip.rs:27, 421-434).  Sharded over GPUs -- one process per GPU, the index replicated, path p on rank p mod world

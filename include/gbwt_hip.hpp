@@ -107,6 +107,13 @@ public:
         check(gbwt_hip_last_build_info(index_.get(), &info));
         return info;
     }
+    // ---- merging on the device (gbwt_hip.h, "merging"): the index of a's sequences followed by b's; a and b are only read
+    static GBWT merge(const GBWT &a, const GBWT &b, uint32_t algorithm = GBWT_HIP_MERGE_AUTO, uint32_t flags = GBWT_HIP_OPEN_ALL) { return GBWT(merged_handle(a, b, algorithm, flags)); }
+    gbwt_hip_merge_info last_merge_info() const {
+        gbwt_hip_merge_info info{};
+        check(gbwt_hip_last_merge_info(index_.get(), &info));
+        return info;
+    }
     GBWT clone_workspace() const { GBWT other(*this, 0); return other; }
 
     // ---- statistics, src/gbwt.rs:108-182
@@ -297,6 +304,12 @@ protected:
         for (uint64_t e : r.edges) out.emplace_back(e >> 1, (e & 1) ? Orientation::Reverse : Orientation::Forward);
         return out;
     }
+    static gbwt_hip_index *merged_handle(const GBWT &a, const GBWT &b, uint32_t algorithm, uint32_t flags) {
+        const gbwt_hip_merge_options options{algorithm, 0, {0, 0}};
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_merge(a.index_.get(), b.index_.get(), &options, flags, &h));
+        return h;
+    }
     GBWT(const GBWT &other, int) : index_(other.index_), stats_(other.stats_) { make_workspace(); }
     explicit GBWT(gbwt_hip_index *built) { index_.reset(built, gbwt_hip_close); init(); }
     void init() {
@@ -343,6 +356,8 @@ private:
     explicit GBZ(gbwt_hip_index *built) : GBWT(built) {}
 
 public:
+    // two GBZ: records, metadata, tags and the union of the node labels (gbwt_hip.h, "merging")
+    static GBZ merge(const GBZ &a, const GBZ &b, uint32_t algorithm = GBWT_HIP_MERGE_AUTO, uint32_t flags = GBWT_HIP_OPEN_ALL) { return GBZ(merged_handle(a, b, algorithm, flags)); }
     // ---- construction from GFA on the device (gbwt_hip.h, "construction from GFA"): a GBZ like a loaded one, from a file or a text in memory
     static GBZ from_gfa(const std::string &path, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
         gbwt_hip_index *h = nullptr;
@@ -561,6 +576,10 @@ private:
         return out;
     }
 };
+
+// merge(a, b): GBWT::merge for two GBWT, GBZ::merge for two GBZ
+template <class Index>
+inline Index merge(const Index &a, const Index &b, uint32_t algorithm = GBWT_HIP_MERGE_AUTO, uint32_t flags = GBWT_HIP_OPEN_ALL) { return Index::merge(a, b, algorithm, flags); }
 
 // The ordered gather of a sharded extraction (one process per GPU; the reference's writer mutex, src/bin/gbunzip.rs:421-434).  Rank 0 makes
 // the id (Comm::unique_id), every rank constructs a Comm from it (collective), and after gbwt_hip_extract_device / _path_lines_device on
