@@ -145,6 +145,20 @@ class MergeInfo(C.Structure):
                [("metadata_ms", C.c_double), ("open_ms", C.c_double)]
 
 
+REMOVE_AUTO, REMOVE_REBUILD, REMOVE_DELETE = 0, 1, 2   # gbwt_hip_remove_options.algorithm
+
+
+class RemoveOptions(C.Structure):
+    _fields_ = [("algorithm", C.c_uint32), ("reserved32", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+class RemoveInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("visits", "sequences", "records", "data_bytes", "peak_scratch_bytes", "removed_sequences", "removed_steps")] + \
+               [(name, C.c_uint32) for name in ("algorithm_used", "removed", "rounds", "reserved32")] + \
+               [(name, C.c_float) for name in ("walk_ms", "decode_ms", "compact_ms", "edges_ms", "encode_ms")] + \
+               [("metadata_ms", C.c_double), ("open_ms", C.c_double)]
+
+
 _p, _u64, _int = C.c_void_p, C.c_uint64, C.c_int
 
 SIGNATURES = {
@@ -240,6 +254,8 @@ SIGNATURES = {
     "gbwt_hip_parse_gfa": (_int, [C.c_char_p, C.POINTER(GfaInfo)]),
     "gbwt_hip_merge": (_int, [_p, _p, C.POINTER(MergeOptions), C.c_uint32, C.POINTER(_p)]),
     "gbwt_hip_last_merge_info": (_int, [_p, C.POINTER(MergeInfo)]),
+    "gbwt_hip_remove_paths": (_int, [_p, _p, _u64, C.POINTER(RemoveOptions), C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_last_remove_info": (_int, [_p, C.POINTER(RemoveInfo)]),
     "gbwt_hip_path_sums": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_path_hashes": (_int, [_p, _p, _p, _u64]),
     "gbwt_hip_copy_path": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64)]),

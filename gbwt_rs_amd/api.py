@@ -193,6 +193,36 @@ class GBWT:
         check(self._L.gbwt_hip_last_merge_info(self._h, C.byref(m)))
         return {name: getattr(m, name) for name, _ in _lib.MergeInfo._fields_}
 
+    def remove_paths(self, path_ids, algorithm=None, flags=_lib.OPEN_ALL):
+        """The index without the paths path_ids, a new handle of the same class (gbwt_hip_remove_paths): what from_paths gives for the kept
+        sequences in their old order, with the metadata, tags and -- for a GBZ -- node labels that still apply.  In a bidirectional index
+        path p is the sequences 2p and 2p + 1.  algorithm: None (the library chooses: the rebuild where the handle is open for
+        extraction, else the deletion) or _lib.REMOVE_AUTO | REMOVE_REBUILD | REMOVE_DELETE.  This handle is only read."""
+        ids = np.ascontiguousarray(np.asarray(path_ids, dtype=np.int64).reshape(-1))
+        if ids.size and int(ids.min()) < 0:
+            raise ValueError("a path id is negative")
+        ids = ids.astype(np.uint64)
+        opts = None if algorithm is None else _lib.RemoveOptions(int(algorithm), 0)
+        h = C.c_void_p()
+        check(self._L.gbwt_hip_remove_paths(self._h, _ptr(ids), ids.size, C.byref(opts) if opts is not None else None, flags, C.byref(h)))
+        return type(self)(h, device=self._device)
+
+    def keep_paths(self, path_ids, algorithm=None, flags=_lib.OPEN_ALL):
+        """The index of the paths path_ids alone, in their old order: remove_paths of the complement."""
+        total = self.sequences() // 2 if self.is_bidirectional() else self.sequences()
+        keep = np.zeros(total, dtype=bool)
+        ids = np.asarray(path_ids, dtype=np.int64).reshape(-1)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= total):
+            raise ValueError(f"a path id is not in [0, {total})")
+        keep[ids] = True
+        return self.remove_paths(np.flatnonzero(~keep), algorithm=algorithm, flags=flags)
+
+    def last_remove_info(self):
+        """The removal behind the handle (gbwt_hip_last_remove_info): a dict; all zeros for a handle that did not come from a removal."""
+        m = _lib.RemoveInfo()
+        check(self._L.gbwt_hip_last_remove_info(self._h, C.byref(m)))
+        return {name: getattr(m, name) for name, _ in _lib.RemoveInfo._fields_}
+
     def records(self):
         """(data u8[], starts u64[records]) of the handle: its record stream and dense record starts (gbwt_hip_records)."""
         data_len, records = C.c_uint64(0), C.c_uint64(0)
@@ -893,6 +923,10 @@ class GBZ(GBWT):
         if isinstance(contig, str):
             return contig.encode()
         raise TypeError("contig must be None, str or bytes")
+
+    def remove_contig(self, name, algorithm=None, flags=_lib.OPEN_ALL):
+        """The GBZ without the paths select_paths(contig=name) gives: the whole component in which a path with that contig name starts."""
+        return self.remove_paths(self.select_paths(contig=name), algorithm=algorithm, flags=flags)
 
     def select_paths(self, contig=None):
         """select_paths of gbz-extract (src/bin/gbz-extract.rs:196-264): every path id for contig=None; otherwise the ascending ids of every path

@@ -17,6 +17,7 @@
 #include "build.hpp"
 #include "build_codec.hpp"
 #include "capi_internal.hpp"
+#include "hip_raii.hpp"
 
 namespace gbwt_hip {
 
@@ -231,14 +232,6 @@ int bits_for(uint64_t values) {                      // bits that hold 0 .. valu
     return b;
 }
 
-struct Events {
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    Events() { for (auto &x : e) HIP_CHECK(hipEventCreate(&x)); }
-    ~Events() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
-    Events(const Events &) = delete;
-    Events &operator=(const Events &) = delete;
-};
-
 // exclusive sum of n u64 (temp grows as needed)
 void exclusive_sum(const uint64_t *in, uint64_t *out, uint64_t n, Scratch &sc, Buf &temp, hipStream_t s) {
     size_t bytes = 0;
@@ -276,7 +269,7 @@ void build_node_range(const uint32_t *d_nodes, uint64_t n, uint32_t &min_node, u
 // merge (merge.hip) both enter here.  rec and succ are given back on the way, temp (any size) is the scratch of the library calls; `begin` is an event the caller has recorded on s.
 void encode_sorted_bodies(BuildBuf &rec, BuildBuf &succ, uint64_t slots, uint64_t records, uint64_t alphabet_offset, const BodyOffsets &offsets, BuildScratch &sc, BuildBuf &temp,
                           BuildOutput &out, hipEvent_t begin, hipStream_t s) {
-    Events ev;
+    EventSet<5> ev;
     Buf head(sc, slots * sizeof(uint32_t)), count(sc, sizeof(uint64_t));
     uint64_t runs = 0;
     {
@@ -363,7 +356,7 @@ void build_records_on_device(const BuildInput &in, BuildOutput &out, hipStream_t
     const uint64_t alphabet_offset = in.min_node - 1, alphabet_size = in.max_node + 1, records = alphabet_size - alphabet_offset;
     out.sequences = sequences; out.visits = visits; out.records = records; out.alphabet_offset = alphabet_offset; out.alphabet_size = alphabet_size;
     Scratch sc;
-    Events ev;
+    EventSet<5> ev;
     Buf temp;
     HIP_CHECK(hipEventRecord(ev.e[0], s));
 

@@ -8,18 +8,11 @@
 #include "build.hpp"
 #include "build_codec.hpp"
 #include "capi_internal.hpp"
+#include "hip_raii.hpp"
 
 using namespace gbwt_hip;
 
 namespace {
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIP_CHECK(hipStreamCreate(&s)); }
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-    Stream(const Stream &) = delete;
-    Stream &operator=(const Stream &) = delete;
-};
 
 gbwt_hip_status check_call(const void *offsets, uint64_t n_paths, int bidirectional, uint32_t flags, gbwt_hip_index **out) {
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");

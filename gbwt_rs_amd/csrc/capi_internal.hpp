@@ -1,4 +1,4 @@
-// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, capi_topology.hip, capi_build.hip, capi_gfa_build.hip, capi_merge.hip, gfa.hip, comm.hip).
+// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, capi_topology.hip, capi_build.hip, capi_gfa_build.hip, capi_merge.hip, capi_remove.hip, gfa.hip, comm.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -385,6 +385,7 @@ struct gbwt_hip_index {
     gbwt_hip_gfa_info gfa_info{};     // the parse behind a handle made from GFA (capi_gfa_build.hip); zeros for every other handle
     gbwt_hip_gfa_translation_info gfa_translation_info{};   // its translation, if it made one
     gbwt_hip_merge_info merge_info{};   // the merge behind the handle (capi_merge.hip); zeros for every other handle
+    gbwt_hip_remove_info remove_info{}; // the removal behind the handle (capi_remove.hip); zeros for every other handle
     uint32_t uniform_len = 0;         // every sequence has this many nodes (0: lengths differ, or unknown): an extraction then knows its offsets without asking the device
     bool orientation_pairs = false;   // verified at open: sequence 2k + 1 is sequence 2k reversed (rows can be filled from both ends)
     gbwt_hip_stats stats{};

@@ -8,28 +8,13 @@
 
 #include "build.hpp"
 #include "capi_internal.hpp"
+#include "hip_raii.hpp"
 #include "merge.hpp"
 #include "merge_meta.hpp"
 
 using namespace gbwt_hip;
 
 namespace {
-
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIP_CHECK(hipStreamCreate(&s)); }
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-    Stream(const Stream &) = delete;
-    Stream &operator=(const Stream &) = delete;
-};
-
-struct Workspace {
-    gbwt_hip_workspace *ws = nullptr;
-    ~Workspace() { if (ws) gbwt_hip_workspace_destroy(ws); }
-};
 
 gbwt_hip_status refusal_status(const MergeRefusal &bad) {
     return fail(bad.kind == MergeRefusal::UNSUPPORTED ? GBWT_HIP_UNSUPPORTED : GBWT_HIP_INVALID_DATA, "merge: " + bad.what);

@@ -1,0 +1,162 @@
+// capi_remove.hip -- GBWT / GBZ path removal over the C ABI (include/gbwt_hip.h, "removal"): the checks of the handle and the path ids, the
+// records by deletion (remove.hip) or by a construction over the extracted rows of the kept sequences (build.hip), the metadata, tags and
+// labels of remove_meta.hpp, and the open behind them.
+#include <chrono>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "build.hpp"
+#include "capi_internal.hpp"
+#include "hip_raii.hpp"
+#include "merge.hpp"
+#include "remove.hpp"
+#include "remove_meta.hpp"
+
+using namespace gbwt_hip;
+
+namespace {
+
+gbwt_hip_status refusal_status(const MergeRefusal &bad) {
+    return fail(bad.kind == MergeRefusal::UNSUPPORTED ? GBWT_HIP_UNSUPPORTED : GBWT_HIP_INVALID_DATA, "remove: " + bad.what);
+}
+
+// REMOVE_REBUILD: the rows of the kept sequences through the construction -- as sequences, so the order is kept exactly
+gbwt_hip_status rebuild(const gbwt_hip_index *ix, const std::vector<uint64_t> &kept, BuildOutput &o, hipStream_t s) {
+    Workspace w;
+    gbwt_hip_paths rows{nullptr, nullptr, 0, 0};
+    gbwt_hip_status st = gbwt_hip_workspace_create(ix, &w.ws);
+    if (st != GBWT_HIP_OK) return st;
+    st = gbwt_hip_extract_device(ix, w.ws, kept.data(), kept.size(), &rows);
+    if (st != GBWT_HIP_OK) return st;
+    HIP_CHECK(hipDeviceSynchronize());                     // (the rows were written on the workspace's stream)
+    if (rows.total == 0) { build_without_visits(kept.size(), o); return GBWT_HIP_OK; }
+    st = check_build_sizes(rows.n, rows.total, 0);         // the widths of the construction over the kept set (known before the call where the input is within them)
+    if (st != GBWT_HIP_OK) return st;
+    uint32_t lo = 0, hi = 0;
+    build_node_range(rows.d_nodes, rows.total, lo, hi, s);
+    st = check_build_range(lo, hi);
+    if (st != GBWT_HIP_OK) return st;
+    build_records_on_device(BuildInput{rows.d_offsets, rows.d_nodes, rows.n, rows.total, false, lo, hi}, o, s);
+    return GBWT_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gbwt_hip_status gbwt_hip_remove_paths(const gbwt_hip_index *index, const uint64_t *path_ids, uint64_t n, const gbwt_hip_remove_options *opts, uint32_t flags, gbwt_hip_index **out) {
+    GBWT_HIP_GUARD_BEGIN
+    if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
+    *out = nullptr;
+    if (!index) return fail(GBWT_HIP_BAD_ARGUMENT, "null index");
+    if (n && !path_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null path ids");
+    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
+    uint32_t algorithm = GBWT_HIP_REMOVE_AUTO;
+    if (opts) {
+        if (opts->algorithm > GBWT_HIP_REMOVE_DELETE) return fail(GBWT_HIP_BAD_ARGUMENT, "options: algorithm is one of GBWT_HIP_REMOVE_AUTO | _REBUILD | _DELETE");
+        if (opts->reserved32 != 0 || opts->reserved[0] != 0 || opts->reserved[1] != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "options: reserved must be 0");
+        algorithm = opts->algorithm;
+    }
+    const HostIndex &hi = index->host;
+    const uint64_t per_path = hi.bidirectional ? 2 : 1, paths = hi.sequences / per_path;
+    std::string what;
+    if (!remove_check_ids(path_ids, n, paths, what)) return fail(GBWT_HIP_BAD_ARGUMENT, what);
+    const bool extractable = (index->caps & GBWT_HIP_OPEN_EXTRACT) != 0;
+    if (algorithm == GBWT_HIP_REMOVE_REBUILD && !extractable) return fail(GBWT_HIP_BAD_ARGUMENT, "options: GBWT_HIP_REMOVE_REBUILD needs a handle that is open for extraction");
+    // AUTO: the rebuild, which was measured faster on both shapes of tools/remove_bench.py, where it can run -- it extracts
+    // the sequences --, else the deletion, which reads only what every handle keeps
+    if (algorithm == GBWT_HIP_REMOVE_AUTO) algorithm = extractable ? GBWT_HIP_REMOVE_REBUILD : GBWT_HIP_REMOVE_DELETE;
+    if (hi.is_gbz && hi.has_translation) return fail(GBWT_HIP_UNSUPPORTED, "remove: the graph has a node-to-segment translation: removing paths from a translated graph is not supported");
+
+    // the paths as sequences, and the metadata without them: on the host, from what the handle holds
+    const auto t_meta = Clock::now();
+    std::vector<uint8_t> gone(paths, 0);
+    for (uint64_t k = 0; k < n; k++) gone[path_ids[k]] = 1;
+    std::vector<uint64_t> removed, kept;
+    removed.reserve(n * per_path); kept.reserve(hi.sequences - n * per_path);
+    for (uint64_t s = 0; s < hi.sequences; s++) (s / per_path < paths && gone[s / per_path] ? removed : kept).push_back(s);
+    HostIndex meta;
+    MergeRefusal bad = remove_metadata(hi, gone, meta);
+    if (bad) return refusal_status(bad);
+    meta.tags = remove_tags(hi.tags, hi.sample_names, meta.sample_names);
+    meta.gbz_tags = remove_tags(hi.gbz_tags, hi.sample_names, meta.sample_names);
+    double metadata_ms = ms_since(t_meta);
+
+    // The widths of the construction (u32 positions, build.hpp).  The deletion lays out all positions of the INPUT; the rebuild those of the
+    // kept sequences, whose visits the host knows only behind the extraction where the input itself is beyond the widths (rebuild()).
+    const uint64_t input_visits = hi.size >= hi.sequences ? hi.size - hi.sequences : 0;
+    const bool device_work = !kept.empty() && input_visits != 0;
+    if (device_work) {
+        const gbwt_hip_status st = algorithm == GBWT_HIP_REMOVE_DELETE ? check_build_sizes(hi.sequences, input_visits, 0) : check_build_sizes(kept.size(), 0, 0);
+        if (st != GBWT_HIP_OK) return st;
+    }
+
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)"); }
+    const int device = index->device;
+    try {
+        HIP_CHECK(hipSetDevice(device));
+        Stream stream;
+        const MergeInput in{index->dev, hi.sequences, input_visits, hi.alphabet_offset, hi.alphabet_size};
+        BuildOutput o;
+        RemoveWalk walk;
+        if (!device_work) build_without_visits(kept.size(), o);
+        else if (algorithm == GBWT_HIP_REMOVE_REBUILD) {
+            const gbwt_hip_status st = rebuild(index, kept, o, stream.s);
+            if (st != GBWT_HIP_OK) return st;
+        } else remove_records_on_device(in, removed.data(), removed.size(), o, walk, stream.s);
+        walk.removed_sequences = removed.size(); walk.removed_steps = in.visits - o.visits;
+
+        const auto t_open = Clock::now();
+        std::unique_ptr<gbwt_hip_index> ix(new gbwt_hip_index);
+        ix->device = device;
+        ix->caps = (flags & GBWT_HIP_OPEN_GFA) ? (flags | GBWT_HIP_OPEN_EXTRACT) : flags;
+        ix->knobs = OpenKnobs::from_env();
+        HostIndex &h = ix->host;
+        h = index_from_records(o.data.data(), o.data.size(), o.starts.data(), o.starts.size(), o.alphabet_offset, o.alphabet_size, o.sequences, o.visits + o.sequences, hi.bidirectional);
+        if (hi.is_gbz) {
+            const auto t_graph = Clock::now();
+            bad = remove_graph(hi, h, meta);
+            if (bad) return refusal_status(bad);
+            metadata_ms += ms_since(t_graph);
+        }
+        h.tags = std::move(meta.tags); h.gbz_tags = std::move(meta.gbz_tags);
+        if (meta.has_metadata) {
+            h.has_metadata = true; h.metadata_flags = meta.metadata_flags;
+            h.sample_count = meta.sample_count; h.haplotype_count = meta.haplotype_count; h.contig_count = meta.contig_count;
+            h.path_names = std::move(meta.path_names); h.sample_names = std::move(meta.sample_names); h.contig_names = std::move(meta.contig_names);
+            h.generic_phase_on_disk = meta.generic_phase_on_disk;
+        }
+        if (meta.is_gbz) {
+            h.is_gbz = true; h.has_translation = false; h.graph_nodes = meta.graph_nodes;
+            h.sequences_labels = std::move(meta.sequences_labels);
+        }
+
+        gbwt_hip_remove_info m{};
+        m.visits = o.visits; m.sequences = o.sequences; m.records = o.records; m.data_bytes = o.data.size(); m.peak_scratch_bytes = o.peak_scratch;
+        m.removed_sequences = walk.removed_sequences; m.removed_steps = walk.removed_steps;
+        m.algorithm_used = algorithm; m.removed = 1; m.rounds = o.rounds;
+        m.walk_ms = walk.walk_ms; m.decode_ms = walk.decode_ms; m.compact_ms = walk.compact_ms; m.edges_ms = o.edges_ms; m.encode_ms = o.encode_ms;
+        m.metadata_ms = metadata_ms;
+        const gbwt_hip_status st = open_host_index(std::move(ix), out, t_open);
+        if (st != GBWT_HIP_OK) return st;
+        m.open_ms = ms_since(t_open);
+        (*out)->remove_info = m;
+        return GBWT_HIP_OK;
+    } catch (const HipError &e) {
+        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the removal does not fit in device memory: ") + e.what); }
+        return status_of(e);
+    }
+    GBWT_HIP_GUARD_END
+}
+
+gbwt_hip_status gbwt_hip_last_remove_info(const gbwt_hip_index *ix, gbwt_hip_remove_info *out) {
+    GBWT_HIP_GUARD_BEGIN
+    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
+    *out = ix->remove_info;
+    return GBWT_HIP_OK;
+    GBWT_HIP_GUARD_END
+}
+
+}  // extern "C"

@@ -17,6 +17,7 @@
 
 #include "build.hpp"
 #include "capi_internal.hpp"
+#include "hip_raii.hpp"
 #include "lf_device.hpp"
 #include "merge.hpp"
 
@@ -24,8 +25,9 @@ namespace gbwt_hip {
 
 namespace {
 
+using namespace record_access;
+
 constexpr uint32_t THREADS = 256;
-constexpr uint64_t NO_RECORD = ~uint64_t(0);
 
 using Scratch = BuildScratch;
 using Buf = BuildBuf;
@@ -33,60 +35,12 @@ using Buf = BuildBuf;
 inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + THREADS - 1) / THREADS); }
 __device__ __forceinline__ uint64_t global_thread() { return static_cast<uint64_t>(blockIdx.x) * THREADS + threadIdx.x; }
 
-// entries of a[0, n) that are <= x (a is non-decreasing)
-__device__ __forceinline__ uint64_t upper_bound(const uint32_t *a, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // An input with the first position of every record (first[records] = sequences + visits)
 struct Side {
     DeviceIndex ix;
     const uint32_t *first;
     uint64_t sequences;
 };
-
-// the record of node v (0: the endmarker), or NO_RECORD
-__device__ __forceinline__ uint64_t record_of_node(const DeviceIndex &ix, uint64_t v) {
-    if (v == 0) return 0;
-    if (v <= ix.alphabet_offset) return NO_RECORD;
-    const uint64_t r = v - ix.alphabet_offset;
-    return r < ix.n_records ? r : NO_RECORD;
-}
-
-__device__ __forceinline__ uint64_t node_of_record(const DeviceIndex &ix, uint64_t r) { return r == 0 ? 0 : r + ix.alphabet_offset; }
-
-// opens record r: the cursor stands behind sigma; false for an empty record
-__device__ __forceinline__ bool open_by_record(const DeviceIndex &ix, uint64_t r, ByteCursor &c, uint64_t &sigma) {
-    if (r >= ix.n_records) return false;
-    uint64_t start, limit;
-    record_bounds(ix, r, start, limit);
-    if (start >= limit || limit > ix.data_len) return false;
-    c = ByteCursor(ix.data, start, limit);
-    if (!c.varint(sigma)) return false;
-    return sigma != 0;
-}
-
-// the stored offset of edge v -> w in X (v, w real nodes); false when X has no such edge
-__device__ __forceinline__ bool edge_offset_of(const DeviceIndex &ix, uint64_t v, uint64_t w, uint64_t &offset) {
-    ByteCursor c(ix.data, 0, 0);
-    uint64_t sigma;
-    const uint64_t r = record_of_node(ix, v);
-    if (r == NO_RECORD || !open_by_record(ix, r, c, sigma)) return false;
-    uint64_t node = 0;
-    for (uint64_t e = 0; e < sigma; e++) {
-        uint64_t delta, off;
-        if (!c.varint(delta) || !c.varint(off)) return false;
-        node += delta;
-        if (node == w) { offset = off; return true; }
-        if (node > w) return false;
-    }
-    return false;
-}
 
 // P_X(w, v) where X has no edge v -> w: through the smallest predecessor of w above v.  The edge list of flip(w) is sorted by the
 // successor, that is by flip(u): of the two orientations of a node the reverse one comes first as a predecessor, so the whole list
@@ -248,7 +202,7 @@ __global__ __launch_bounds__(THREADS) void k_merge_decode_long(DeviceIndex ix, c
         __syncthreads();
         const uint64_t lo = s_start[0], hi = s_start[runs];
         for (uint64_t p = lo + threadIdx.x; p < hi; p += THREADS) {
-            const uint64_t k = upper_bound(s_start, runs, p) - 1;       // s_start[0] <= p
+            const uint64_t k = merge_upper_bound(s_start, runs, p) - 1;       // s_start[0] <= p
             body[base + p] = s_value[k];
         }
         __syncthreads();
@@ -297,7 +251,7 @@ __global__ __launch_bounds__(THREADS) void k_merge_lengths(Side A, Side B, uint6
 
 // Position t of X's bodies: its record and its place in it
 __device__ __forceinline__ void locate_position(const Side &X, uint64_t t, uint64_t &r, uint64_t &k) {
-    r = upper_bound(X.first, X.ix.n_records + 1, t) - 1;     // the last record that starts at or before t: the one that is not empty
+    r = merge_upper_bound(X.first, X.ix.n_records + 1, t) - 1;     // the last record that starts at or before t: the one that is not empty
     k = t - X.first[r];
 }
 
@@ -319,7 +273,7 @@ __global__ __launch_bounds__(THREADS) void k_merge_interleave(Side W, Side R, co
         v = node_of_record(R.ix, r);
         const uint64_t rw = record_of_node(W.ix, v);
         at = k;
-        if (rw != NO_RECORD) at += upper_bound(cross + W.first[rw], W.first[rw + 1] - W.first[rw], k);
+        if (rw != NO_RECORD) at += merge_upper_bound(cross + W.first[rw], W.first[rw + 1] - W.first[rw], k);
         next = body_r[u];
     }
     const uint64_t rm = v == 0 ? 0 : v - alphabet_offset;
@@ -349,14 +303,6 @@ __global__ __launch_bounds__(THREADS) void k_merge_concat(const uint64_t *__rest
     else if (t == na + nb) offsets[t] = ta + tb;
 }
 
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    Events() { for (auto &x : e) HIP_CHECK(hipEventCreate(&x)); }
-    ~Events() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
-    Events(const Events &) = delete;
-    Events &operator=(const Events &) = delete;
-};
-
 void exclusive_sum32(const uint32_t *in, uint32_t *out, uint64_t n, Scratch &sc, Buf &temp, hipStream_t s) {
     size_t bytes = 0;
     HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n, s));
@@ -364,13 +310,9 @@ void exclusive_sum32(const uint32_t *in, uint32_t *out, uint64_t n, Scratch &sc,
     HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp.ptr, bytes, in, out, n, s));
 }
 
-// first[] and the bodies of one input
-struct Decoded {
-    Buf first, body;
-    uint64_t positions = 0;
-};
+}  // namespace
 
-void decode_bodies(const MergeInput &in, Decoded &d, Scratch &sc, Buf &temp, hipStream_t s) {
+void merge_decode_bodies(const MergeInput &in, MergeDecoded &d, BuildScratch &sc, BuildBuf &temp, hipStream_t s) {
     const uint64_t records = in.ix.n_records;
     d.positions = in.sequences + in.visits;
     d.first.alloc(sc, (records + 1) * sizeof(uint32_t));
@@ -398,26 +340,24 @@ void decode_bodies(const MergeInput &in, Decoded &d, Scratch &sc, Buf &temp, hip
     HIP_CHECK(hipStreamSynchronize(s));                     // (len, is_long and long_records go out of scope)
 }
 
-}  // namespace
-
 void merge_records_on_device(const MergeInput &a, const MergeInput &b, BuildOutput &out, MergeWalk &walk, hipStream_t s) {
     const uint64_t slots = out.sequences + out.visits, records = out.records, alphabet_offset = out.alphabet_offset;
     Scratch sc;
-    Events ev;
+    EventSet<4> ev;
     Buf temp;
     HIP_CHECK(hipEventRecord(ev.e[0], s));
 
     // 2. lengths and bodies of both inputs (the walk wants the lengths)
-    Decoded da, db;
-    decode_bodies(a, da, sc, temp, s);
-    decode_bodies(b, db, sc, temp, s);
+    MergeDecoded da, db;
+    merge_decode_bodies(a, da, sc, temp, s);
+    merge_decode_bodies(b, db, sc, temp, s);
     HIP_CHECK(hipEventRecord(ev.e[1], s));
     const Side A{a.ix, da.first.as<uint32_t>(), a.sequences}, B{b.ix, db.first.as<uint32_t>(), b.sequences};
 
     // 1. cross ranks of the input with fewer visits; ties go to b
     const bool walk_b = b.visits <= a.visits;
     const Side &W = walk_b ? B : A, &R = walk_b ? A : B;
-    const Decoded &dw = walk_b ? db : da, &dr = walk_b ? da : db;
+    const MergeDecoded &dw = walk_b ? db : da, &dr = walk_b ? da : db;
     const MergeInput &w_in = walk_b ? b : a;
     walk.walked_input = walk_b ? 1 : 0; walk.walked_sequences = w_in.sequences; walk.walked_steps = w_in.visits;
     Buf cross(sc, dw.positions * sizeof(uint32_t));

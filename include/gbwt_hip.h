@@ -771,6 +771,60 @@ typedef struct {
 } gbwt_hip_merge_info;
 gbwt_hip_status gbwt_hip_last_merge_info(const gbwt_hip_index *index, gbwt_hip_merge_info *out);
 
+/* ---- removal: an index without some of its paths ------------------------------------------------------------------------------------------
+ * The index of the sequences of `index` that do not belong to the paths path_ids[0, n), in their old order and renumbered densely: byte
+ * for byte what gbwt_hip_build_from_paths returns for those sequences -- record stream, record starts, sequences, size, alphabet_offset,
+ * alphabet_size, bidirectional.  In a bidirectional index path p is the sequences 2p and 2p + 1, in a unidirectional one sequence p.
+ * alphabet_offset and alphabet_size are those of the kept sequences, as the construction defines them: the alphabet shrinks when the
+ * smallest or the largest visited node goes, and a node that nobody visits any more has the record of one byte 0.  n == 0 gives a copy
+ * built from all sequences; removing every path gives the index of a set without sequences.  The result is opened with `flags` as by
+ * gbwt_hip_open_records_flags; the input is only read and stays usable.
+ *
+ * GBWT_HIP_BAD_ARGUMENT, before the device is touched: a null index or out; null path_ids with n > 0; bad flags; an unknown algorithm; a
+ * nonzero reserved field; a path id at or above the number of paths, or one that appears twice (the message names the id); _REBUILD on
+ * a handle that is not open for extraction.  *out is cleared by a call that fails.
+ * Widths: those of the construction (visits + sequences at most 2^32 - 1), else GBWT_HIP_UNSUPPORTED in its wording -- for DELETE over
+ * the INPUT, whose positions it lays out, and before the device is touched; for REBUILD over the kept sequences, before the device is
+ * touched where the input is within the widths or the kept sequences alone are beyond them, else behind the extraction and before the
+ * construction.  A larger index loses paths by REBUILD when what is kept fits.
+ *
+ * Algorithms.  DELETE (bidirectional or not): all positions of all records form one array; one lane per removed sequence
+ * follows it with the plain LF step and marks its positions, a prefix sum over the marks moves every kept position forward, and the
+ * compacted record bodies are encoded by the construction's own phases.  The offset of a kept edge v -> w is its old offset P less the
+ * marks among the first P positions of w's old record.  Nothing is ranked or sorted by prefix, and no atomics are used.  It reads the
+ * record bytes, the record starts and the endmarker, which every handle keeps, whatever it was opened for.  REBUILD:
+ * gbwt_hip_extract_device of the kept sequences and the construction over those rows.  AUTO: REBUILD where the handle is open for
+ * extraction, else DELETE -- the rule of gbwt_hip_merge, which the measurement confirmed.  (The walk of DELETE is one dependent chain per
+ * removed sequence; on 100 000 sites x 1 000 haplotypes DELETE took 1 245 ms against 630 ms of REBUILD for 10 removed haplotypes and
+ * 1 348 ms against 301 ms for 500: profiles/r17_remove_few.json, _half.json, tools/remove_bench.py.)
+ *
+ * Metadata (assembled on the host).  None in the input: none.  Metadata without path, sample or contig names: GBWT_HIP_UNSUPPORTED.
+ * Else the names of the removed paths go, and so do the sample names and the contig names that no kept path uses; the rest keep their
+ * order and the ids in the kept path names are remapped.  haplotype_count = distinct (sample, phase) over the kept path names.  Tags of
+ * the GBWT and of the GBZ are copied; reference_samples loses the names that were samples and no longer are, and is absent when none is
+ * left.  Document-array samples are dropped.
+ * Graph (a GBZ): the labels of the nodes that are still visited, as in a construction from GFA.  A graph with a node-to-segment
+ * translation: GBWT_HIP_UNSUPPORTED. */
+#define GBWT_HIP_REMOVE_AUTO    0   /* rebuild where the handle is open for extraction, else deletion */
+#define GBWT_HIP_REMOVE_REBUILD 1   /* extract the kept sequences to rows in HBM, run the construction */
+#define GBWT_HIP_REMOVE_DELETE  2   /* mark, compact, re-encode; ranks nothing */
+typedef struct { uint32_t algorithm; uint32_t reserved32; uint64_t reserved[2]; } gbwt_hip_remove_options;   /* reserved: 0; NULL: AUTO */
+gbwt_hip_status gbwt_hip_remove_paths(const gbwt_hip_index *index, const uint64_t *path_ids, uint64_t n, const gbwt_hip_remove_options *opts,
+                                      uint32_t flags, gbwt_hip_index **out);
+/* The removal behind a handle; all zeros for a handle that did not come from one.  visits .. data_bytes: of the result;
+ * peak_scratch_bytes: the most HBM the removal held at once (without the input); removed_sequences / removed_steps: the sequences that
+ * went and their visits; algorithm_used: _DELETE or _REBUILD; rounds: the doubling rounds of a REBUILD; decode .. encode: HIP events around
+ * the phases (a REBUILD fills edges and encode only) -- decode: lengths, scan and bodies; walk: the clearing of the marks, the copy of the
+ * sequence ids to the device and the marking walk; compact: the prefix sum, the copy of its total to the host, the scatter and the
+ * min / max reduction of the new alphabet; edges and encode: as in gbwt_hip_build_info; metadata / open: host clock. */
+typedef struct {
+    uint64_t visits, sequences, records, data_bytes, peak_scratch_bytes, removed_sequences, removed_steps;
+    uint32_t algorithm_used, removed, rounds, reserved32;
+    float walk_ms, decode_ms, compact_ms, edges_ms, encode_ms;
+    double metadata_ms, open_ms;
+} gbwt_hip_remove_info;
+gbwt_hip_status gbwt_hip_last_remove_info(const gbwt_hip_index *index, gbwt_hip_remove_info *out);
+
 /* ---- multi-GPU: the one exchange of a sharded extraction -------------------------------------------------------------
  * The reference's parallel axis is the path: rayon workers pull path ids and hand their finished lines to ONE writer behind a mutex
  * (src/bin/gbunzip.rs:27, 421-434).  Sharded over GPUs -- one process per GPU, the index replicated, path p on rank p mod world

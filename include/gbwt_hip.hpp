@@ -114,6 +114,15 @@ public:
         check(gbwt_hip_last_merge_info(index_.get(), &info));
         return info;
     }
+    // ---- removal on the device (gbwt_hip.h, "removal"): the index without the paths `path_ids`; *this is only read
+    GBWT remove_paths(const std::vector<uint64_t> &path_ids, uint32_t algorithm = GBWT_HIP_REMOVE_AUTO, uint32_t flags = GBWT_HIP_OPEN_ALL) const {
+        return GBWT(removed_handle(path_ids, algorithm, flags));
+    }
+    gbwt_hip_remove_info last_remove_info() const {
+        gbwt_hip_remove_info info{};
+        check(gbwt_hip_last_remove_info(index_.get(), &info));
+        return info;
+    }
     GBWT clone_workspace() const { GBWT other(*this, 0); return other; }
 
     // ---- statistics, src/gbwt.rs:108-182
@@ -310,6 +319,12 @@ protected:
         check(gbwt_hip_merge(a.index_.get(), b.index_.get(), &options, flags, &h));
         return h;
     }
+    gbwt_hip_index *removed_handle(const std::vector<uint64_t> &path_ids, uint32_t algorithm, uint32_t flags) const {
+        const gbwt_hip_remove_options options{algorithm, 0, {0, 0}};
+        gbwt_hip_index *h = nullptr;
+        check(gbwt_hip_remove_paths(index_.get(), path_ids.data(), path_ids.size(), &options, flags, &h));
+        return h;
+    }
     GBWT(const GBWT &other, int) : index_(other.index_), stats_(other.stats_) { make_workspace(); }
     explicit GBWT(gbwt_hip_index *built) { index_.reset(built, gbwt_hip_close); init(); }
     void init() {
@@ -358,6 +373,10 @@ private:
 public:
     // two GBZ: records, metadata, tags and the union of the node labels (gbwt_hip.h, "merging")
     static GBZ merge(const GBZ &a, const GBZ &b, uint32_t algorithm = GBWT_HIP_MERGE_AUTO, uint32_t flags = GBWT_HIP_OPEN_ALL) { return GBZ(merged_handle(a, b, algorithm, flags)); }
+    // a GBZ without some of its paths: records, metadata, tags and the labels of the nodes still visited (gbwt_hip.h, "removal")
+    GBZ remove_paths(const std::vector<uint64_t> &path_ids, uint32_t algorithm = GBWT_HIP_REMOVE_AUTO, uint32_t flags = GBWT_HIP_OPEN_ALL) const {
+        return GBZ(removed_handle(path_ids, algorithm, flags));
+    }
     // ---- construction from GFA on the device (gbwt_hip.h, "construction from GFA"): a GBZ like a loaded one, from a file or a text in memory
     static GBZ from_gfa(const std::string &path, int device = 0, uint32_t flags = GBWT_HIP_OPEN_ALL) {
         gbwt_hip_index *h = nullptr;
