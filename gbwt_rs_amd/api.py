@@ -83,7 +83,15 @@ def parse_gfa(path):
     """Host-only counts of a GFA file (gbwt_hip_parse_gfa, no GPU): a dict with the fields of gbwt_hip_gfa_info."""
     g = GfaInfo()
     check(_lib.lib().gbwt_hip_parse_gfa(os.fsencode(path), C.byref(g)))
-    return {name: getattr(g, name) for name, _ in GfaInfo._fields_}
+    return _as_dict(g)
+
+
+def _as_dict(s, skip_reserved=False):  # the fields of a ctypes struct the library has filled, by name
+    return {name: getattr(s, name) for name, _ in s._fields_ if not (skip_reserved and name == "reserved")}
+
+
+def _ref_or_null(opts):  # an options struct as the library takes it: NULL = the call without options
+    return C.byref(opts) if opts is not None else None
 
 
 def _ptr(a):
@@ -180,7 +188,7 @@ class GBWT:
         for k, nxt in enumerate(handles[1:]):
             left = handles[0] if result is None else result
             h = C.c_void_p()
-            check(_lib.lib().gbwt_hip_merge(left._h, nxt._h, C.byref(opts) if opts is not None else None, flags if k == len(handles) - 2 else _lib.OPEN_ALL, C.byref(h)))
+            check(_lib.lib().gbwt_hip_merge(left._h, nxt._h, _ref_or_null(opts), flags if k == len(handles) - 2 else _lib.OPEN_ALL, C.byref(h)))
             merged = cls(h, device=left._device)
             if result is not None:
                 result.close()
@@ -191,7 +199,7 @@ class GBWT:
         """The merge behind the handle (gbwt_hip_last_merge_info): a dict; all zeros for a handle that was not merged."""
         m = _lib.MergeInfo()
         check(self._L.gbwt_hip_last_merge_info(self._h, C.byref(m)))
-        return {name: getattr(m, name) for name, _ in _lib.MergeInfo._fields_}
+        return _as_dict(m)
 
     def remove_paths(self, path_ids, algorithm=None, flags=_lib.OPEN_ALL):
         """The index without the paths path_ids, a new handle of the same class (gbwt_hip_remove_paths): what from_paths gives for the kept
@@ -204,7 +212,7 @@ class GBWT:
         ids = ids.astype(np.uint64)
         opts = None if algorithm is None else _lib.RemoveOptions(int(algorithm), 0)
         h = C.c_void_p()
-        check(self._L.gbwt_hip_remove_paths(self._h, _ptr(ids), ids.size, C.byref(opts) if opts is not None else None, flags, C.byref(h)))
+        check(self._L.gbwt_hip_remove_paths(self._h, _ptr(ids), ids.size, _ref_or_null(opts), flags, C.byref(h)))
         return type(self)(h, device=self._device)
 
     def keep_paths(self, path_ids, algorithm=None, flags=_lib.OPEN_ALL):
@@ -221,7 +229,7 @@ class GBWT:
         """The removal behind the handle (gbwt_hip_last_remove_info): a dict; all zeros for a handle that did not come from a removal."""
         m = _lib.RemoveInfo()
         check(self._L.gbwt_hip_last_remove_info(self._h, C.byref(m)))
-        return {name: getattr(m, name) for name, _ in _lib.RemoveInfo._fields_}
+        return _as_dict(m)
 
     def records(self):
         """(data u8[], starts u64[records]) of the handle: its record stream and dense record starts (gbwt_hip_records)."""
@@ -239,7 +247,7 @@ class GBWT:
         """The construction behind the handle (gbwt_hip_last_build_info): a dict; all zeros for a handle that was not built."""
         b = BuildInfo()
         check(self._L.gbwt_hip_last_build_info(self._h, C.byref(b)))
-        return {name: getattr(b, name) for name, _ in BuildInfo._fields_}
+        return _as_dict(b)
 
     def close(self):
         if getattr(self, "_ws", None):
@@ -274,13 +282,13 @@ class GBWT:
         """Where the time of the open went (gbwt_hip_get_open_times): a dict of milliseconds and counts."""
         t = OpenTimes()
         check(self._L.gbwt_hip_get_open_times(self._h, C.byref(t)))
-        return {name: getattr(t, name) for name, _ in OpenTimes._fields_}
+        return _as_dict(t)
 
     def memory_usage(self):
         """Bytes held by the index (device, host) and by this object's workspace (gbwt_hip_memory_usage): a dict."""
         m = Memory()
         check(self._L.gbwt_hip_memory_usage(self._h, self._ws, C.byref(m)))
-        return {name: getattr(m, name) for name, _ in Memory._fields_}
+        return _as_dict(m)
 
     # ---- statistics (src/gbwt.rs:105-175) -----------------------------------------------------
     def len(self):
@@ -471,7 +479,7 @@ class GBWT:
         hook_ms, jump_ms, shape_ms, hook_launches, jump_launches, shape_launches."""
         t = _lib.ComponentsTimes()
         check(self._L.gbwt_hip_last_components_ms(self._h, C.byref(t)))
-        return {name: getattr(t, name) for name, _ in _lib.ComponentsTimes._fields_}
+        return _as_dict(t)
 
     # ---- the graph: nodes and edges (any handle) --------------------------------------------------
     def node_iter(self):
@@ -742,7 +750,7 @@ class GBWT:
         """The locate index of the handle (gbwt_hip_locate_index_info) as a dict; all zeros before the first locate call."""
         info = LocateInfo()
         check(self._L.gbwt_hip_locate_index_info(self._h, C.byref(info)))
-        return {name: getattr(info, name) for name, _ in LocateInfo._fields_ if name != "reserved"}
+        return _as_dict(info, skip_reserved=True)
 
 
 class GBZ(GBWT):
@@ -766,10 +774,7 @@ class GBZ(GBWT):
         are no node ids (gbwt_hip_build_from_gfa_opts); both None is the call without options."""
         h = C.c_void_p()
         opts = cls._gfa_options(max_node, translate)
-        if opts is None:
-            check(_lib.lib().gbwt_hip_build_from_gfa(os.fsencode(path), device, flags, C.byref(h)))
-        else:
-            check(_lib.lib().gbwt_hip_build_from_gfa_opts(os.fsencode(path), C.byref(opts), device, flags, C.byref(h)))
+        check(_lib.lib().gbwt_hip_build_from_gfa_opts(os.fsencode(path), _ref_or_null(opts), device, flags, C.byref(h)))
         return cls(h, device=device)
 
     @classmethod
@@ -780,23 +785,20 @@ class GBZ(GBWT):
         text = np.frombuffer(bytes(data), dtype=np.uint8)
         h = C.c_void_p()
         opts = cls._gfa_options(max_node, translate)
-        if opts is None:
-            check(_lib.lib().gbwt_hip_build_from_gfa_text(_ptr(text), text.size, device, flags, C.byref(h)))
-        else:
-            check(_lib.lib().gbwt_hip_build_from_gfa_text_opts(_ptr(text), text.size, C.byref(opts), device, flags, C.byref(h)))
+        check(_lib.lib().gbwt_hip_build_from_gfa_text_opts(_ptr(text), text.size, _ref_or_null(opts), device, flags, C.byref(h)))
         return cls(h, device=device)
 
     def last_gfa_translation_info(self):
         """The translation behind a handle made from GFA (gbwt_hip_last_gfa_translation_info): a dict; all zeros for every other handle."""
         g = _lib.GfaTranslationInfo()
         check(self._L.gbwt_hip_last_gfa_translation_info(self._h, C.byref(g)))
-        return {name: getattr(g, name) for name, _ in _lib.GfaTranslationInfo._fields_ if name != "reserved"}
+        return _as_dict(g, skip_reserved=True)
 
     def last_gfa_info(self):
         """The parse behind a handle made from GFA (gbwt_hip_last_gfa_info): a dict; all zeros for every other handle."""
         g = GfaInfo()
         check(self._L.gbwt_hip_last_gfa_info(self._h, C.byref(g)))
-        return {name: getattr(g, name) for name, _ in GfaInfo._fields_}
+        return _as_dict(g)
 
     def paths(self):
         return self.sequences() // 2

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <functional>
+#include <memory>
 
 #include "../../include/gbwt_hip.h"
 #include "capi_internal.hpp"
@@ -98,5 +99,24 @@ void build_node_range(const uint32_t *d_nodes, uint64_t n, uint32_t &min_node, u
 gbwt_hip_status check_build_sizes(uint64_t n_paths, uint64_t path_visits, int bidirectional);
 gbwt_hip_status check_build_range(uint64_t min_node, uint64_t max_node);
 void build_without_visits(uint64_t sequences, BuildOutput &out);
+
+// THE ROAD FROM RECORDS TO A HANDLE, the same for every maker (construction, from GFA, merge, removal): the new handle
+// (new_handle) with its host image filled from the records (index_from_records).  The caller decorates the image -- metadata, tags, graph
+// (host_index.hpp: adopt_metadata) -- and hands it to open_host_index.
+std::unique_ptr<gbwt_hip_index> handle_from_build(const BuildOutput &o, bool bidirectional, int device, uint32_t flags);
+
+// What gbwt_hip_build_info, gbwt_hip_merge_info and gbwt_hip_remove_info say about the records, under the same names
+template <class Info>
+static void fill_build_counters(Info &m, const BuildOutput &o) {
+    m.visits = o.visits; m.sequences = o.sequences; m.records = o.records; m.data_bytes = o.data.size(); m.peak_scratch_bytes = o.peak_scratch;
+    m.rounds = o.rounds; m.edges_ms = o.edges_ms; m.encode_ms = o.encode_ms;
+}
+// ... and the whole of a gbwt_hip_build_info but open_ms, which the caller knows behind the open
+inline gbwt_hip_build_info build_info_of(const BuildOutput &o) {
+    gbwt_hip_build_info b{};
+    fill_build_counters(b, o);
+    b.built = 1; b.expand_ms = o.expand_ms; b.rank_ms = o.rank_ms;
+    return b;
+}
 
 }  // namespace gbwt_hip

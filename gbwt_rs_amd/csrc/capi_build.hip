@@ -19,8 +19,7 @@ gbwt_hip_status check_call(const void *offsets, uint64_t n_paths, int bidirectio
     *out = nullptr;
     if (n_paths && !offsets) return fail(GBWT_HIP_BAD_ARGUMENT, "null offsets");
     if (bidirectional != 0 && bidirectional != 1) return fail(GBWT_HIP_BAD_ARGUMENT, "bidirectional must be 0 or 1");
-    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
-    return GBWT_HIP_OK;
+    return check_open_flags(flags);
 }
 
 }  // namespace
@@ -52,6 +51,12 @@ void build_without_visits(uint64_t sequences, BuildOutput &o) {
     o.starts.assign(1, 0);
 }
 
+std::unique_ptr<gbwt_hip_index> handle_from_build(const BuildOutput &o, bool bidirectional, int device, uint32_t flags) {
+    std::unique_ptr<gbwt_hip_index> ix = new_handle(device, flags);
+    ix->host = index_from_records(o.data.data(), o.data.size(), o.starts.data(), o.starts.size(), o.alphabet_offset, o.alphabet_size, o.sequences, o.visits + o.sequences, bidirectional);
+    return ix;
+}
+
 }  // namespace gbwt_hip
 
 namespace {
@@ -67,8 +72,6 @@ gbwt_hip_status check_offsets(const uint64_t *offsets, uint64_t n_paths, int bid
     return check_build_sizes(n_paths, path_visits, bidirectional);
 }
 
-gbwt_hip_status check_range(uint64_t min_node, uint64_t max_node) { return check_build_range(min_node, max_node); }
-
 // d_offsets / d_nodes in HBM of `device` (made current by the caller), the range of the nodes over the sequences known
 gbwt_hip_status build_and_open(const uint64_t *d_offsets, const uint32_t *d_nodes, uint64_t n_paths, uint64_t path_visits, uint64_t min_node, uint64_t max_node, int bidirectional,
                                int device, uint32_t flags, hipStream_t s, gbwt_hip_index **out) {
@@ -78,24 +81,12 @@ gbwt_hip_status build_and_open(const uint64_t *d_offsets, const uint32_t *d_node
         const BuildInput in{d_offsets, d_nodes, n_paths, path_visits, bidirectional != 0, min_node, max_node};
         build_records_on_device(in, o, s);               // (all of its scratch is free again when it returns)
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    const gbwt_hip_status st = gbwt_hip_open_records_flags(o.data.data(), o.data.size(), o.starts.data(), o.starts.size(), o.alphabet_offset, o.alphabet_size, o.sequences,
-                                                           o.visits + o.sequences, bidirectional, device, flags, out);
+    const auto t_open = Clock::now();
+    const gbwt_hip_status st = open_host_index(handle_from_build(o, bidirectional != 0, device, flags), out, t_open);
     if (st != GBWT_HIP_OK) return st;
-    gbwt_hip_build_info &b = (*out)->build_info;
-    b.visits = o.visits; b.sequences = o.sequences; b.records = o.records; b.data_bytes = o.data.size(); b.peak_scratch_bytes = o.peak_scratch;
-    b.rounds = o.rounds; b.built = 1;
-    b.expand_ms = o.expand_ms; b.rank_ms = o.rank_ms; b.edges_ms = o.edges_ms; b.encode_ms = o.encode_ms;
-    b.open_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    (*out)->build_info = build_info_of(o);
+    (*out)->build_info.open_ms = ms_since(t_open);
     return GBWT_HIP_OK;
-}
-
-gbwt_hip_status no_device() { return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)"); }
-
-bool have_device() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return false; }
-    return true;
 }
 
 }  // namespace
@@ -117,10 +108,11 @@ gbwt_hip_status gbwt_hip_build_from_paths(const uint64_t *offsets, const uint64_
     }
     if (path_visits) {
         if (bidirectional) { min_node &= ~uint64_t(1); max_node |= 1; }   // the reverse sequences visit the flipped nodes
-        st = check_range(min_node, max_node);
+        st = check_build_range(min_node, max_node);
         if (st != GBWT_HIP_OK) return st;
     }
-    if (!have_device()) return no_device();
+    st = require_device();
+    if (st != GBWT_HIP_OK) return st;
     try {
         HIP_CHECK(hipSetDevice(device));
         Stream stream;
@@ -136,8 +128,7 @@ gbwt_hip_status gbwt_hip_build_from_paths(const uint64_t *offsets, const uint64_
         }
         return build_and_open(d_offsets.as<uint64_t>(), d_nodes.as<uint32_t>(), n_paths, path_visits, min_node, max_node, bidirectional, device, flags, stream.s, out);
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the construction does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "the construction");
     }
     GBWT_HIP_GUARD_END
 }
@@ -147,7 +138,8 @@ gbwt_hip_status gbwt_hip_build_from_rows_device(const uint64_t *d_offsets, const
     GBWT_HIP_GUARD_BEGIN
     gbwt_hip_status st = check_call(d_offsets, n_paths, bidirectional, flags, out);
     if (st != GBWT_HIP_OK) return st;
-    if (!have_device()) return no_device();
+    st = require_device();
+    if (st != GBWT_HIP_OK) return st;
     try {
         HIP_CHECK(hipSetDevice(device));
         Stream stream;
@@ -164,13 +156,12 @@ gbwt_hip_status gbwt_hip_build_from_rows_device(const uint64_t *d_offsets, const
             if (lo < 2) return fail(GBWT_HIP_BAD_ARGUMENT, "a node of the rows is " + std::to_string(lo) + ", below 2 (a node is 2 * id + orientation, id >= 1)");
             min_node = lo; max_node = hi;
             if (bidirectional) { min_node &= ~uint64_t(1); max_node |= 1; }
-            st = check_range(min_node, max_node);
+            st = check_build_range(min_node, max_node);
             if (st != GBWT_HIP_OK) return st;
         }
         return build_and_open(d_offsets, d_nodes, n_paths, path_visits, min_node, max_node, bidirectional, device, flags, stream.s, out);
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the construction does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "the construction");
     }
     GBWT_HIP_GUARD_END
 }
@@ -206,9 +197,7 @@ gbwt_hip_status gbwt_hip_save(const gbwt_hip_index *ix, const char *path) {
 
 gbwt_hip_status gbwt_hip_last_build_info(const gbwt_hip_index *ix, gbwt_hip_build_info *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    *out = ix->build_info;
-    return GBWT_HIP_OK;
+    return last_info(ix, out, &gbwt_hip_index::build_info);
     GBWT_HIP_GUARD_END
 }
 

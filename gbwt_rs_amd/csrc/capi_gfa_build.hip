@@ -9,28 +9,17 @@
 #include "capi_internal.hpp"
 #include "gfa_meta.hpp"
 #include "gfa_parse.hpp"
+#include "hip_raii.hpp"
 
 using namespace gbwt_hip;
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIP_CHECK(hipStreamCreate(&s)); }
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-    Stream(const Stream &) = delete;
-    Stream &operator=(const Stream &) = delete;
-};
-
 gbwt_hip_status check_call(const void *input, const char *what, uint32_t flags, gbwt_hip_index **out) {
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     *out = nullptr;
     if (!input) return fail(GBWT_HIP_BAD_ARGUMENT, std::string("null ") + what);
-    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
-    return GBWT_HIP_OK;
+    return check_open_flags(flags);
 }
 
 gbwt_hip_status refuse(uint64_t line, uint32_t code) {
@@ -65,8 +54,8 @@ gbwt_hip_status check_options(const gbwt_hip_gfa_options *opts, GfaParseOptions 
 }
 
 gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, const GfaParseOptions &options, int device, uint32_t flags, gbwt_hip_index **out) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)"); }
+    gbwt_hip_status st = require_device();
+    if (st != GBWT_HIP_OK) return st;
     try {
         HIP_CHECK(hipSetDevice(device));
         Stream stream;
@@ -90,7 +79,7 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
         if (parse.refusal) return refuse(parse.refusal.line, parse.refusal.code);
 
         const uint64_t n_paths = parse.n_paths, steps = parse.row_nodes;      // (translated: the nodes of the steps)
-        gbwt_hip_status st = static_cast<gbwt_hip_status>(check_build_sizes(n_paths, steps, 1));
+        st = check_build_sizes(n_paths, steps, 1);
         if (st != GBWT_HIP_OK) return st;
         const uint64_t min_node = parse.min_node & ~uint64_t(1), max_node = parse.max_node | uint64_t(1);
         if (steps) {
@@ -109,25 +98,15 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
         else build_records_on_device(BuildInput{parse.d_offsets(), parse.d_nodes(), n_paths, steps, true, min_node, max_node}, o, stream.s);
 
         const auto t_open = Clock::now();
-        std::unique_ptr<gbwt_hip_index> ix(new gbwt_hip_index);
-        ix->device = device;
-        ix->caps = (flags & GBWT_HIP_OPEN_GFA) ? (flags | GBWT_HIP_OPEN_EXTRACT) : flags;
-        ix->knobs = OpenKnobs::from_env();
+        std::unique_ptr<gbwt_hip_index> ix = handle_from_build(o, true, device, flags);
         HostIndex &h = ix->host;
-        h = index_from_records(o.data.data(), o.data.size(), o.starts.data(), o.starts.size(), o.alphabet_offset, o.alphabet_size, o.sequences, o.visits + o.sequences, true);
-        h.has_metadata = true; h.metadata_flags = meta.metadata_flags;
-        h.sample_count = meta.sample_count; h.haplotype_count = meta.haplotype_count; h.contig_count = meta.contig_count;
-        h.path_names = std::move(meta.path_names); h.sample_names = std::move(meta.sample_names); h.contig_names = std::move(meta.contig_names);
-        h.generic_phase_on_disk = meta.generic_phase_on_disk;
-        if (have_reference_samples) { h.tags.emplace_back("reference_samples", reference_samples); h.gbz_tags.emplace_back("reference_samples", reference_samples); }
+        if (have_reference_samples) { meta.tags.emplace_back("reference_samples", reference_samples); meta.gbz_tags.emplace_back("reference_samples", reference_samples); }
+        adopt_metadata(h, std::move(meta));                                  // (assemble_gfa_metadata always says has_metadata; the graph comes from the parse)
         const bool translated = parse.translated && steps != 0;             // (without visits there are no nodes to map)
         if (translated) fill_gfa_translated_graph(h, std::move(labels), graph_nodes, std::move(translation.names), std::move(translation.starts), translation.mapping_len);
         else fill_gfa_graph(h, std::move(labels), graph_nodes);
 
-        gbwt_hip_build_info b{};
-        b.visits = o.visits; b.sequences = o.sequences; b.records = o.records; b.data_bytes = o.data.size(); b.peak_scratch_bytes = o.peak_scratch;
-        b.rounds = o.rounds; b.built = 1;
-        b.expand_ms = o.expand_ms; b.rank_ms = o.rank_ms; b.edges_ms = o.edges_ms; b.encode_ms = o.encode_ms;
+        gbwt_hip_build_info b = build_info_of(o);
         gbwt_hip_gfa_info g{};
         const GfaCounts &c = parse.counts;
         g.bytes = c.bytes; g.lines = c.lines; g.headers = c.headers; g.segments = c.segments; g.links = c.links; g.p_lines = c.p_lines; g.w_lines = c.w_lines;
@@ -150,8 +129,7 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
         (*out)->gfa_translation_info = tr;
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the construction does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "the construction");
     }
 }
 
@@ -160,11 +138,7 @@ gbwt_hip_status build_from_text(const char *text, uint64_t len, double read_ms, 
 extern "C" {
 
 gbwt_hip_status gbwt_hip_build_from_gfa_text(const char *text, uint64_t len, int device, uint32_t flags, gbwt_hip_index **out) {
-    GBWT_HIP_GUARD_BEGIN
-    const gbwt_hip_status st = check_call(len ? static_cast<const void *>(text) : static_cast<const void *>(""), "text", flags, out);
-    if (st != GBWT_HIP_OK) return st;
-    return build_from_text(text, len, 0.0, GfaParseOptions(), device, flags, out);
-    GBWT_HIP_GUARD_END
+    return gbwt_hip_build_from_gfa_text_opts(text, len, nullptr, device, flags, out);       // (no options: the defaults)
 }
 
 gbwt_hip_status gbwt_hip_build_from_gfa_text_opts(const char *text, uint64_t len, const gbwt_hip_gfa_options *opts, int device, uint32_t flags, gbwt_hip_index **out) {
@@ -193,27 +167,17 @@ gbwt_hip_status gbwt_hip_build_from_gfa_opts(const char *path, const gbwt_hip_gf
 
 gbwt_hip_status gbwt_hip_last_gfa_translation_info(const gbwt_hip_index *ix, gbwt_hip_gfa_translation_info *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    *out = ix->gfa_translation_info;
-    return GBWT_HIP_OK;
+    return last_info(ix, out, &gbwt_hip_index::gfa_translation_info);
     GBWT_HIP_GUARD_END
 }
 
 gbwt_hip_status gbwt_hip_build_from_gfa(const char *path, int device, uint32_t flags, gbwt_hip_index **out) {
-    GBWT_HIP_GUARD_BEGIN
-    const gbwt_hip_status st = check_call(path, "path", flags, out);
-    if (st != GBWT_HIP_OK) return st;
-    const auto t0 = Clock::now();
-    const GfaFile file(path);                     // (IoError: before the device is touched)
-    return build_from_text(file.data(), file.size(), ms_since(t0), GfaParseOptions(), device, flags, out);
-    GBWT_HIP_GUARD_END
+    return gbwt_hip_build_from_gfa_opts(path, nullptr, device, flags, out);
 }
 
 gbwt_hip_status gbwt_hip_last_gfa_info(const gbwt_hip_index *ix, gbwt_hip_gfa_info *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    *out = ix->gfa_info;
-    return GBWT_HIP_OK;
+    return last_info(ix, out, &gbwt_hip_index::gfa_info);
     GBWT_HIP_GUARD_END
 }
 

@@ -1,4 +1,4 @@
-// capi_internal.hpp -- handle / workspace structures shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, capi_topology.hip, capi_build.hip, capi_gfa_build.hip, capi_merge.hip, capi_remove.hip, gfa.hip, comm.hip).
+// capi_internal.hpp -- handle / workspace structures, statuses and the checks of a call that makes a handle, shared by the C-ABI translation units (capi_open.hip, capi_extract.hip, capi_query.hip, capi_graph.hip, capi_topology.hip, capi_refpos.hip, capi_locate.hip, capi_build.hip, capi_gfa_build.hip, capi_merge.hip, capi_remove.hip, gfa.hip, sequences.hip, tags.hip, comm.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -168,6 +168,27 @@ inline gbwt_hip_status status_of(const HipError &e) {
     std::string msg = std::string(e.what) + ": " + hipGetErrorString(e.err);
     if (e.err == hipErrorNoDevice || e.err == hipErrorInvalidDevice) return fail(GBWT_HIP_NO_DEVICE, msg);
     return fail(GBWT_HIP_DEVICE_ERROR, msg);
+}
+
+// The catch of an entry point that allocates by the size of a request: out of device memory is the caller's to act on (`what`: "the
+// merge", "a locate request", ...), and the error state is cleared so that the next call starts clean
+inline gbwt_hip_status status_of(const HipError &e, const char *what) {
+    if (e.err != hipErrorOutOfMemory) return status_of(e);
+    (void)hipGetLastError();
+    return fail(GBWT_HIP_CAPACITY, std::string(what) + " does not fit in device memory: " + e.what);
+}
+
+// The checks every call that makes a handle starts with: its flags, and -- once its arguments are through -- a device to make it on
+inline gbwt_hip_status check_open_flags(uint32_t flags) {
+    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
+    return GBWT_HIP_OK;
+}
+inline uint32_t normalised_caps(uint32_t flags) { return (flags & GBWT_HIP_OPEN_GFA) ? (flags | GBWT_HIP_OPEN_EXTRACT) : flags; }   // the lines are formatted from extracted rows
+inline gbwt_hip_status require_device() {
+    int count = 0;
+    if (hipGetDeviceCount(&count) == hipSuccess && count != 0) return GBWT_HIP_OK;
+    (void)hipGetLastError();
+    return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)");
 }
 
 // Lippincott function: the status of the exception in flight.  No exception may cross the C ABI (the caller is Rust / C /
@@ -489,8 +510,27 @@ struct gbwt_hip_workspace {
 };
 
 namespace gbwt_hip {
+// A handle with its settings and nothing else: the device, what it is opened for (caps decide which arrays the open makes) and the
+// GBWT_HIP_* settings of the open, read here and nowhere else
+inline std::unique_ptr<gbwt_hip_index> new_handle(int device, uint32_t flags) {
+    std::unique_ptr<gbwt_hip_index> ix(new gbwt_hip_index);
+    ix->device = device;
+    ix->caps = normalised_caps(flags);
+    ix->knobs = OpenKnobs::from_env();
+    return ix;
+}
+
+// gbwt_hip_last_*_info, gbwt_hip_get_stats, gbwt_hip_get_open_times: a struct the open or a maker left on the handle
+// (static, like fill_build_counters and extract_rows: a helper over the ABI's types adds no symbol to what the library exports)
+template <class Info>
+static gbwt_hip_status last_info(const gbwt_hip_index *ix, Info *out, Info gbwt_hip_index::*member) {
+    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
+    *out = ix->*member;
+    return GBWT_HIP_OK;
+}
+
 // capi_open.hip: the open behind every handle -- device passes, GFA tables, line cache -- for a host image that is already filled (takes
-// ownership; t_open: when the caller started, for the handle's open times).  Settings (knobs, caps, device) are the caller's to set.
+// ownership; t_open: when the caller started, for the handle's open times).  Settings come with the handle (new_handle).
 gbwt_hip_status open_host_index(std::unique_ptr<gbwt_hip_index> ix, gbwt_hip_index **out, std::chrono::steady_clock::time_point t_open);
 
 // The labels of a handle as the kernels see them (sequences.hip, tags.hip): node v (GBWT-encoded, 2 id + o) has label bytes[off[s] .. off[s + 1])

@@ -242,8 +242,7 @@ gbwt_hip_status locate_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws,
         }
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("a locate request does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "a locate request");
     }
 }
 
@@ -339,8 +338,7 @@ gbwt_hip_status gbwt_hip_locate_positions(const gbwt_hip_index *ix, gbwt_hip_wor
             return fail(GBWT_HIP_DEVICE_ERROR, "locate: a position met neither a sampled record nor the end of a sequence (an inconsistent index)");
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("a locate request does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "a locate request");
     }
     GBWT_HIP_GUARD_END
 }

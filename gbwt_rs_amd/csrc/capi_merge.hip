@@ -16,25 +16,16 @@ using namespace gbwt_hip;
 
 namespace {
 
-gbwt_hip_status refusal_status(const MergeRefusal &bad) {
-    return fail(bad.kind == MergeRefusal::UNSUPPORTED ? GBWT_HIP_UNSUPPORTED : GBWT_HIP_INVALID_DATA, "merge: " + bad.what);
-}
-
 MergeInput input_of(const gbwt_hip_index *ix) {
     const HostIndex &h = ix->host;
     return MergeInput{ix->dev, h.sequences, h.size - h.sequences, h.alphabet_offset, h.alphabet_size};
 }
 
-// all sequences of a handle as rows in HBM (they stay in the workspace)
+// all sequences of a handle as rows in HBM
 gbwt_hip_status extract_all(const gbwt_hip_index *ix, Workspace &w, gbwt_hip_paths &rows) {
-    rows = gbwt_hip_paths{nullptr, nullptr, 0, 0};
-    const uint64_t n = ix->host.sequences;
-    if (n == 0) return GBWT_HIP_OK;
-    gbwt_hip_status st = gbwt_hip_workspace_create(ix, &w.ws);
-    if (st != GBWT_HIP_OK) return st;
-    std::vector<uint64_t> ids(n);
-    for (uint64_t i = 0; i < n; i++) ids[i] = i;
-    return gbwt_hip_extract_device(ix, w.ws, ids.data(), n, &rows);
+    std::vector<uint64_t> ids(ix->host.sequences);
+    for (uint64_t i = 0; i < ids.size(); i++) ids[i] = i;
+    return extract_rows(ix, w, ids.data(), ids.size(), rows);
 }
 
 // MERGE_REBUILD: the rows of both, behind one another, through the construction -- as sequences, so the order is kept exactly
@@ -48,7 +39,6 @@ gbwt_hip_status rebuild(const gbwt_hip_index *a, const gbwt_hip_index *b, uint64
     const uint64_t n = ra.n + rb.n, total = ra.total + rb.total;
     BuildScratch sc;
     BuildBuf offsets(sc, (n + 1) * sizeof(uint64_t)), nodes(sc, total * sizeof(uint32_t));
-    HIP_CHECK(hipDeviceSynchronize());                     // (the rows were written on the workspaces' streams)
     merge_concat_rows(ra.d_offsets, ra.d_nodes, ra.n, ra.total, rb.d_offsets, rb.d_nodes, rb.n, rb.total, offsets.as<uint64_t>(), nodes.as<uint32_t>(), s);
     HIP_CHECK(hipStreamSynchronize(s));
     build_records_on_device(BuildInput{offsets.as<uint64_t>(), nodes.as<uint32_t>(), n, total, false, min_node, max_node}, o, s);
@@ -65,7 +55,8 @@ gbwt_hip_status gbwt_hip_merge(const gbwt_hip_index *a, const gbwt_hip_index *b,
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     *out = nullptr;
     if (!a || !b) return fail(GBWT_HIP_BAD_ARGUMENT, "null index");
-    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
+    gbwt_hip_status st = check_open_flags(flags);
+    if (st != GBWT_HIP_OK) return st;
     uint32_t algorithm = GBWT_HIP_MERGE_AUTO;
     if (opts) {
         if (opts->algorithm > GBWT_HIP_MERGE_INSERT) return fail(GBWT_HIP_BAD_ARGUMENT, "options: algorithm is one of GBWT_HIP_MERGE_AUTO | _REBUILD | _INSERT");
@@ -87,7 +78,7 @@ gbwt_hip_status gbwt_hip_merge(const gbwt_hip_index *a, const gbwt_hip_index *b,
     // the widths of the construction over the merged set
     const MergeInput ia = input_of(a), ib = input_of(b);
     const uint64_t sequences = ia.sequences + ib.sequences, visits = ia.visits + ib.visits;
-    gbwt_hip_status st = check_build_sizes(sequences, visits, 0);
+    st = check_build_sizes(sequences, visits, 0);
     if (st != GBWT_HIP_OK) return st;
     BuildOutput o;
     o.sequences = sequences; o.visits = visits; o.alphabet_offset = 0; o.alphabet_size = 1;
@@ -104,17 +95,17 @@ gbwt_hip_status gbwt_hip_merge(const gbwt_hip_index *a, const gbwt_hip_index *b,
     const auto t_meta = Clock::now();
     HostIndex meta;
     MergeRefusal bad = merge_metadata(ha, hb, meta);
-    if (bad) return refusal_status(bad);
+    if (bad) return refusal_status(bad, "merge: ");
     if (ha.is_gbz) {
         bad = merge_graph(ha, hb, o.alphabet_offset, o.alphabet_size, meta);
-        if (bad) return refusal_status(bad);
+        if (bad) return refusal_status(bad, "merge: ");
     }
     meta.tags = merge_tags(ha.tags, hb.tags);
     meta.gbz_tags = merge_tags(ha.gbz_tags, hb.gbz_tags);
     const double metadata_ms = ms_since(t_meta);
 
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)"); }
+    st = require_device();
+    if (st != GBWT_HIP_OK) return st;
     const int device = a->device;
     try {
         HIP_CHECK(hipSetDevice(device));
@@ -127,29 +118,14 @@ gbwt_hip_status gbwt_hip_merge(const gbwt_hip_index *a, const gbwt_hip_index *b,
         } else merge_records_on_device(ia, ib, o, walk, stream.s);
 
         const auto t_open = Clock::now();
-        std::unique_ptr<gbwt_hip_index> ix(new gbwt_hip_index);
-        ix->device = device;
-        ix->caps = (flags & GBWT_HIP_OPEN_GFA) ? (flags | GBWT_HIP_OPEN_EXTRACT) : flags;
-        ix->knobs = OpenKnobs::from_env();
-        HostIndex &h = ix->host;
-        h = index_from_records(o.data.data(), o.data.size(), o.starts.data(), o.starts.size(), o.alphabet_offset, o.alphabet_size, o.sequences, o.visits + o.sequences, ha.bidirectional);
-        h.tags = std::move(meta.tags); h.gbz_tags = std::move(meta.gbz_tags);
-        if (meta.has_metadata) {
-            h.has_metadata = true; h.metadata_flags = meta.metadata_flags;
-            h.sample_count = meta.sample_count; h.haplotype_count = meta.haplotype_count; h.contig_count = meta.contig_count;
-            h.path_names = std::move(meta.path_names); h.sample_names = std::move(meta.sample_names); h.contig_names = std::move(meta.contig_names);
-            h.generic_phase_on_disk = meta.generic_phase_on_disk;
-        }
-        if (meta.is_gbz) {
-            h.is_gbz = true; h.has_translation = false; h.graph_nodes = meta.graph_nodes;
-            h.sequences_labels = std::move(meta.sequences_labels);
-        }
+        std::unique_ptr<gbwt_hip_index> ix = handle_from_build(o, ha.bidirectional, device, flags);
+        adopt_metadata(ix->host, std::move(meta));
 
         gbwt_hip_merge_info m{};
-        m.visits = o.visits; m.sequences = o.sequences; m.records = o.records; m.data_bytes = o.data.size(); m.peak_scratch_bytes = o.peak_scratch;
+        fill_build_counters(m, o);
         m.walked_sequences = walk.walked_sequences; m.walked_steps = walk.walked_steps;
-        m.algorithm_used = algorithm; m.walked_input = walk.walked_input; m.merged = 1; m.rounds = o.rounds;
-        m.walk_ms = walk.walk_ms; m.decode_ms = walk.decode_ms; m.interleave_ms = walk.interleave_ms; m.edges_ms = o.edges_ms; m.encode_ms = o.encode_ms;
+        m.algorithm_used = algorithm; m.walked_input = walk.walked_input; m.merged = 1;
+        m.walk_ms = walk.walk_ms; m.decode_ms = walk.decode_ms; m.interleave_ms = walk.interleave_ms;
         m.metadata_ms = metadata_ms;
         st = open_host_index(std::move(ix), out, t_open);
         if (st != GBWT_HIP_OK) return st;
@@ -157,17 +133,14 @@ gbwt_hip_status gbwt_hip_merge(const gbwt_hip_index *a, const gbwt_hip_index *b,
         (*out)->merge_info = m;
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the merge does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "the merge");
     }
     GBWT_HIP_GUARD_END
 }
 
 gbwt_hip_status gbwt_hip_last_merge_info(const gbwt_hip_index *ix, gbwt_hip_merge_info *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    *out = ix->merge_info;
-    return GBWT_HIP_OK;
+    return last_info(ix, out, &gbwt_hip_index::merge_info);
     GBWT_HIP_GUARD_END
 }
 

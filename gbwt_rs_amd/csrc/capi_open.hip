@@ -643,9 +643,7 @@ void release_for_lean_extraction(gbwt_hip_index &x) {
 gbwt_hip_status open_common(std::unique_ptr<gbwt_hip_index> ix, gbwt_hip_index **out, std::chrono::steady_clock::time_point t_open) {
     const auto t_parsed = std::chrono::steady_clock::now();
     fill_stats(*ix);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)");
+    if (const gbwt_hip_status st = require_device(); st != GBWT_HIP_OK) return st;
     OpenTrace trace{ix->knobs.trace};
     if (ix->host.pending && ix->record_bytes_uploaded) {
         // The loader still has work in the background (the record bytes into the host image, the node labels) and the GFA tables need
@@ -718,20 +716,15 @@ gbwt_hip_status gbwt_hip_parse_file(const char *path, gbwt_hip_stats *out) {
     GBWT_HIP_GUARD_END
 }
 
-static uint32_t normalised_caps(uint32_t flags) { return (flags & GBWT_HIP_OPEN_GFA) ? (flags | GBWT_HIP_OPEN_EXTRACT) : flags; }   // the lines are formatted from extracted rows
-
 gbwt_hip_status gbwt_hip_open_file(const char *path, int device, gbwt_hip_index **out) { return gbwt_hip_open_file_flags(path, device, GBWT_HIP_OPEN_ALL, out); }
 
 gbwt_hip_status gbwt_hip_open_file_flags(const char *path, int device, uint32_t flags, gbwt_hip_index **out) {
     GBWT_HIP_GUARD_BEGIN
     if (!path || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
+    if (const gbwt_hip_status st = check_open_flags(flags); st != GBWT_HIP_OK) return st;
     *out = nullptr;
     const auto t_open = std::chrono::steady_clock::now();
-    std::unique_ptr<gbwt_hip_index> ix(new gbwt_hip_index);
-    ix->device = device;
-    ix->caps = normalised_caps(flags);
-    ix->knobs = OpenKnobs::from_env();
+    std::unique_ptr<gbwt_hip_index> ix = new_handle(device, flags);
     // The record bytes start for the device as soon as the loader knows where they are, next to its decoding of the record starts
     // (9 ms of staged copy next to 6.7 ms of Elias-Fano decode on the headline index, one after the other until round 3).
     struct EarlyCopy {
@@ -804,15 +797,11 @@ gbwt_hip_status gbwt_hip_open_records_flags(const uint8_t *data, uint64_t data_l
                                             int bidirectional, int device, uint32_t flags, gbwt_hip_index **out) {
     GBWT_HIP_GUARD_BEGIN
     if (!out || (data_len && !data) || (n_records && !starts)) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
+    if (const gbwt_hip_status st = check_open_flags(flags); st != GBWT_HIP_OK) return st;
     *out = nullptr;
     const auto t_open = std::chrono::steady_clock::now();
-    std::unique_ptr<gbwt_hip_index> ix(new gbwt_hip_index);
-    ix->device = device;
-    ix->caps = normalised_caps(flags);
-    ix->knobs = OpenKnobs::from_env();
-    ix->host = index_from_records(data, data_len, starts, n_records, alphabet_offset, alphabet_size, n_sequences, size,
-                                  bidirectional != 0);
+    std::unique_ptr<gbwt_hip_index> ix = new_handle(device, flags);
+    ix->host = index_from_records(data, data_len, starts, n_records, alphabet_offset, alphabet_size, n_sequences, size, bidirectional != 0);
     return open_common(std::move(ix), out, t_open);
     GBWT_HIP_GUARD_END
 }
@@ -821,9 +810,7 @@ void gbwt_hip_close(gbwt_hip_index *index) { delete index; }
 
 gbwt_hip_status gbwt_hip_get_stats(const gbwt_hip_index *index, gbwt_hip_stats *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!index || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    *out = index->stats;
-    return GBWT_HIP_OK;
+    return last_info(index, out, &gbwt_hip_index::stats);
     GBWT_HIP_GUARD_END
 }
 
@@ -887,9 +874,7 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
 
 gbwt_hip_status gbwt_hip_get_open_times(const gbwt_hip_index *index, gbwt_hip_open_times *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!index || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    *out = index->times;
-    return GBWT_HIP_OK;
+    return last_info(index, out, &gbwt_hip_index::times);
     GBWT_HIP_GUARD_END
 }
 

@@ -178,8 +178,7 @@ gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
     } catch (const OutOfMemory &e) {
         return fail(GBWT_HIP_CAPACITY, e.what);
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("a request for positions does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "a request for positions");
     }
 }
 

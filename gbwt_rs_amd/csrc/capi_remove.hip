@@ -17,19 +17,12 @@ using namespace gbwt_hip;
 
 namespace {
 
-gbwt_hip_status refusal_status(const MergeRefusal &bad) {
-    return fail(bad.kind == MergeRefusal::UNSUPPORTED ? GBWT_HIP_UNSUPPORTED : GBWT_HIP_INVALID_DATA, "remove: " + bad.what);
-}
-
 // REMOVE_REBUILD: the rows of the kept sequences through the construction -- as sequences, so the order is kept exactly
 gbwt_hip_status rebuild(const gbwt_hip_index *ix, const std::vector<uint64_t> &kept, BuildOutput &o, hipStream_t s) {
     Workspace w;
-    gbwt_hip_paths rows{nullptr, nullptr, 0, 0};
-    gbwt_hip_status st = gbwt_hip_workspace_create(ix, &w.ws);
+    gbwt_hip_paths rows;
+    gbwt_hip_status st = extract_rows(ix, w, kept.data(), kept.size(), rows);
     if (st != GBWT_HIP_OK) return st;
-    st = gbwt_hip_extract_device(ix, w.ws, kept.data(), kept.size(), &rows);
-    if (st != GBWT_HIP_OK) return st;
-    HIP_CHECK(hipDeviceSynchronize());                     // (the rows were written on the workspace's stream)
     if (rows.total == 0) { build_without_visits(kept.size(), o); return GBWT_HIP_OK; }
     st = check_build_sizes(rows.n, rows.total, 0);         // the widths of the construction over the kept set (known before the call where the input is within them)
     if (st != GBWT_HIP_OK) return st;
@@ -51,7 +44,8 @@ gbwt_hip_status gbwt_hip_remove_paths(const gbwt_hip_index *index, const uint64_
     *out = nullptr;
     if (!index) return fail(GBWT_HIP_BAD_ARGUMENT, "null index");
     if (n && !path_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null path ids");
-    if (flags == 0 || (flags & ~uint32_t(GBWT_HIP_OPEN_ALL)) != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags: a non-empty set of GBWT_HIP_OPEN_EXTRACT | _SEARCH | _GFA");
+    gbwt_hip_status st = check_open_flags(flags);
+    if (st != GBWT_HIP_OK) return st;
     uint32_t algorithm = GBWT_HIP_REMOVE_AUTO;
     if (opts) {
         if (opts->algorithm > GBWT_HIP_REMOVE_DELETE) return fail(GBWT_HIP_BAD_ARGUMENT, "options: algorithm is one of GBWT_HIP_REMOVE_AUTO | _REBUILD | _DELETE");
@@ -78,7 +72,7 @@ gbwt_hip_status gbwt_hip_remove_paths(const gbwt_hip_index *index, const uint64_
     for (uint64_t s = 0; s < hi.sequences; s++) (s / per_path < paths && gone[s / per_path] ? removed : kept).push_back(s);
     HostIndex meta;
     MergeRefusal bad = remove_metadata(hi, gone, meta);
-    if (bad) return refusal_status(bad);
+    if (bad) return refusal_status(bad, "remove: ");
     meta.tags = remove_tags(hi.tags, hi.sample_names, meta.sample_names);
     meta.gbz_tags = remove_tags(hi.gbz_tags, hi.sample_names, meta.sample_names);
     double metadata_ms = ms_since(t_meta);
@@ -88,12 +82,12 @@ gbwt_hip_status gbwt_hip_remove_paths(const gbwt_hip_index *index, const uint64_
     const uint64_t input_visits = hi.size >= hi.sequences ? hi.size - hi.sequences : 0;
     const bool device_work = !kept.empty() && input_visits != 0;
     if (device_work) {
-        const gbwt_hip_status st = algorithm == GBWT_HIP_REMOVE_DELETE ? check_build_sizes(hi.sequences, input_visits, 0) : check_build_sizes(kept.size(), 0, 0);
+        st = algorithm == GBWT_HIP_REMOVE_DELETE ? check_build_sizes(hi.sequences, input_visits, 0) : check_build_sizes(kept.size(), 0, 0);
         if (st != GBWT_HIP_OK) return st;
     }
 
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(GBWT_HIP_NO_DEVICE, "no HIP device available (libgbwt_hip has no CPU fallback)"); }
+    st = require_device();
+    if (st != GBWT_HIP_OK) return st;
     const int device = index->device;
     try {
         HIP_CHECK(hipSetDevice(device));
@@ -103,59 +97,41 @@ gbwt_hip_status gbwt_hip_remove_paths(const gbwt_hip_index *index, const uint64_
         RemoveWalk walk;
         if (!device_work) build_without_visits(kept.size(), o);
         else if (algorithm == GBWT_HIP_REMOVE_REBUILD) {
-            const gbwt_hip_status st = rebuild(index, kept, o, stream.s);
+            st = rebuild(index, kept, o, stream.s);
             if (st != GBWT_HIP_OK) return st;
         } else remove_records_on_device(in, removed.data(), removed.size(), o, walk, stream.s);
         walk.removed_sequences = removed.size(); walk.removed_steps = in.visits - o.visits;
 
         const auto t_open = Clock::now();
-        std::unique_ptr<gbwt_hip_index> ix(new gbwt_hip_index);
-        ix->device = device;
-        ix->caps = (flags & GBWT_HIP_OPEN_GFA) ? (flags | GBWT_HIP_OPEN_EXTRACT) : flags;
-        ix->knobs = OpenKnobs::from_env();
-        HostIndex &h = ix->host;
-        h = index_from_records(o.data.data(), o.data.size(), o.starts.data(), o.starts.size(), o.alphabet_offset, o.alphabet_size, o.sequences, o.visits + o.sequences, hi.bidirectional);
-        if (hi.is_gbz) {
+        std::unique_ptr<gbwt_hip_index> ix = handle_from_build(o, hi.bidirectional, device, flags);
+        if (hi.is_gbz) {                                   // (the graph of the nodes the new records still visit)
             const auto t_graph = Clock::now();
-            bad = remove_graph(hi, h, meta);
-            if (bad) return refusal_status(bad);
+            bad = remove_graph(hi, ix->host, meta);
+            if (bad) return refusal_status(bad, "remove: ");
             metadata_ms += ms_since(t_graph);
         }
-        h.tags = std::move(meta.tags); h.gbz_tags = std::move(meta.gbz_tags);
-        if (meta.has_metadata) {
-            h.has_metadata = true; h.metadata_flags = meta.metadata_flags;
-            h.sample_count = meta.sample_count; h.haplotype_count = meta.haplotype_count; h.contig_count = meta.contig_count;
-            h.path_names = std::move(meta.path_names); h.sample_names = std::move(meta.sample_names); h.contig_names = std::move(meta.contig_names);
-            h.generic_phase_on_disk = meta.generic_phase_on_disk;
-        }
-        if (meta.is_gbz) {
-            h.is_gbz = true; h.has_translation = false; h.graph_nodes = meta.graph_nodes;
-            h.sequences_labels = std::move(meta.sequences_labels);
-        }
+        adopt_metadata(ix->host, std::move(meta));
 
         gbwt_hip_remove_info m{};
-        m.visits = o.visits; m.sequences = o.sequences; m.records = o.records; m.data_bytes = o.data.size(); m.peak_scratch_bytes = o.peak_scratch;
+        fill_build_counters(m, o);
         m.removed_sequences = walk.removed_sequences; m.removed_steps = walk.removed_steps;
-        m.algorithm_used = algorithm; m.removed = 1; m.rounds = o.rounds;
-        m.walk_ms = walk.walk_ms; m.decode_ms = walk.decode_ms; m.compact_ms = walk.compact_ms; m.edges_ms = o.edges_ms; m.encode_ms = o.encode_ms;
+        m.algorithm_used = algorithm; m.removed = 1;
+        m.walk_ms = walk.walk_ms; m.decode_ms = walk.decode_ms; m.compact_ms = walk.compact_ms;
         m.metadata_ms = metadata_ms;
-        const gbwt_hip_status st = open_host_index(std::move(ix), out, t_open);
+        st = open_host_index(std::move(ix), out, t_open);
         if (st != GBWT_HIP_OK) return st;
         m.open_ms = ms_since(t_open);
         (*out)->remove_info = m;
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the removal does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "the removal");
     }
     GBWT_HIP_GUARD_END
 }
 
 gbwt_hip_status gbwt_hip_last_remove_info(const gbwt_hip_index *ix, gbwt_hip_remove_info *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
-    *out = ix->remove_info;
-    return GBWT_HIP_OK;
+    return last_info(ix, out, &gbwt_hip_index::remove_info);
     GBWT_HIP_GUARD_END
 }
 

@@ -133,14 +133,7 @@ inline bool gfa_reference_samples(std::string_view line, std::string &value) {
     return false;
 }
 
-// The graph of a GBZ without a translation, as the loader leaves it: one label per potential node of the GBWT's alphabet
-inline void fill_gfa_graph(HostIndex &h, Strings &&labels, uint64_t graph_nodes) {
-    h.is_gbz = true; h.has_translation = false;
-    h.graph_nodes = graph_nodes;
-    h.sequences_labels = std::move(labels);
-    h.segment_names = Strings(); h.segment_starts.clear(); h.mapping_len = 0;
-}
-
+// (the graph of a GBZ without a translation: host_index.hpp, fill_gfa_graph)
 // The graph of a GBZ with a translation, as the loader leaves it: one label per node 1 .. mapping_len - 1 (empty where no path goes), the
 // names of the segments (empty likewise) and the first node of each
 inline void fill_gfa_translated_graph(HostIndex &h, Strings &&labels, uint64_t graph_nodes, Strings &&names, Words &&starts, uint64_t mapping_len) {

@@ -12,6 +12,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace gbwt_hip {
@@ -141,5 +142,26 @@ std::vector<std::pair<uint32_t, uint32_t>> decompress_endmarker(const HostIndex 
 HostIndex index_from_records(const uint8_t *data, uint64_t data_len, const uint64_t *starts, uint64_t n_records,
                              uint64_t alphabet_offset, uint64_t alphabet_size, uint64_t n_sequences, uint64_t size,
                              bool bidirectional);
+
+// The graph of a GBZ without a translation, as the loader leaves it: one label per potential node of the GBWT's alphabet
+inline void fill_gfa_graph(HostIndex &h, Strings &&labels, uint64_t graph_nodes) {
+    h.is_gbz = true; h.has_translation = false;
+    h.graph_nodes = graph_nodes;
+    h.sequences_labels = std::move(labels);
+    h.segment_names = Strings(); h.segment_starts.clear(); h.mapping_len = 0;
+}
+
+// What a maker of an index (from GFA, merge, removal) has assembled in `meta` beside the records, into the image made from the records:
+// the tags always, the metadata where meta has any, the graph (without a translation) where meta is a GBZ.  Everything else of `h` stays.
+inline void adopt_metadata(HostIndex &h, HostIndex &&meta) {
+    h.tags = std::move(meta.tags); h.gbz_tags = std::move(meta.gbz_tags);
+    if (meta.has_metadata) {
+        h.has_metadata = true; h.metadata_flags = meta.metadata_flags;
+        h.sample_count = meta.sample_count; h.haplotype_count = meta.haplotype_count; h.contig_count = meta.contig_count;
+        h.path_names = std::move(meta.path_names); h.sample_names = std::move(meta.sample_names); h.contig_names = std::move(meta.contig_names);
+        h.generic_phase_on_disk = meta.generic_phase_on_disk;
+    }
+    if (meta.is_gbz) fill_gfa_graph(h, std::move(meta.sequences_labels), meta.graph_nodes);
+}
 
 }  // namespace gbwt_hip

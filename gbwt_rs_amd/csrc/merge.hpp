@@ -8,6 +8,7 @@
 #include "build.hpp"
 #include "device_index.hpp"
 #include "lf_device.hpp"
+#include "merge_meta.hpp"
 
 namespace gbwt_hip {
 
@@ -69,6 +70,11 @@ __device__ __forceinline__ bool edge_offset_of(const DeviceIndex &ix, uint64_t v
 }
 
 }  // namespace record_access
+
+// A refusal of the host's part (merge_meta.hpp, remove_meta.hpp) as a status; prefix: "merge: " or "remove: "
+inline gbwt_hip_status refusal_status(const MergeRefusal &bad, const char *prefix) {
+    return fail(bad.kind == MergeRefusal::UNSUPPORTED ? GBWT_HIP_UNSUPPORTED : GBWT_HIP_INVALID_DATA, prefix + bad.what);
+}
 
 // An input as the kernels read it: the record bytes, starts and endmarker every handle keeps, and the header
 struct MergeInput {

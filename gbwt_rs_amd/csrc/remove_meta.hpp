@@ -132,10 +132,7 @@ inline MergeRefusal remove_graph(const HostIndex &in, const HostIndex &records, 
         }
         labels.offsets.push_back(labels.bytes.size());
     }
-    out.is_gbz = true; out.has_translation = false;
-    out.graph_nodes = nodes;
-    out.sequences_labels = std::move(labels);
-    out.segment_names = Strings(); out.segment_starts.clear(); out.mapping_len = 0;
+    fill_gfa_graph(out, std::move(labels), nodes);
     return bad;
 }
 

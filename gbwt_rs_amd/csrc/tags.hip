@@ -287,8 +287,7 @@ gbwt_hip_status tags_plan(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, cons
     } catch (const OutOfMemory &e) {
         return fail(GBWT_HIP_CAPACITY, e.what);
     } catch (const HipError &e) {
-        if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string("the tag plan does not fit in device memory: ") + e.what); }
-        return status_of(e);
+        return status_of(e, "the tag plan");
     }
 }
 
@@ -326,11 +325,6 @@ gbwt_hip_status gather_once(gbwt_hip_workspace *ws, const uint64_t *d_sa, uint64
     if (state.bad) return fail(GBWT_HIP_INVALID_DATA, "suffix array value out of range: the text has " + std::to_string(ws->tag_text_len) + " positions");
     if (runs) *runs = state.runs;
     return GBWT_HIP_OK;
-}
-
-gbwt_hip_status capacity_or_status(const HipError &e, const char *what) {
-    if (e.err == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GBWT_HIP_CAPACITY, std::string(what) + " does not fit in device memory: " + e.what); }
-    return status_of(e);
 }
 
 // first tab field = path id, last tab field = bases (read_names, src/bin/gbz-extract.rs:296-318)
@@ -386,7 +380,7 @@ gbwt_hip_status gbwt_hip_tags(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, 
     } catch (const OutOfMemory &e) {
         return fail(GBWT_HIP_CAPACITY, e.what);
     } catch (const HipError &e) {
-        return capacity_or_status(e, "the suffix array");
+        return status_of(e, "the suffix array");
     }
     GBWT_HIP_GUARD_END
 }
@@ -517,7 +511,7 @@ gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *ix, gbwt_hip_work
     } catch (const OutOfMemory &e) {
         return fail(GBWT_HIP_CAPACITY, e.what);
     } catch (const HipError &e) {
-        return capacity_or_status(e, "the batches of the tag array");
+        return status_of(e, "the batches of the tag array");
     }
     GBWT_HIP_GUARD_END
 }

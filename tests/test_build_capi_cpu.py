@@ -2,7 +2,6 @@
 shared record encoder (csrc/build_codec.hpp) on the host against the oracle's ByteCode / RLE."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 
 import oracle_lib as O
 from gbwt_rs_amd import _lib
+from test_merge_cpu import host_compiler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -114,14 +114,6 @@ def test_python_mirror_validates_before_it_calls(monkeypatch):
         G.GBWT.from_rows_device(_lib.Paths(), 1)                           # more rows than the struct holds
     for method in ("from_paths", "from_rows_device", "records", "save", "last_build_info"):
         assert callable(getattr(G.GBWT, method)), method
-
-
-def host_compiler():
-    for name in ("g++", "clang++", "c++"):
-        found = shutil.which(name)
-        if found:
-            return found
-    raise AssertionError("no host C++ compiler")
 
 
 def test_build_codec_against_the_oracle(tmp_path):

@@ -4,7 +4,6 @@ of its own under ASan + UBSan, and the resources of the parse kernels."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
@@ -14,6 +13,7 @@ import gfa_expect as X
 import kat
 import oracle_lib as O
 from gbwt_rs_amd import _lib
+from test_merge_cpu import host_compiler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXAMPLE, TRANSLATION = os.path.join(O.GOLDEN, "example.gfa"), os.path.join(O.GOLDEN, "translation.gfa")
@@ -86,14 +86,6 @@ def test_expected_reader_on_the_fixtures():
     with pytest.raises(X.Refused) as e:
         X.Expected(open(TRANSLATION, "rb").read())
     assert (e.value.line, e.value.status) == (2, X.UNSUPPORTED)
-
-
-def host_compiler():
-    for name in ("g++", "clang++", "c++"):
-        found = shutil.which(name)
-        if found:
-            return found
-    raise AssertionError("no host C++ compiler")
 
 
 def test_metadata_assembly_under_sanitizers(tmp_path):

@@ -5,7 +5,6 @@ import ctypes as C
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
@@ -15,6 +14,7 @@ import gfa_translate_expect as T
 import oracle_lib as O
 from gbwt_rs_amd import _lib
 from gbwt_rs_amd import synth as S
+from test_merge_cpu import host_compiler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXAMPLE, TRANSLATION = os.path.join(O.GOLDEN, "example.gfa"), os.path.join(O.GOLDEN, "translation.gfa")
@@ -61,14 +61,6 @@ def test_reader_modes():
         with pytest.raises(X.Refused) as e:
             T.Translated(bad, max_node=2)
         assert (e.value.line, e.value.status) == (line, status), bad
-
-
-def host_compiler():
-    for name in ("g++", "clang++", "c++"):
-        found = shutil.which(name)
-        if found:
-            return found
-    raise AssertionError("no host C++ compiler")
 
 
 def test_name_table_under_sanitizers(tmp_path):

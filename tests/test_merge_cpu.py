@@ -109,17 +109,22 @@ def host_compiler():
     raise AssertionError("no host C++ compiler")
 
 
-def test_merge_metadata_assembly_under_sanitizers(tmp_path):
-    """tests/cpp/merge_meta.cpp: merge_meta.hpp on the host, built with ASan + UBSan and run as a program; it checks itself and prints
-    one line per case."""
-    exe = tmp_path / "merge_meta"
+def sanitized_program(tmp_path, name, *more_sources):
+    """tests/cpp/<name>.cpp, built with ASan + UBSan and run as a program: ({first word of a line: its rest}, the lines); the last one is "done"."""
+    exe = tmp_path / name
     subprocess.run([host_compiler(), "-std=c++17", "-O2", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", _lib.CSRC,
-                    os.path.join(ROOT, "tests", "cpp", "merge_meta.cpp"), "-o", str(exe)], check=True)
+                    os.path.join(ROOT, "tests", "cpp", name + ".cpp"), *more_sources, "-ldl", "-lpthread", "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = out.stdout.splitlines()
     assert not any(line.startswith("FAIL") for line in lines), out.stdout
-    got = {line.split(" ", 1)[0]: line.split(" ", 1)[1] for line in lines if " " in line}
+    assert lines[-1] == "done"
+    return {line.split(" ", 1)[0]: line.split(" ", 1)[1] for line in lines if " " in line}, lines
+
+
+def test_merge_metadata_assembly_under_sanitizers(tmp_path):
+    """tests/cpp/merge_meta.cpp: merge_meta.hpp on the host; it checks itself and prints one line per case."""
+    got, _ = sanitized_program(tmp_path, "merge_meta")
     assert got["samples"] == "_gbwt_ref s1 s2 s3"                # a's in order, then those of b that a lacks, in b's order
     assert got["contigs"] == "chrA chrB chrC"
     assert got["paths"] == "0,0,0,0 1,0,1,0 1,1,2,5 2,1,1,0 3,2,1,0 1,0,2,0"     # b's with sample and contig ids remapped
@@ -130,7 +135,21 @@ def test_merge_metadata_assembly_under_sanitizers(tmp_path):
     assert got["tags"] == "source=x|reference_samples=r1 r2 r3|k=a|only_b=q"
     assert got["rs_only_b"] == "source=x|reference_samples=r9" and got["rs_absent"] == "source=x"
     assert got["labels"] == "3 ACG||T|GG" and got["conflict"] == "INVALID node 12" and got["translation"] == "UNSUPPORTED"
-    assert lines[-1] == "done"
+
+
+def test_adopt_metadata_under_sanitizers(tmp_path):
+    """tests/cpp/adopt_metadata.cpp: what a maker assembled beside the records, moved into the image made from the records (host_index.hpp)."""
+    got, _ = sanitized_program(tmp_path, "adopt_metadata", os.path.join(_lib.CSRC, "host_index.cpp"))
+    assert got["fresh.tags"] == " ; " and got["fresh.metadata"] == "0 flags 0 counts 0 0 0 generic 1 paths samples  contigs "
+    assert got["fresh.graph"] == "0 translation 0 nodes 0 labels  segments 0 0 0"
+    assert got["fresh.records"] == "0 sequences 0 alphabet 21 28 bidirectional 1 data 1 starts 2"
+    assert got["all.tags"] == "source=x|reference_samples=s1 ; source=y|k=v"
+    assert got["all.metadata"] == "1 flags 7 counts 2 3 1 generic 0 paths 0,0,0,0 1,0,1,0 1,0,2,7 samples s1|s2 contigs chr"
+    assert got["all.graph"] == "1 translation 0 nodes 3 labels A|CC|GGG segments 0 0 0"
+    for case, part in (("no_metadata", "metadata"), ("no_graph", "graph")):      # the part the assembled image lacks stays as index_from_records made it
+        for key in ("tags", "metadata", "graph"):
+            assert got[case + "." + key] == got[("fresh." if key == part else "all.") + key], (case, key)
+    assert all(got[case + ".records"] == got["fresh.records"] for case in ("all", "no_metadata", "no_graph"))
 
 
 def test_merge_kernels_compile_without_scratch():

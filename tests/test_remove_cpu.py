@@ -15,10 +15,8 @@ import merge_expect as MX
 import remove_expect as RX
 from gbwt_rs_amd import _lib
 from gbwt_rs_amd import synth as S
-from test_merge_cpu import host_compiler
+from test_merge_cpu import sanitized_program
 from test_synth import random_paths
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -118,14 +116,7 @@ def test_remove_metadata_assembly_under_sanitizers(tmp_path):
     """tests/cpp/remove_meta.cpp: remove_meta.hpp on the host, built with ASan + UBSan and run as a program; it prints one line per case.
     The refusals of a path id at or above the path count and of one that appears twice, which need a handle on the device, are checked
     here through the function the library calls for them (remove_check_ids) and end to end in tests/test_gpu_remove.py."""
-    exe = tmp_path / "remove_meta"
-    subprocess.run([host_compiler(), "-std=c++17", "-O2", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", _lib.CSRC,
-                    os.path.join(ROOT, "tests", "cpp", "remove_meta.cpp"), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = out.stdout.splitlines()
-    assert not any(line.startswith("FAIL") for line in lines), out.stdout
-    got = {line.split(" ", 1)[0]: line.split(" ", 1)[1] for line in lines if " " in line}
+    got, lines = sanitized_program(tmp_path, "remove_meta")
     assert got["ids_good"] == "1" and got["ids_none"] == "1"
     assert got["ids_high"].startswith("0 path id 6 ") and got["ids_twice"] == "0 path id 3 appears twice"
     assert got["some_samples"] == "_gbwt_ref s1 s3"                # s2 was used by a removed path alone; the rest keep their order
@@ -142,7 +133,6 @@ def test_remove_metadata_assembly_under_sanitizers(tmp_path):
     assert got["labels"] == "2 C||GG"                              # node 12 is no longer visited: its label is cleared
     assert got["labels_none"] == "0 0"
     assert got["translation"] == "UNSUPPORTED named"
-    assert lines[-1] == "done"
 
 
 def test_remove_kernels_compile_without_scratch():
