@@ -27,14 +27,14 @@ gbwt_hip_status gbwt_hip_workspace_create(const gbwt_hip_index *index, gbwt_hip_
     if (!index || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null argument");
     *out = nullptr;
     std::unique_ptr<gbwt_hip_workspace> ws(new gbwt_hip_workspace);
-    ws->nodes.may_spread = true;
-    ws->nodes.policy = vmm_policy_from_env();
+    ws->extract.nodes.may_spread = true;
+    ws->extract.nodes.policy = vmm_policy_from_env();
     ws->knobs = ExtractKnobs::from_env();
     ws->index = index;
     HIP_CHECK(hipSetDevice(index->device));
-    HIP_CHECK(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
-    for (auto &e : ws->ev) HIP_CHECK(hipEventCreate(&e));
-    ws->counters.reserve(4 * sizeof(uint32_t));
+    ws->stream.create(hipStreamNonBlocking);
+    ws->extract.ev.ensure();
+    ws->extract.counters.reserve(4 * sizeof(uint32_t));
     // optional overrides for experiments / tests (same meaning as gbwt_hip_workspace_tune)
     if (const char *v = std::getenv("GBWT_HIP_WALK_MODE")) { int m = std::atoi(v); if (m >= 0 && m <= 3) ws->walk_mode = static_cast<uint32_t>(m); }
     if (const char *v = std::getenv("GBWT_HIP_PATHS_PER_WAVE")) { int p = std::atoi(v); if (p >= 0 && p <= 64) ws->paths_per_wave = static_cast<uint32_t>(p); }
@@ -54,7 +54,7 @@ gbwt_hip_status gbwt_hip_workspace_tune(gbwt_hip_workspace *ws, uint32_t walk_mo
     GBWT_HIP_GUARD_END
 }
 
-void *gbwt_hip_workspace_stream(gbwt_hip_workspace *ws) { return ws ? static_cast<void *>(ws->stream) : nullptr; }
+void *gbwt_hip_workspace_stream(gbwt_hip_workspace *ws) { return ws ? static_cast<void *>(ws->stream.s) : nullptr; }
 
 gbwt_hip_status gbwt_hip_extract_device(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const uint64_t *seq_ids, uint64_t n,
                                         gbwt_hip_paths *out) {
@@ -71,23 +71,23 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
     // GBWT::sequence: id >= sequences -> no iterator (src/gbwt.rs:254-256).  "Not found" is a value here as well: such an id
     // gets an empty row (the kernels test the id), the rest of the batch is extracted; callers tell None from an empty
     // sequence by id < sequences.
-    ws->extract_cached = false;
-    ws->timed = false; ws->last_n = 0; ws->last_total = 0;   // what copy_result / path_sums / copy_path trust: set again only when this call succeeds
+    ws->extract.memo.drop();
+    ws->extract.timed = false; ws->extract.last_n = 0; ws->extract.last_total = 0;   // what copy_result / path_sums / copy_path trust: set again only when this call succeeds
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
-        ws->seq_ids.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
-        ws->lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
-        ws->offsets.reserve((n + 1) * sizeof(uint64_t));
-        ws->head.reserve(std::max<uint64_t>(n, 1) * sizeof(uint32_t));
+        ws->extract.seq_ids.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+        ws->extract.lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+        ws->extract.offsets.reserve((n + 1) * sizeof(uint64_t));
+        ws->extract.head.reserve(std::max<uint64_t>(n, 1) * sizeof(uint32_t));
         size_t temp_bytes = n ? scan_temp_bytes(n) : 0;
-        ws->scan_temp.reserve(std::max<size_t>(temp_bytes, 16));
+        ws->scratch.scan_temp.reserve(std::max<size_t>(temp_bytes, 16));
         // Pool bound for distinct ids: all sequences together hold size - sequences nodes
         // (src/gbwt.rs:108-122), and every path wastes less than one block.
         const uint64_t all_nodes = ix->host.size >= ix->host.sequences ? ix->host.size - ix->host.sequences : 0;
         uint64_t pool_blocks = all_nodes / POOL_BLOCK_NODES + n + 1;
-        HIP_CHECK(hipEventRecord(ws->ev[3], s));   // everything the extraction puts on the stream lies between ev[3] and ev[2]
-        if (n) HIP_CHECK(hipMemcpyAsync(ws->seq_ids.ptr, seq_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipEventRecord(ws->extract.ev[3], s));   // everything the extraction puts on the stream lies between ev[3] and ev[2]
+        if (n) HIP_CHECK(hipMemcpyAsync(ws->extract.seq_ids.ptr, seq_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         const ExtractKnobs &knobs = ws->knobs;
         if (n && ix->dev.seq_len && ws->walk_mode == WALK_TWO_STEP && knobs.direct != 0) {
             // Lengths known: offsets first, then every lane writes into its row; in a bidirectional index two walkers per
@@ -98,12 +98,12 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
             // An index without samples (GBWT_HIP_SAMPLE_INTERVAL=0, GBWT_HIP_SEGMENTS=0) cannot cut: the last part is the whole row there.
             const bool can_cut = ix->dev.samples != nullptr && ix->max_samples > 0 && knobs.segments != 0 && n <= 0x7FFFFFFFull;
             if (parts > 1 && !can_cut && part + 1 < parts) {
-                HIP_CHECK(hipMemsetAsync(ws->offsets.ptr, 0, (n + 1) * sizeof(uint64_t), s));
-                ws->nodes.reserve(sizeof(uint32_t));
-                HIP_CHECK(hipEventRecord(ws->ev[0], s)); HIP_CHECK(hipEventRecord(ws->ev[1], s)); HIP_CHECK(hipEventRecord(ws->ev[2], s));
+                HIP_CHECK(hipMemsetAsync(ws->extract.offsets.ptr, 0, (n + 1) * sizeof(uint64_t), s));
+                ws->extract.nodes.reserve(sizeof(uint32_t));
+                HIP_CHECK(hipEventRecord(ws->extract.ev[0], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[1], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
                 HIP_CHECK(hipStreamSynchronize(s));
-                ws->timed = true; ws->last_n = n; ws->last_total = 0;
-                out->d_offsets = ws->offsets.as<uint64_t>(); out->d_nodes = ws->nodes.as<uint32_t>(); out->total = 0; out->n = n;
+                ws->extract.timed = true; ws->extract.last_n = n; ws->extract.last_total = 0;
+                out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = 0; out->n = n;
                 return GBWT_HIP_OK;
             }
             const bool parted = parts > 1 && can_cut;
@@ -124,11 +124,11 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
             const bool all_valid = ids_valid && ix->uniform_len != 0 && !parted;
             const bool fused_offsets = all_valid && knobs.fused_offsets != 0;
             // lengths, offsets and extremes: one launch for the batch sizes there are, else a memset and three
-            if (!fused_offsets && !launch_row_offsets(strided, ws->seq_ids.as<uint64_t>(), n, ws->lengths.as<uint64_t>(), ws->offsets.as<uint64_t>(), ws->counters.as<uint32_t>(), s)) {
-                HIP_CHECK(hipMemsetAsync(ws->counters.ptr, 0, 4 * sizeof(uint32_t), s));
-                if (parted) launch_part_lengths(strided, ws->seq_ids.as<uint64_t>(), n, ws->lengths.as<uint64_t>(), ws->counters.as<uint32_t>(), s);
-                else launch_gather_lengths(ix->dev.seq_len, ix->dev.n_sequences, ws->seq_ids.as<uint64_t>(), n, ws->lengths.as<uint64_t>(), ws->counters.as<uint32_t>(), s);
-                launch_scan(ws->lengths.as<uint64_t>(), ws->offsets.as<uint64_t>(), n, ws->scan_temp.ptr, temp_bytes, s);
+            if (!fused_offsets && !launch_row_offsets(strided, ws->extract.seq_ids.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>(), ws->extract.offsets.as<uint64_t>(), ws->extract.counters.as<uint32_t>(), s)) {
+                HIP_CHECK(hipMemsetAsync(ws->extract.counters.ptr, 0, 4 * sizeof(uint32_t), s));
+                if (parted) launch_part_lengths(strided, ws->extract.seq_ids.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>(), ws->extract.counters.as<uint32_t>(), s);
+                else launch_gather_lengths(ix->dev.seq_len, ix->dev.n_sequences, ws->extract.seq_ids.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>(), ws->extract.counters.as<uint32_t>(), s);
+                launch_scan(ws->extract.lengths.as<uint64_t>(), ws->extract.offsets.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, temp_bytes, s);
             }
             uint64_t total = 0;
             uint32_t extremes[2] = {0, 0};   // the longest row, ~(the shortest)
@@ -143,7 +143,7 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
             // workspace does not wait for the total of its row lengths either -- 20 us of a round trip in front of a walk of 0.6 ms: the walk
             // is launched into the rows that are there with their size as `capacity`, every workgroup looks at offsets[n] first, and
             // if the rows were too small (the first request of its size) the host makes them and launches again.  One host wait per request.
-            const uint64_t capacity = ws->nodes.bytes / sizeof(uint32_t);
+            const uint64_t capacity = ws->extract.nodes.bytes / sizeof(uint32_t);
             const bool defer = knobs.defer_total != 0 && !all_valid && can_cut && ids_valid && common != 0 && capacity != 0;
             if (all_valid) {
                 // every row has the same, known length: total and extremes without a round trip to the device (the offsets are
@@ -151,19 +151,19 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
                 total = n * static_cast<uint64_t>(ix->uniform_len);
                 extremes[0] = ix->uniform_len; extremes[1] = ~ix->uniform_len;
             } else if (defer) {
-                if (!ws->pinned_words) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ws->pinned_words), 4 * sizeof(uint64_t)));
-                HIP_CHECK(hipMemcpyAsync(ws->pinned_words, ws->offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                ws->extract.pinned_words.ensure();
+                HIP_CHECK(hipMemcpyAsync(ws->extract.pinned_words.p, ws->extract.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
                 total = capacity;                                  // (stands in until the wait at the end)
                 extremes[0] = 1; extremes[1] = ~1u;                // (a row may have nodes: the walk is a segmented one)
             } else {
-                HIP_CHECK(hipMemcpyAsync(&total, ws->offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipMemcpyAsync(extremes, ws->counters.ptr, sizeof(extremes), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipMemcpyAsync(&total, ws->extract.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipMemcpyAsync(extremes, ws->extract.counters.ptr, sizeof(extremes), hipMemcpyDeviceToHost, s));
                 HIP_CHECK(hipStreamSynchronize(s));
             }
             const uint32_t max_len = extremes[0];
-            ws->nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
+            ws->extract.nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
             WalkArgs a{};
-            a.seq_ids = ws->seq_ids.as<uint64_t>(); a.n = n;
+            a.seq_ids = ws->extract.seq_ids.as<uint64_t>(); a.n = n;
             a.mode = ws->walk_mode;
             // many walkers per row when the index has sequence samples (GBWT_HIP_SEGMENTS=0: one walker per end instead)
             const bool segmented = ix->dev.samples != nullptr && max_len > 0 && n <= 0x7FFFFFFFull && ix->max_samples > 0 && knobs.segments != 0;   // (the walker order sorts 32-bit row numbers)
@@ -185,16 +185,16 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
             } else if (segmented) {
                 // rows with different numbers of segments: walkers segment by segment over the rows that have the segment (rows sorted by their segment count)
                 const size_t ob = walker_order_temp_bytes(n), sb = scan_temp_bytes(a.segments);
-                ws->order_keys.reserve(2 * n * sizeof(uint32_t)); ws->order_rows.reserve(2 * n * sizeof(uint32_t));
-                ws->order_counts.reserve(a.segments * sizeof(uint64_t)); ws->order_level.reserve((a.segments + 1ull) * sizeof(uint64_t));
-                ws->order_temp.reserve(std::max<size_t>(std::max(ob, sb), 16));
+                ws->extract.order_keys.reserve(2 * n * sizeof(uint32_t)); ws->extract.order_rows.reserve(2 * n * sizeof(uint32_t));
+                ws->extract.order_counts.reserve(a.segments * sizeof(uint64_t)); ws->extract.order_level.reserve((a.segments + 1ull) * sizeof(uint64_t));
+                ws->extract.order_temp.reserve(std::max<size_t>(std::max(ob, sb), 16));
                 const uint32_t *sorted_rows = nullptr;
-                launch_walker_order(strided, ws->seq_ids.as<uint64_t>(), n, a.segments, ws->order_keys.as<uint32_t>(), ws->order_rows.as<uint32_t>(),
-                                    ws->order_counts.as<uint64_t>(), ws->order_level.as<uint64_t>(), ws->order_temp.ptr, ob, &sorted_rows, s);
-                launch_scan(ws->order_counts.as<uint64_t>(), ws->order_level.as<uint64_t>(), a.segments, ws->order_temp.ptr, sb, s);
-                HIP_CHECK(hipMemcpyAsync(&walkers, ws->order_level.as<uint64_t>() + a.segments, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                launch_walker_order(strided, ws->extract.seq_ids.as<uint64_t>(), n, a.segments, ws->extract.order_keys.as<uint32_t>(), ws->extract.order_rows.as<uint32_t>(),
+                                    ws->extract.order_counts.as<uint64_t>(), ws->extract.order_level.as<uint64_t>(), ws->extract.order_temp.ptr, ob, &sorted_rows, s);
+                launch_scan(ws->extract.order_counts.as<uint64_t>(), ws->extract.order_level.as<uint64_t>(), a.segments, ws->extract.order_temp.ptr, sb, s);
+                HIP_CHECK(hipMemcpyAsync(&walkers, ws->extract.order_level.as<uint64_t>() + a.segments, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
                 HIP_CHECK(hipStreamSynchronize(s));
-                a.sorted_rows = sorted_rows; a.level = ws->order_level.as<uint64_t>(); a.walkers = walkers;
+                a.sorted_rows = sorted_rows; a.level = ws->extract.order_level.as<uint64_t>(); a.walkers = walkers;
             }
             // many walkers: the walk is a throughput problem, full waves; few walkers (one or two per row): latency, and
             // about one workgroup per four SIMDs keeps every workgroup resident (32 KB of LDS each)
@@ -206,7 +206,7 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
             // many walkers per CU: a helper that polls less leaves more issue slots and LDS cycles to them (6 until the packed half-blocks
             // made the walkers faster: 3 / 4 / 6 / 8 / 10 naps = 4.30 / 4.31 / 4.35 / 4.42 / 4.51 ms)
             a.helper_naps = knobs.helper_naps >= 0 ? static_cast<uint32_t>(knobs.helper_naps) : (segmented ? 4u : 1u);
-            a.out_nodes = ws->nodes.as<uint32_t>(); a.out_offsets = ws->offsets.as<uint64_t>();
+            a.out_nodes = ws->extract.nodes.as<uint32_t>(); a.out_offsets = ws->extract.offsets.as<uint64_t>();
             a.xcd_map = knobs.xcd_map >= 0 ? (knobs.xcd_map ? 1u : 0u) : (segmented ? 1u : 0u);
             a.uniform_loop = knobs.uniform_loop >= 0 ? (knobs.uniform_loop ? 1u : 0u) : 1u;
             // (2: single steps on the two-step descriptors + packed half-blocks: what a lean handle has -- and GBWT_HIP_CATCH_UP=2 on any)
@@ -231,39 +231,39 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
             a.debug = knobs.debug;                               // timing experiments only, see WalkArgs::debug
             a.both_ends = (ix->orientation_pairs && knobs.both_ends != 0) ? 1u : 0u;
             a.capacity = defer ? capacity : 0;
-            if (fused_offsets) { a.uniform_len = ix->uniform_len; a.fill_offsets = ws->offsets.as<uint64_t>(); }
-            HIP_CHECK(hipEventRecord(ws->ev[0], s));
+            if (fused_offsets) { a.uniform_len = ix->uniform_len; a.fill_offsets = ws->extract.offsets.as<uint64_t>(); }
+            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s));
             if (!parted || (total != 0 && walkers != 0)) launch_walk(dev, a, s);   // (a part of nothing but empty stretches: no walkers)
-            HIP_CHECK(hipEventRecord(ws->ev[1], s));
-            HIP_CHECK(hipEventRecord(ws->ev[2], s));
+            HIP_CHECK(hipEventRecord(ws->extract.ev[1], s));
+            HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
             HIP_CHECK(hipStreamSynchronize(s));
             HIP_CHECK(hipGetLastError());
             if (defer) {
-                total = ws->pinned_words[0];
+                total = ws->extract.pinned_words.p[0];
                 if (total > capacity) {                              // the rows were too small and nobody walked: make them, walk
-                    ws->nodes.reserve(total * sizeof(uint32_t));
-                    a.out_nodes = ws->nodes.as<uint32_t>(); a.capacity = 0;
-                    HIP_CHECK(hipEventRecord(ws->ev[0], s));
+                    ws->extract.nodes.reserve(total * sizeof(uint32_t));
+                    a.out_nodes = ws->extract.nodes.as<uint32_t>(); a.capacity = 0;
+                    HIP_CHECK(hipEventRecord(ws->extract.ev[0], s));
                     if (walkers != 0) launch_walk(dev, a, s);
-                    HIP_CHECK(hipEventRecord(ws->ev[1], s));
-                    HIP_CHECK(hipEventRecord(ws->ev[2], s));
+                    HIP_CHECK(hipEventRecord(ws->extract.ev[1], s));
+                    HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
                     HIP_CHECK(hipStreamSynchronize(s));
                     HIP_CHECK(hipGetLastError());
                 }
             }
-            ws->timed = true; ws->last_n = n; ws->last_total = total;
-            if (!parted) { ws->extract_key.assign(seq_ids, seq_ids + n); ws->extract_cached = true; }   // (gbwt_hip_extract's fill call asks for whole rows)
-            out->d_offsets = ws->offsets.as<uint64_t>(); out->d_nodes = ws->nodes.as<uint32_t>(); out->total = total; out->n = n;
+            ws->extract.timed = true; ws->extract.last_n = n; ws->extract.last_total = total;
+            if (!parted) ws->extract.memo.store({{seq_ids, n * sizeof(uint64_t)}}, {});   // (gbwt_hip_extract's fill call asks for whole rows)
+            out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = total; out->n = n;
             return GBWT_HIP_OK;
         }
         if (n == 0) {                                        // nothing asked for: an empty CSR, whatever the handle holds
-            HIP_CHECK(hipMemsetAsync(ws->offsets.ptr, 0, sizeof(uint64_t), s));
-            ws->nodes.reserve(sizeof(uint32_t));
-            HIP_CHECK(hipEventRecord(ws->ev[0], s)); HIP_CHECK(hipEventRecord(ws->ev[1], s)); HIP_CHECK(hipEventRecord(ws->ev[2], s));
+            HIP_CHECK(hipMemsetAsync(ws->extract.offsets.ptr, 0, sizeof(uint64_t), s));
+            ws->extract.nodes.reserve(sizeof(uint32_t));
+            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[1], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
             HIP_CHECK(hipStreamSynchronize(s));
-            ws->timed = true; ws->last_n = 0; ws->last_total = 0;
-            ws->extract_key.clear(); ws->extract_cached = true;
-            out->d_offsets = ws->offsets.as<uint64_t>(); out->d_nodes = ws->nodes.as<uint32_t>(); out->total = 0; out->n = 0;
+            ws->extract.timed = true; ws->extract.last_n = 0; ws->extract.last_total = 0;
+            ws->extract.memo.store({{nullptr, 0}}, {});
+            out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = 0; out->n = 0;
             return GBWT_HIP_OK;
         }
         if (ix->lean_extract) return fail(GBWT_HIP_UNSUPPORTED, "this handle was opened for extraction only and has given its raw descriptors back: the pool-output walk modes need GBWT_HIP_OPEN_ALL");
@@ -271,12 +271,12 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
         // header says for rows that cannot be cut, the LAST part is the whole row and every earlier part is n empty rows -- never the whole
         // row from every part (a gather of parts would then hold every row `parts` times).
         if (parts > 1 && part + 1 < parts) {
-            HIP_CHECK(hipMemsetAsync(ws->offsets.ptr, 0, (n + 1) * sizeof(uint64_t), s));
-            ws->nodes.reserve(sizeof(uint32_t));
-            HIP_CHECK(hipEventRecord(ws->ev[0], s)); HIP_CHECK(hipEventRecord(ws->ev[1], s)); HIP_CHECK(hipEventRecord(ws->ev[2], s));
+            HIP_CHECK(hipMemsetAsync(ws->extract.offsets.ptr, 0, (n + 1) * sizeof(uint64_t), s));
+            ws->extract.nodes.reserve(sizeof(uint32_t));
+            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[1], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
             HIP_CHECK(hipStreamSynchronize(s));
-            ws->timed = true; ws->last_n = n; ws->last_total = 0;
-            out->d_offsets = ws->offsets.as<uint64_t>(); out->d_nodes = ws->nodes.as<uint32_t>(); out->total = 0; out->n = n;
+            ws->extract.timed = true; ws->extract.last_n = n; ws->extract.last_total = 0;
+            out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = 0; out->n = n;
             return GBWT_HIP_OK;
         }
         uint32_t flags = 0;
@@ -284,12 +284,12 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
         const DeviceIndex dev = ws->walk_mode == WALK_TWO_STEP ? with_cblocks(ix) : ix->dev;   // the pool-output kernel walks on the full-width two-step blocks
         for (int attempt = 0; attempt < 8; attempt++) {
             if (pool_blocks >= POOL_NONE) return fail(GBWT_HIP_UNSUPPORTED, "path pool would exceed 2^32 blocks");
-            ws->pool.reserve(pool_blocks * POOL_BLOCK_NODES * sizeof(uint32_t));
-            ws->next.reserve(pool_blocks * sizeof(uint32_t));
-            a.seq_ids = ws->seq_ids.as<uint64_t>(); a.n = n;
-            a.pool = ws->pool.as<uint32_t>(); a.next = ws->next.as<uint32_t>(); a.pool_blocks = static_cast<uint32_t>(pool_blocks);
-            a.counter = ws->counters.as<uint32_t>(); a.flags = ws->counters.as<uint32_t>() + 1;
-            a.head = ws->head.as<uint32_t>(); a.lengths = ws->lengths.as<uint64_t>();
+            ws->extract.pool.reserve(pool_blocks * POOL_BLOCK_NODES * sizeof(uint32_t));
+            ws->extract.next.reserve(pool_blocks * sizeof(uint32_t));
+            a.seq_ids = ws->extract.seq_ids.as<uint64_t>(); a.n = n;
+            a.pool = ws->extract.pool.as<uint32_t>(); a.next = ws->extract.next.as<uint32_t>(); a.pool_blocks = static_cast<uint32_t>(pool_blocks);
+            a.counter = ws->extract.counters.as<uint32_t>(); a.flags = ws->extract.counters.as<uint32_t>() + 1;
+            a.head = ws->extract.head.as<uint32_t>(); a.lengths = ws->extract.lengths.as<uint64_t>();
             a.mode = ws->walk_mode; a.small_record = ws->small_record;
             // automatic: the walk is latency-bound and every lane of a wave runs the same instructions whether it owns a
             // sequence or not, so owners per wave cost nothing; at least 32 measured best (fewer, fuller waves keep the walks
@@ -299,12 +299,12 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
             a.pack16 = ix->stats.max_record_len < 65536 ? 1u : 0u;
             a.helper_lanes = 64u;
             a.wide_addresses = knobs.wide_addresses ? 1u : 0u;
-            HIP_CHECK(hipMemsetAsync(ws->counters.ptr, 0, 4 * sizeof(uint32_t), s));
-            HIP_CHECK(hipEventRecord(ws->ev[0], s));
+            HIP_CHECK(hipMemsetAsync(ws->extract.counters.ptr, 0, 4 * sizeof(uint32_t), s));
+            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s));
             launch_walk(dev, a, s);
-            HIP_CHECK(hipEventRecord(ws->ev[1], s));
+            HIP_CHECK(hipEventRecord(ws->extract.ev[1], s));
             HIP_CHECK(hipMemcpyAsync(&flags, a.flags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            launch_scan(a.lengths, ws->offsets.as<uint64_t>(), n, ws->scan_temp.ptr, temp_bytes, s);
+            launch_scan(a.lengths, ws->extract.offsets.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, temp_bytes, s);
             HIP_CHECK(hipStreamSynchronize(s));
             HIP_CHECK(hipGetLastError());
             if (!(flags & FLAG_POOL_OVERFLOW)) break;
@@ -312,18 +312,18 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
         }
         if (flags & FLAG_POOL_OVERFLOW) return fail(GBWT_HIP_DEVICE_ERROR, "path pool overflow");
         uint64_t total = 0;
-        HIP_CHECK(hipMemcpyAsync(&total, ws->offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&total, ws->extract.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        ws->nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
-        launch_compact(a, ws->offsets.as<uint64_t>(), ws->nodes.as<uint32_t>(), s);
-        HIP_CHECK(hipEventRecord(ws->ev[2], s));
+        ws->extract.nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
+        launch_compact(a, ws->extract.offsets.as<uint64_t>(), ws->extract.nodes.as<uint32_t>(), s);
+        HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
         HIP_CHECK(hipStreamSynchronize(s));
         HIP_CHECK(hipGetLastError());
-        ws->timed = true;
-        ws->last_n = n; ws->last_total = total;
-        ws->extract_key.assign(seq_ids, seq_ids + n); ws->extract_cached = true;
-        out->d_offsets = ws->offsets.as<uint64_t>();
-        out->d_nodes = ws->nodes.as<uint32_t>();
+        ws->extract.timed = true;
+        ws->extract.last_n = n; ws->extract.last_total = total;
+        ws->extract.memo.store({{seq_ids, n * sizeof(uint64_t)}}, {});
+        out->d_offsets = ws->extract.offsets.as<uint64_t>();
+        out->d_nodes = ws->extract.nodes.as<uint32_t>();
         out->total = total;
         out->n = n;
         return GBWT_HIP_OK;
@@ -414,8 +414,8 @@ gbwt_hip_status gbwt_hip_extract(const gbwt_hip_index *ix, gbwt_hip_workspace *w
     if (!out_offsets || !total) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     gbwt_hip_paths p{};
     // the fill call after a size query (or after gbwt_hip_extract_device) with the same ids: the rows are still in the workspace
-    if (ix && ws && ws->index == ix && ws->extract_cached && ws->extract_key.size() == n && (n == 0 || (seq_ids && std::memcmp(ws->extract_key.data(), seq_ids, n * sizeof(uint64_t)) == 0))) {
-        p.d_offsets = ws->offsets.as<uint64_t>(); p.d_nodes = ws->nodes.as<uint32_t>(); p.total = ws->last_total; p.n = n;
+    if (ix && ws && ws->index == ix && ws->extract.memo.matches({{seq_ids, n * sizeof(uint64_t)}}, {})) {
+        p.d_offsets = ws->extract.offsets.as<uint64_t>(); p.d_nodes = ws->extract.nodes.as<uint32_t>(); p.total = ws->extract.last_total; p.n = n;
     } else {
         gbwt_hip_status st = gbwt_hip_extract_device(ix, ws, seq_ids, n, &p);
         if (st != GBWT_HIP_OK) return st;
@@ -447,28 +447,28 @@ gbwt_hip_status gbwt_hip_extract_paths(const gbwt_hip_index *ix, gbwt_hip_worksp
 
 gbwt_hip_status gbwt_hip_copy_result(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, uint64_t *out_offsets, uint32_t *out_nodes, uint64_t capacity) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ix || !ws || ws->index != ix || !ws->timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
+    if (!ix || !ws || ws->index != ix || !ws->extract.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
     if (!out_offsets && !out_nodes) return fail(GBWT_HIP_BAD_ARGUMENT, "null outputs");
     HIP_CHECK(hipSetDevice(ix->device));
-    if (out_offsets) HIP_CHECK(hipMemcpy(out_offsets, ws->offsets.ptr, (ws->last_n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (out_offsets) HIP_CHECK(hipMemcpy(out_offsets, ws->extract.offsets.ptr, (ws->extract.last_n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (out_nodes) {
-        if (capacity < ws->last_total) return fail(GBWT_HIP_CAPACITY, "output capacity " + std::to_string(capacity) + " < " + std::to_string(ws->last_total));
-        if (ws->last_total) copy_to_host(ws, out_nodes, ws->nodes.ptr, ws->last_total * sizeof(uint32_t));
+        if (capacity < ws->extract.last_total) return fail(GBWT_HIP_CAPACITY, "output capacity " + std::to_string(capacity) + " < " + std::to_string(ws->extract.last_total));
+        if (ws->extract.last_total) copy_to_host(ws, out_nodes, ws->extract.nodes.ptr, ws->extract.last_total * sizeof(uint32_t));
     }
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
 
 static gbwt_hip_status path_sums(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, uint64_t *out_sums, uint64_t n, bool hashed) {
-    if (!ix || !ws || ws->index != ix || !ws->timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
-    if (n != ws->last_n || (n && !out_sums)) return fail(GBWT_HIP_BAD_ARGUMENT, "n does not match the last extraction");
+    if (!ix || !ws || ws->index != ix || !ws->extract.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
+    if (n != ws->extract.last_n || (n && !out_sums)) return fail(GBWT_HIP_BAD_ARGUMENT, "n does not match the last extraction");
     if (n == 0) return GBWT_HIP_OK;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        ws->out_a.reserve(n * sizeof(uint64_t));
-        launch_path_sums(ws->offsets.as<uint64_t>(), ws->nodes.as<uint32_t>(), n, ws->out_a.as<uint64_t>(), hashed, ws->stream);
+        ws->query.out_a.reserve(n * sizeof(uint64_t));
+        launch_path_sums(ws->extract.offsets.as<uint64_t>(), ws->extract.nodes.as<uint32_t>(), n, ws->query.out_a.as<uint64_t>(), hashed, ws->stream);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out_sums, ws->out_a.ptr, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        HIP_CHECK(hipMemcpyAsync(out_sums, ws->query.out_a.ptr, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
         HIP_CHECK(hipStreamSynchronize(ws->stream));
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
@@ -491,15 +491,15 @@ gbwt_hip_status gbwt_hip_path_hashes(const gbwt_hip_index *ix, gbwt_hip_workspac
 gbwt_hip_status gbwt_hip_copy_path(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, uint64_t k, uint32_t *out_nodes,
                                    uint64_t capacity, uint64_t *len) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ix || !ws || ws->index != ix || !ws->timed || !len) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
-    if (k >= ws->last_n) return fail(GBWT_HIP_BAD_ARGUMENT, "row out of range");
+    if (!ix || !ws || ws->index != ix || !ws->extract.timed || !len) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
+    if (k >= ws->extract.last_n) return fail(GBWT_HIP_BAD_ARGUMENT, "row out of range");
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         uint64_t range[2];
-        HIP_CHECK(hipMemcpy(range, ws->offsets.as<uint64_t>() + k, sizeof(range), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(range, ws->extract.offsets.as<uint64_t>() + k, sizeof(range), hipMemcpyDeviceToHost));
         *len = range[1] - range[0];
         uint64_t count = std::min(*len, capacity);
-        if (count && out_nodes) HIP_CHECK(hipMemcpy(out_nodes, ws->nodes.as<uint32_t>() + range[0], count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (count && out_nodes) HIP_CHECK(hipMemcpy(out_nodes, ws->extract.nodes.as<uint32_t>() + range[0], count * sizeof(uint32_t), hipMemcpyDeviceToHost));
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         return status_of(e);
@@ -509,9 +509,9 @@ gbwt_hip_status gbwt_hip_copy_path(const gbwt_hip_index *ix, gbwt_hip_workspace 
 
 gbwt_hip_status gbwt_hip_last_kernel_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *total_ms) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed extraction on this workspace");
+    if (!ws || !ws->extract.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed extraction on this workspace");
     float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, ws->ev[0], ws->ev[1]) != hipSuccess || hipEventElapsedTime(&b, ws->ev[3], ws->ev[2]) != hipSuccess)
+    if (hipEventElapsedTime(&a, ws->extract.ev[0], ws->extract.ev[1]) != hipSuccess || hipEventElapsedTime(&b, ws->extract.ev[3], ws->extract.ev[2]) != hipSuccess)
         return fail(GBWT_HIP_DEVICE_ERROR, "hipEventElapsedTime failed");
     if (walk_ms) *walk_ms = a;
     if (total_ms) *total_ms = b;

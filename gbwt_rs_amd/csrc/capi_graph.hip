@@ -12,21 +12,15 @@ namespace {
 
 // stream, events and the pinned word of one build
 struct BuildScratch {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Stream stream;
+    EventSet<2> ev;
     uint32_t *pinned = nullptr;
-    BuildScratch() {
-        HIP_CHECK(hipStreamCreate(&stream));
-        for (auto &e : ev) HIP_CHECK(hipEventCreate(&e));
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&pinned), 4 * sizeof(uint32_t)));
-    }
+    BuildScratch() { HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&pinned), 4 * sizeof(uint32_t))); }
     BuildScratch(const BuildScratch &) = delete;
     BuildScratch &operator=(const BuildScratch &) = delete;
     ~BuildScratch() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        (void)hipStreamSynchronize(stream);
         if (pinned) (void)hipHostFree(pinned);
-        if (stream) (void)hipStreamDestroy(stream);
     }
     void begin() { HIP_CHECK(hipEventRecord(ev[0], stream)); }
     // waits for the stream; milliseconds since begin()
@@ -42,7 +36,7 @@ struct BuildScratch {
 
 // The components of a handle, made once by the first call that needs them (any thread).  A failure marks nothing: the next call tries again.
 void ensure_components(const gbwt_hip_index *ix) {
-    ix->components_built.ensure([ix]() {
+    ix->components.built.ensure([ix]() {
         HIP_CHECK(hipSetDevice(ix->device));
         const DeviceIndex &d = ix->dev;
         ComponentGeometry g{0, 0};
@@ -56,8 +50,8 @@ void ensure_components(const gbwt_hip_index *ix) {
         BuildScratch b;
         DeviceBuffer changed;
         changed.reserve(sizeof(uint32_t));
-        ix->comp_of.reserve(std::max<uint64_t>(slots, 4) * sizeof(uint32_t));
-        uint32_t *label = ix->comp_of.as<uint32_t>();
+        ix->components.of.reserve(std::max<uint64_t>(slots, 4) * sizeof(uint32_t));
+        uint32_t *label = ix->components.of.as<uint32_t>();
         // 1. labels: hook passes over the records, jump passes over the labels in between, until a hook pass changes nothing
         const auto pass = [&](bool hook) {
             HIP_CHECK(hipMemsetAsync(changed.ptr, 0, sizeof(uint32_t), b.stream));
@@ -74,7 +68,7 @@ void ensure_components(const gbwt_hip_index *ix) {
             while (pass(false)) {}
         // 2. component numbers, CSR, path components
         uint64_t components = 0, nodes = 0;
-        ix->comp_paths.reserve(std::max<uint64_t>(paths, 4) * sizeof(uint32_t));
+        ix->components.paths.reserve(std::max<uint64_t>(paths, 4) * sizeof(uint32_t));
         b.begin();
         if (slots != 0) {
             DeviceBuffer first, flag, rank, key, value, temp, counts;
@@ -90,37 +84,37 @@ void ensure_components(const gbwt_hip_index *ix) {
             HIP_CHECK(hipStreamSynchronize(b.stream));
             components = static_cast<uint64_t>(b.pinned[0]) + b.pinned[1];
             times.shape_launches += 5;
-            ix->comp_offsets.reserve((components + 1) * sizeof(uint64_t));
+            ix->components.offsets.reserve((components + 1) * sizeof(uint64_t));
             counts.reserve(std::max<uint64_t>(components, 1) * sizeof(uint64_t));
             DeviceBuffer scan_temp;
             const size_t tb = std::max<size_t>(scan_temp_bytes(components + 1), 16);
             scan_temp.reserve(tb);
             launch_component_counts(g, label, components, counts.as<uint64_t>(), b.stream);
-            launch_scan(counts.as<uint64_t>(), ix->comp_offsets.as<uint64_t>(), components, scan_temp.ptr, tb, b.stream);
+            launch_scan(counts.as<uint64_t>(), ix->components.offsets.as<uint64_t>(), components, scan_temp.ptr, tb, b.stream);
             uint64_t *total = reinterpret_cast<uint64_t *>(b.pinned + 2);
-            HIP_CHECK(hipMemcpyAsync(total, ix->comp_offsets.as<uint64_t>() + components, sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream));
+            HIP_CHECK(hipMemcpyAsync(total, ix->components.offsets.as<uint64_t>() + components, sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream));
             HIP_CHECK(hipStreamSynchronize(b.stream));
             nodes = *total;
-            ix->comp_nodes.reserve(std::max<uint64_t>(nodes, 4) * sizeof(uint32_t));
-            launch_component_csr(g, w, components, ix->comp_nodes.as<uint32_t>(), b.stream);
+            ix->components.nodes.reserve(std::max<uint64_t>(nodes, 4) * sizeof(uint32_t));
+            launch_component_csr(g, w, components, ix->components.nodes.as<uint32_t>(), b.stream);
             times.shape_launches += 4;
-            launch_path_components(d, g, label, paths, static_cast<uint32_t>(stride), ix->comp_paths.as<uint32_t>(), b.stream);
+            launch_path_components(d, g, label, paths, static_cast<uint32_t>(stride), ix->components.paths.as<uint32_t>(), b.stream);
             times.shape_launches += paths ? 1 : 0;
-            ix->host_path_component.assign(paths, COMPONENT_NONE);
-            if (paths) HIP_CHECK(hipMemcpyAsync(ix->host_path_component.data(), ix->comp_paths.ptr, paths * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream));
+            ix->components.host_paths.assign(paths, COMPONENT_NONE);
+            if (paths) HIP_CHECK(hipMemcpyAsync(ix->components.host_paths.data(), ix->components.paths.ptr, paths * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream));
             times.shape_ms = b.end();                       // (before the scratch buffers go: hipFree waits anyway)
         } else {
-            ix->comp_offsets.reserve(sizeof(uint64_t));
-            ix->comp_nodes.reserve(sizeof(uint32_t));
-            HIP_CHECK(hipMemsetAsync(ix->comp_offsets.ptr, 0, sizeof(uint64_t), b.stream));
-            if (paths) HIP_CHECK(hipMemsetAsync(ix->comp_paths.ptr, 0xFF, paths * sizeof(uint32_t), b.stream));
-            ix->host_path_component.assign(paths, COMPONENT_NONE);
+            ix->components.offsets.reserve(sizeof(uint64_t));
+            ix->components.nodes.reserve(sizeof(uint32_t));
+            HIP_CHECK(hipMemsetAsync(ix->components.offsets.ptr, 0, sizeof(uint64_t), b.stream));
+            if (paths) HIP_CHECK(hipMemsetAsync(ix->components.paths.ptr, 0xFF, paths * sizeof(uint32_t), b.stream));
+            ix->components.host_paths.assign(paths, COMPONENT_NONE);
             times.shape_ms = b.end();
         }
-        ix->comp_geometry = g;
-        ix->comp_count = components;
-        ix->comp_node_count = nodes;
-        ix->comp_times = times;
+        ix->components.geometry = g;
+        ix->components.count = components;
+        ix->components.node_count = nodes;
+        ix->components.times = times;
     });
 }
 
@@ -143,8 +137,8 @@ std::vector<uint64_t> select_paths(const gbwt_hip_index *ix, const char *contig)
         if (h.path_names[p].contig == contig_id) initial.push_back(p);
     if (initial.empty()) throw InvalidData("The graph does not contain any paths for contig " + name);
     ensure_components(ix);
-    const std::vector<uint32_t> &of = ix->host_path_component;
-    std::vector<uint8_t> wanted(ix->comp_count, 0);
+    const std::vector<uint32_t> &of = ix->components.host_paths;
+    std::vector<uint8_t> wanted(ix->components.count, 0);
     for (uint64_t p : initial)
         if (p < of.size() && of[p] != COMPONENT_NONE) wanted[of[p]] = 1;
     for (uint64_t p = 0; p < of.size(); p++)                                             // 0..gbz.paths()
@@ -165,15 +159,15 @@ gbwt_hip_status gbwt_hip_components_device(const gbwt_hip_index *ix, gbwt_hip_co
     } catch (const HipError &e) {
         return status_of(e);
     }
-    out->d_component = ix->comp_of.as<uint32_t>();
-    out->d_offsets = ix->comp_offsets.as<uint64_t>();
-    out->d_nodes = ix->comp_nodes.as<uint32_t>();
-    out->d_path_component = ix->comp_paths.as<uint32_t>();
-    out->min_node = ix->comp_geometry.min_node;
-    out->slots = ix->comp_geometry.slots;
-    out->components = ix->comp_count;
-    out->nodes = ix->comp_node_count;
-    out->paths = ix->host_path_component.size();
+    out->d_component = ix->components.of.as<uint32_t>();
+    out->d_offsets = ix->components.offsets.as<uint64_t>();
+    out->d_nodes = ix->components.nodes.as<uint32_t>();
+    out->d_path_component = ix->components.paths.as<uint32_t>();
+    out->min_node = ix->components.geometry.min_node;
+    out->slots = ix->components.geometry.slots;
+    out->components = ix->components.count;
+    out->nodes = ix->components.node_count;
+    out->paths = ix->components.host_paths.size();
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
@@ -186,16 +180,16 @@ gbwt_hip_status gbwt_hip_weakly_connected_components(const gbwt_hip_index *ix, u
     *components = 0; *nodes = 0;
     try {
         ensure_components(ix);
-        *components = ix->comp_count;
-        *nodes = ix->comp_node_count;
+        *components = ix->components.count;
+        *nodes = ix->components.node_count;
         if (!out_offsets && !out_nodes) return GBWT_HIP_OK;
-        if ((out_offsets && offsets_capacity < ix->comp_count + 1) || (out_nodes && nodes_capacity < ix->comp_node_count))
+        if ((out_offsets && offsets_capacity < ix->components.count + 1) || (out_nodes && nodes_capacity < ix->components.node_count))
             return fail(GBWT_HIP_CAPACITY, "output capacity too small for the components");
         HIP_CHECK(hipSetDevice(ix->device));
-        if (out_offsets) HIP_CHECK(hipMemcpy(out_offsets, ix->comp_offsets.ptr, (ix->comp_count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (out_nodes && ix->comp_node_count) {
-            std::vector<uint32_t> ids(ix->comp_node_count);
-            HIP_CHECK(hipMemcpy(ids.data(), ix->comp_nodes.ptr, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (out_offsets) HIP_CHECK(hipMemcpy(out_offsets, ix->components.offsets.ptr, (ix->components.count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (out_nodes && ix->components.node_count) {
+            std::vector<uint32_t> ids(ix->components.node_count);
+            HIP_CHECK(hipMemcpy(ids.data(), ix->components.nodes.ptr, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (size_t k = 0; k < ids.size(); k++) out_nodes[k] = ids[k];
         }
         return GBWT_HIP_OK;
@@ -214,7 +208,7 @@ gbwt_hip_status gbwt_hip_path_components(const gbwt_hip_index *ix, const uint64_
     } catch (const HipError &e) {
         return status_of(e);
     }
-    const std::vector<uint32_t> &of = ix->host_path_component;
+    const std::vector<uint32_t> &of = ix->components.host_paths;
     for (uint64_t k = 0; k < n; k++)
         if (path_ids[k] >= of.size()) return fail(GBWT_HIP_BAD_ARGUMENT, "path id out of range");
     for (uint64_t k = 0; k < n; k++) out[k] = of[path_ids[k]];
@@ -225,8 +219,8 @@ gbwt_hip_status gbwt_hip_path_components(const gbwt_hip_index *ix, const uint64_
 gbwt_hip_status gbwt_hip_last_components_ms(const gbwt_hip_index *ix, gbwt_hip_components_times *out) {
     GBWT_HIP_GUARD_BEGIN
     if (!ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null index / output");
-    if (!ix->components_built.made()) return fail(GBWT_HIP_BAD_ARGUMENT, "the components of this handle have not been made yet");
-    *out = ix->comp_times;
+    if (!ix->components.built.made()) return fail(GBWT_HIP_BAD_ARGUMENT, "the components of this handle have not been made yet");
+    *out = ix->components.times;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }

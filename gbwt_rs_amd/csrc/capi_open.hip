@@ -835,38 +835,18 @@ gbwt_hip_status gbwt_hip_memory_usage(const gbwt_hip_index *index, const gbwt_hi
     GBWT_HIP_GUARD_BEGIN
     if (!index || !out || (ws && ws->index != index)) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
     *out = gbwt_hip_memory{};
-    const auto sum = [](std::initializer_list<const DeviceBuffer *> buffers) { uint64_t b = 0; for (const DeviceBuffer *q : buffers) b += q->bytes; return b; };
     const gbwt_hip_index &ix = *index;
-    out->index_device_bytes = sum({&ix.data, &ix.starts, &ix.endmarker, &ix.desc, &ix.desc_raw, &ix.block_base, &ix.blocks, &ix.desc2, &ix.gblocks, &ix.tables,
-                                   &ix.wtables, &ix.wtables_deep, &ix.seq_len, &ix.samples, &ix.sample_base, &ix.label_len, &ix.seg_of, &ix.seg_start,
-                                   &ix.seg_name_off, &ix.seg_names, &ix.seg_seq_len, &ix.node_real, &ix.line_prefix[0], &ix.line_prefix[1], &ix.line_prefix[2],
-                                   &ix.line_prefix_off[0], &ix.line_prefix_off[1], &ix.line_prefix_off[2], &ix.line_fragment, &ix.lc_chunk_first, &ix.lc_text, &ix.lc_path});
-    // (the full-width two-step blocks: at open, or by the first request that needs them)
-    if (ix.dev.cblocks != nullptr || ix.cblocks_built.made()) out->index_device_bytes += ix.cblocks.bytes;
-    // (the node labels: by the first request for bases)
-    if (ix.labels_built.made()) out->index_device_bytes += ix.label_bytes.bytes + ix.label_off.bytes;
-    // (the weakly connected components: by the first call for them)
-    if (ix.components_built.made()) out->index_device_bytes += ix.comp_of.bytes + ix.comp_offsets.bytes + ix.comp_nodes.bytes + ix.comp_paths.bytes;
-    // (the locate index: by the first locate call)
-    if (ix.locate_built.made()) out->index_device_bytes += ix.loc_base.bytes + ix.loc_table.bytes + ix.loc_end_keys.bytes + ix.loc_end_ids.bytes;
+    out->index_device_bytes = ix.device_bytes();   // (every struct that owns buffers sums its own: handle.hpp, workspace.hpp)
     const HostIndex &h = ix.host;
     out->index_host_bytes = (h.records_made() ? h.data.size() + h.starts.size() * sizeof(uint64_t) : 0) + h.da_samples.size() * sizeof(uint64_t) + h.path_names.size() * sizeof(PathName) +
                             h.sample_names.bytes.size() + h.contig_names.bytes.size() + h.sequences_labels.bytes.size() + h.sequences_labels.offsets.size() * sizeof(uint64_t) +
                             h.segment_names.bytes.size() + h.segment_names.offsets.size() * sizeof(uint64_t) + h.segment_starts.size() * sizeof(uint64_t) +
                             ix.sample_counts.size() * sizeof(uint32_t);
     if (ws) {
-        out->workspace_device_bytes = sum({&ws->seq_ids, &ws->lengths, &ws->offsets, &ws->head, &ws->pool, &ws->next, &ws->counters, &ws->nodes, &ws->scan_temp,
-                                           &ws->order_keys, &ws->order_rows, &ws->order_counts, &ws->order_level, &ws->order_temp, &ws->in_a, &ws->in_b, &ws->out_a,
-                                           &ws->out_valid, &ws->follow_off, &ws->gfa_a, &ws->gfa_b, &ws->gfa_c, &ws->gfa_text, &ws->gfa_text2, &ws->gfa_valid, &ws->gfa_chunk_first,
-                                           &ws->gfa_chunks, &ws->gfa_plan, &ws->seq_text, &ws->seq_text2, &ws->seq_offsets, &ws->tag_node, &ws->tag_off, &ws->tag_top, &ws->tag_state,
-                                           &ws->tag_sa, &ws->tag_sa2, &ws->tag_out, &ws->tag_out2, &ws->rp_off, &ws->rp_mark, &ws->rp_jump, &ws->rp_rows, &ws->rp_flags,
-                                           &ws->rp_paths, &ws->rp_positions, &ws->tp_ids, &ws->tp_orient, &ws->tp_seg, &ws->tp_counts, &ws->tp_off, &ws->tp_edges, &ws->tp_rows,
-                                           &ws->tp_valid, &ws->tp_big, &ws->tp_cut, &ws->tp_loff, &ws->tp_links, &ws->gt_items, &ws->gt_soff, &ws->gt_edges, &ws->gt_rows,
-                                           &ws->gt_loff, &ws->gt_text, &ws->lo_states, &ws->lo_counts, &ws->lo_off, &ws->lo_ids, &ws->lo_valid, &ws->lo_keys, &ws->lo_sorted, &ws->lo_flag,
-                                           &ws->lo_rank, &ws->lo_uoff, &ws->lo_temp, &ws->lo_words, &ws->lo_pos, &ws->lo_pos_ids, &ws->lo_pos_valid});
-        out->rows_bytes = ws->nodes.bytes;
-        out->rows_chunks = ws->nodes.chunks.size();
-        out->text_bytes = ws->gfa_text.bytes + ws->gfa_text2.bytes + ws->seq_text.bytes + ws->seq_text2.bytes + ws->gt_text.bytes;
+        out->workspace_device_bytes = ws->device_bytes();
+        out->rows_bytes = ws->extract.rows_bytes();
+        out->rows_chunks = ws->extract.rows_chunks();
+        out->text_bytes = ws->text_bytes();
     }
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END

@@ -6,7 +6,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -36,24 +35,24 @@ gbwt_hip_status run_query(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, cons
     if (!(ix->caps & GBWT_HIP_OPEN_SEARCH)) return fail(GBWT_HIP_BAD_ARGUMENT, "the handle was not opened for navigation / search (GBWT_HIP_OPEN_SEARCH)");
     if (n == 0) return GBWT_HIP_OK;
     if ((!in_a && a_row != 0) || !out || !valid) return fail(GBWT_HIP_BAD_ARGUMENT, "null buffer");   // (rows of no bytes -- queries of no nodes -- have no buffer)
-    ws->follow_cached = false;   // the staging buffers are shared with gbwt_hip_follow
+    ws->query.memo.drop();   // the staging buffers are shared with gbwt_hip_follow
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        ws->in_a.reserve(std::max<size_t>(n * a_row, 16));
-        ws->out_a.reserve(n * out_row);
-        ws->out_valid.reserve(n);
-        if (in_b) ws->in_b.reserve(n * b_row);
-        for (auto &e : ws->qev) if (!e) HIP_CHECK(hipEventCreate(&e));
+        ws->query.in_a.reserve(std::max<size_t>(n * a_row, 16));
+        ws->query.out_a.reserve(n * out_row);
+        ws->query.out_valid.reserve(n);
+        if (in_b) ws->query.in_b.reserve(n * b_row);
+        ws->query.ev.ensure();
         hipStream_t s = ws->stream;
-        if (a_row != 0) HIP_CHECK(hipMemcpyAsync(ws->in_a.ptr, in_a, n * a_row, hipMemcpyHostToDevice, s));
-        if (in_b) HIP_CHECK(hipMemcpyAsync(ws->in_b.ptr, in_b, n * b_row, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipEventRecord(ws->qev[0], s));
-        launch(ws->in_a.as<char>(), in_b ? ws->in_b.as<char>() : nullptr, ws->out_a.as<char>(), ws->out_valid.as<uint8_t>(), n, s);
-        HIP_CHECK(hipEventRecord(ws->qev[1], s));
-        ws->query_timed = true;
+        if (a_row != 0) HIP_CHECK(hipMemcpyAsync(ws->query.in_a.ptr, in_a, n * a_row, hipMemcpyHostToDevice, s));
+        if (in_b) HIP_CHECK(hipMemcpyAsync(ws->query.in_b.ptr, in_b, n * b_row, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipEventRecord(ws->query.ev[0], s));
+        launch(ws->query.in_a.as<char>(), in_b ? ws->query.in_b.as<char>() : nullptr, ws->query.out_a.as<char>(), ws->query.out_valid.as<uint8_t>(), n, s);
+        HIP_CHECK(hipEventRecord(ws->query.ev[1], s));
+        ws->query.timed = true;
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out, ws->out_a.ptr, n * out_row, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(valid, ws->out_valid.ptr, n, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(out, ws->query.out_a.ptr, n * out_row, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(valid, ws->query.out_valid.ptr, n, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
@@ -68,16 +67,16 @@ gbwt_hip_status run_query_device(const gbwt_hip_index *ix, gbwt_hip_workspace *w
     if (!ix || !ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
     if (!(ix->caps & GBWT_HIP_OPEN_SEARCH)) return fail(GBWT_HIP_BAD_ARGUMENT, "the handle was not opened for navigation / search (GBWT_HIP_OPEN_SEARCH)");
     if (n && !d_in) return fail(GBWT_HIP_BAD_ARGUMENT, "null buffer");
-    ws->follow_cached = false;
+    ws->query.memo.drop();
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        ws->out_a.reserve(std::max<uint64_t>(n, 1) * out_row);
-        ws->out_valid.reserve(std::max<uint64_t>(n, 1));
-        for (auto &e : ws->qev) if (!e) HIP_CHECK(hipEventCreate(&e));
-        HIP_CHECK(hipEventRecord(ws->qev[0], ws->stream));
-        if (n) launch(ws->out_a.as<char>(), ws->out_valid.as<uint8_t>(), ws->stream);
-        HIP_CHECK(hipEventRecord(ws->qev[1], ws->stream));
-        ws->query_timed = true;
+        ws->query.out_a.reserve(std::max<uint64_t>(n, 1) * out_row);
+        ws->query.out_valid.reserve(std::max<uint64_t>(n, 1));
+        ws->query.ev.ensure();
+        HIP_CHECK(hipEventRecord(ws->query.ev[0], ws->stream));
+        if (n) launch(ws->query.out_a.as<char>(), ws->query.out_valid.as<uint8_t>(), ws->stream);
+        HIP_CHECK(hipEventRecord(ws->query.ev[1], ws->stream));
+        ws->query.timed = true;
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(ws->stream));
         return GBWT_HIP_OK;
@@ -92,8 +91,8 @@ extern "C" {
 
 gbwt_hip_status gbwt_hip_last_query_ms(const gbwt_hip_workspace *ws, float *kernel_ms) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->query_timed || !kernel_ms) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed query on this workspace");
-    if (hipEventElapsedTime(kernel_ms, ws->qev[0], ws->qev[1]) != hipSuccess) return fail(GBWT_HIP_DEVICE_ERROR, "hipEventElapsedTime failed");
+    if (!ws || !ws->query.timed || !kernel_ms) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed query on this workspace");
+    if (hipEventElapsedTime(kernel_ms, ws->query.ev[0], ws->query.ev[1]) != hipSuccess) return fail(GBWT_HIP_DEVICE_ERROR, "hipEventElapsedTime failed");
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
@@ -196,35 +195,32 @@ gbwt_hip_status gbwt_hip_follow(const gbwt_hip_index *ix, gbwt_hip_workspace *ws
         hipStream_t s = ws->stream;
         // the fill call after a size query with the same states: counts and offsets are still in the workspace
         const size_t key_bytes = n * sizeof(gbwt_hip_bd_state);
-        const bool hit = ws->follow_cached && ws->follow_backward == (backward != 0) && ws->follow_key.size() == key_bytes &&
-                         std::memcmp(ws->follow_key.data(), states, key_bytes) == 0;
+        const bool hit = ws->query.memo.matches({{states, key_bytes}}, {backward != 0});
         if (!hit) {
-            ws->follow_cached = false;
-            ws->in_a.reserve(key_bytes);
-            ws->in_b.reserve(n * sizeof(uint64_t));
-            ws->out_valid.reserve(n);
-            ws->follow_off.reserve((n + 1) * sizeof(uint64_t));
+            ws->query.memo.drop();
+            ws->query.in_a.reserve(key_bytes);
+            ws->query.in_b.reserve(n * sizeof(uint64_t));
+            ws->query.out_valid.reserve(n);
+            ws->query.follow_off.reserve((n + 1) * sizeof(uint64_t));
             const size_t temp_bytes = scan_temp_bytes(n);
-            ws->scan_temp.reserve(std::max<size_t>(temp_bytes, 16));
-            HIP_CHECK(hipMemcpyAsync(ws->in_a.ptr, states, key_bytes, hipMemcpyHostToDevice, s));
-            launch_follow_count(ix->dev, ws->in_a.as<gbwt_hip_bd_state>(), n, backward != 0, ws->in_b.as<uint64_t>(), ws->out_valid.as<uint8_t>(), s);
-            launch_scan(ws->in_b.as<uint64_t>(), ws->follow_off.as<uint64_t>(), n, ws->scan_temp.ptr, temp_bytes, s);
+            ws->scratch.scan_temp.reserve(std::max<size_t>(temp_bytes, 16));
+            HIP_CHECK(hipMemcpyAsync(ws->query.in_a.ptr, states, key_bytes, hipMemcpyHostToDevice, s));
+            launch_follow_count(ix->dev, ws->query.in_a.as<gbwt_hip_bd_state>(), n, backward != 0, ws->query.in_b.as<uint64_t>(), ws->query.out_valid.as<uint8_t>(), s);
+            launch_scan(ws->query.in_b.as<uint64_t>(), ws->query.follow_off.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, temp_bytes, s);
             HIP_CHECK(hipGetLastError());
-            ws->follow_key.assign(reinterpret_cast<const uint8_t *>(states), reinterpret_cast<const uint8_t *>(states) + key_bytes);
-            ws->follow_backward = backward != 0;
         }
-        HIP_CHECK(hipMemcpyAsync(out_offsets, ws->follow_off.ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(valid, ws->out_valid.ptr, n, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(out_offsets, ws->query.follow_off.ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(valid, ws->query.out_valid.ptr, n, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         *total = out_offsets[n];
-        ws->follow_cached = true;
+        if (!hit) ws->query.memo.store({{states, key_bytes}}, {backward != 0});
         if (!out_states) return GBWT_HIP_OK;
         if (capacity < *total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the extensions");
         if (*total == 0) return GBWT_HIP_OK;
-        ws->out_a.reserve(*total * sizeof(gbwt_hip_bd_state));
-        launch_follow_fill(ix->dev, ws->in_a.as<gbwt_hip_bd_state>(), n, backward != 0, ws->follow_off.as<uint64_t>(), ws->out_a.as<gbwt_hip_bd_state>(), s);
+        ws->query.out_a.reserve(*total * sizeof(gbwt_hip_bd_state));
+        launch_follow_fill(ix->dev, ws->query.in_a.as<gbwt_hip_bd_state>(), n, backward != 0, ws->query.follow_off.as<uint64_t>(), ws->query.out_a.as<gbwt_hip_bd_state>(), s);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out_states, ws->out_a.ptr, *total * sizeof(gbwt_hip_bd_state), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(out_states, ws->query.out_a.ptr, *total * sizeof(gbwt_hip_bd_state), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
@@ -252,7 +248,7 @@ gbwt_hip_status gbwt_hip_search_device(const gbwt_hip_index *ix, gbwt_hip_worksp
     const gbwt_hip_status st = run_query_device(ix, ws, d_queries, sizeof(gbwt_hip_state), n, [&](void *o, uint8_t *v, hipStream_t s) {
         launch_search(ix->dev, d_queries, n, len, static_cast<gbwt_hip_state *>(o), v, s);
     });
-    if (st == GBWT_HIP_OK) *out = gbwt_hip_states{ws->out_a.as<gbwt_hip_state>(), ws->out_valid.as<uint8_t>(), n};
+    if (st == GBWT_HIP_OK) *out = gbwt_hip_states{ws->query.out_a.as<gbwt_hip_state>(), ws->query.out_valid.as<uint8_t>(), n};
     return st;
     GBWT_HIP_GUARD_END
 }
@@ -278,7 +274,7 @@ gbwt_hip_status gbwt_hip_bd_search_device(const gbwt_hip_index *ix, gbwt_hip_wor
     const gbwt_hip_status st = run_query_device(ix, ws, d_queries, sizeof(gbwt_hip_bd_state), n, [&](void *o, uint8_t *v, hipStream_t s) {
         launch_bd_search(ix->dev, d_queries, n, len, first, static_cast<gbwt_hip_bd_state *>(o), v, s);
     });
-    if (st == GBWT_HIP_OK) *out = gbwt_hip_bd_states{ws->out_a.as<gbwt_hip_bd_state>(), ws->out_valid.as<uint8_t>(), n};
+    if (st == GBWT_HIP_OK) *out = gbwt_hip_bd_states{ws->query.out_a.as<gbwt_hip_bd_state>(), ws->query.out_valid.as<uint8_t>(), n};
     return st;
     GBWT_HIP_GUARD_END
 }

@@ -65,7 +65,7 @@ uint32_t rounds_for(uint64_t positions) {
     return r;
 }
 
-// The positions of a list of paths, computed once into the workspace (rp_paths, rp_positions, rp_total) unless it holds them already
+// The positions of a list of paths, computed once into the workspace (refpos.paths, positions, total) unless it holds them already
 gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, uint64_t interval) {
     if (!ix || !ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
     if (n && !path_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null path_ids");
@@ -76,21 +76,21 @@ gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
     if (n > (~uint64_t(0)) / 64) return fail(GBWT_HIP_BAD_ARGUMENT, "too many paths");
     for (uint64_t k = 0; k < n; k++)
         if (path_ids[k] >= h.sequences / 2) return fail(GBWT_HIP_BAD_ARGUMENT, "path id out of range: " + std::to_string(path_ids[k]));
-    if (ws->rp_cached && ws->rp_interval == interval && ws->rp_key.size() == n && (n == 0 || std::memcmp(ws->rp_key.data(), path_ids, n * sizeof(uint64_t)) == 0))
-        return GBWT_HIP_OK;
-    ws->rp_cached = ws->rp_timed = false;
+    if (ws->refpos.memo.matches({{path_ids, n * sizeof(uint64_t)}}, {static_cast<int64_t>(interval)})) return GBWT_HIP_OK;
+    ws->refpos.memo.drop();
+    ws->refpos.timed = false;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
-        for (auto &e : ws->rev) if (!e) HIP_CHECK(hipEventCreate(&e));
-        ws->rp_walk_ms = ws->rp_select_ms = ws->rp_offsets_ms = 0;
-        ws->rp_rounds = ws->rp_launches = 0;
-        ws->rp_total = 0;
-        ws->rp_paths.reserve(std::max<uint64_t>(n, 1) * sizeof(gbwt_hip_reference_path));
+        ws->refpos.ev.ensure();
+        ws->refpos.walk_ms = ws->refpos.select_ms = ws->refpos.offsets_ms = 0;
+        ws->refpos.rounds = ws->refpos.launches = 0;
+        ws->refpos.total = 0;
+        ws->refpos.paths.reserve(std::max<uint64_t>(n, 1) * sizeof(gbwt_hip_reference_path));
         if (n == 0) {
-            ws->rp_positions.reserve(sizeof(gbwt_hip_reference_position));
-            ws->rp_key.clear(); ws->rp_interval = interval;
-            ws->rp_cached = ws->rp_timed = true;
+            ws->refpos.positions.reserve(sizeof(gbwt_hip_reference_position));
+            ws->refpos.memo.store({{nullptr, 0}}, {static_cast<int64_t>(interval)});
+            ws->refpos.timed = true;
             return GBWT_HIP_OK;
         }
         ensure_labels(ix);
@@ -107,27 +107,27 @@ gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
         gbwt_hip_paths paths{};
         const gbwt_hip_status st = gbwt_hip_extract_device(ix, ws, seq_ids, n, &paths);
         if (st != GBWT_HIP_OK) return st;
-        HIP_CHECK(hipEventElapsedTime(&ws->rp_walk_ms, ws->ev[0], ws->ev[1]));
+        HIP_CHECK(hipEventElapsedTime(&ws->refpos.walk_ms, ws->extract.ev[0], ws->extract.ev[1]));
         const uint64_t P = paths.total;
         if (P > 0xFFFFFFFFull) return fail(GBWT_HIP_UNSUPPORTED, "the requested paths hold " + std::to_string(P) + " nodes: a request for positions is limited to 2^32 - 1");
         const RefposRows rows{paths.d_offsets, paths.d_nodes, n, P};
         const uint64_t words = (P + 1) * sizeof(uint64_t);
         const size_t tb = std::max<size_t>(scan_temp_bytes(std::min<uint64_t>(std::max<uint64_t>(P, 1), REFPOS_SCAN_PIECE)), 16);
-        require_fits({{&ws->rp_off, words}, {&ws->rp_mark, words}, {&ws->rp_jump, words}, {&ws->scan_temp, tb}}, "the offsets, marks and jumps of a request for positions");
-        ws->rp_off.reserve(words); ws->rp_mark.reserve(words); ws->rp_jump.reserve(words);
-        ws->scan_temp.reserve(tb);
-        ws->rp_rows.reserve(host_rows.size() * sizeof(uint64_t));
-        ws->rp_flags.reserve(REFPOS_FLAGS * sizeof(uint32_t) + sizeof(uint64_t));
-        uint64_t *d_off = ws->rp_off.as<uint64_t>(), *d_mark = ws->rp_mark.as<uint64_t>(), *d_slot = ws->rp_jump.as<uint64_t>();
-        uint32_t *d_jump = ws->rp_jump.as<uint32_t>(), *d_next = d_jump + (P + 1), *d_flags = ws->rp_flags.as<uint32_t>();
+        require_fits({{&ws->refpos.off, words}, {&ws->refpos.mark, words}, {&ws->refpos.jump, words}, {&ws->scratch.scan_temp, tb}}, "the offsets, marks and jumps of a request for positions");
+        ws->refpos.off.reserve(words); ws->refpos.mark.reserve(words); ws->refpos.jump.reserve(words);
+        ws->scratch.scan_temp.reserve(tb);
+        ws->refpos.rows.reserve(host_rows.size() * sizeof(uint64_t));
+        ws->refpos.flags.reserve(REFPOS_FLAGS * sizeof(uint32_t) + sizeof(uint64_t));
+        uint64_t *d_off = ws->refpos.off.as<uint64_t>(), *d_mark = ws->refpos.mark.as<uint64_t>(), *d_slot = ws->refpos.jump.as<uint64_t>();
+        uint32_t *d_jump = ws->refpos.jump.as<uint32_t>(), *d_next = d_jump + (P + 1), *d_flags = ws->refpos.flags.as<uint32_t>();
         uint64_t *d_carry = reinterpret_cast<uint64_t *>(d_flags + REFPOS_FLAGS);
-        const uint64_t *d_rows = ws->rp_rows.as<uint64_t>();
-        HIP_CHECK(hipMemcpyAsync(ws->rp_rows.ptr, host_rows.data(), host_rows.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemsetAsync(ws->rp_flags.ptr, 0, REFPOS_FLAGS * sizeof(uint32_t), s));
-        HIP_CHECK(hipEventRecord(ws->rev[0], s));
+        const uint64_t *d_rows = ws->refpos.rows.as<uint64_t>();
+        HIP_CHECK(hipMemcpyAsync(ws->refpos.rows.ptr, host_rows.data(), host_rows.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(ws->refpos.flags.ptr, 0, REFPOS_FLAGS * sizeof(uint32_t), s));
+        HIP_CHECK(hipEventRecord(ws->refpos.ev[0], s));
         // 2. bases in front of every position
         launch_refpos_lengths(rows, labels_of(ix), d_mark, s);
-        launch_refpos_scan(d_mark, d_off, P, d_carry, ws->scan_temp.ptr, tb, s);
+        launch_refpos_scan(d_mark, d_off, P, d_carry, ws->scratch.scan_temp.ptr, tb, s);
         // 3. successors, 4. the greedy chain of every row by pointer doubling
         launch_refpos_succ(rows, d_off, interval, d_jump, s);
         HIP_CHECK(hipMemsetAsync(d_mark, 0, words, s));
@@ -135,43 +135,41 @@ gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
         const uint32_t rounds = rounds_for(P);
         for (uint32_t t = 0; t < rounds; t++) { launch_refpos_round(d_mark, d_jump, d_next, P, d_flags, t, s); std::swap(d_jump, d_next); }
         // 5. slots (over the jump arrays, which nobody reads any more)
-        launch_refpos_scan(d_mark, d_slot, P, d_carry, ws->scan_temp.ptr, tb, s);
+        launch_refpos_scan(d_mark, d_slot, P, d_carry, ws->scratch.scan_temp.ptr, tb, s);
         uint64_t total = 0;
         uint32_t flags[REFPOS_FLAGS] = {};
         HIP_CHECK(hipMemcpyAsync(&total, d_slot + P, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipEventRecord(ws->rev[1], s));
+        HIP_CHECK(hipEventRecord(ws->refpos.ev[1], s));
         HIP_CHECK(hipStreamSynchronize(s));          // the one wait in front of the results: the total sizes them
         HIP_CHECK(hipGetLastError());
         const uint64_t pieces = (P + REFPOS_SCAN_PIECE - 1) / REFPOS_SCAN_PIECE;
         // lengths, two scans (a piece behind the first has two carry launches around it), successors, first marks, the rounds, paths, walk
-        ws->rp_launches = static_cast<uint32_t>((P ? 1 : 0) + 2 * (P ? 3 * pieces - 2 : 0) + 2 + rounds + 2);
-        for (uint32_t t = 0; t < rounds; t++) ws->rp_rounds += flags[t] != 0 ? 1u : 0u;
+        ws->refpos.launches = static_cast<uint32_t>((P ? 1 : 0) + 2 * (P ? 3 * pieces - 2 : 0) + 2 + rounds + 2);
+        for (uint32_t t = 0; t < rounds; t++) ws->refpos.rounds += flags[t] != 0 ? 1u : 0u;
         if (total > (~uint64_t(0)) / sizeof(gbwt_hip_reference_position)) return fail(GBWT_HIP_CAPACITY, "too many positions for device memory");
         const uint64_t result_bytes = std::max<uint64_t>(total, 1) * sizeof(gbwt_hip_reference_position);
-        require_fits({{&ws->rp_positions, result_bytes}}, "the positions of the request");
-        ws->rp_positions.reserve(result_bytes);
+        require_fits({{&ws->refpos.positions, result_bytes}}, "the positions of the request");
+        ws->refpos.positions.reserve(result_bytes);
         // 6. the walk that carries the in-record offsets
         DeviceIndex d = ix->dev;
         d.sample_stride = 1; d.sample_part = 0; d.sample_parts = 0;
         RefposWalk w{};
         w.seq_ids = d_rows; w.seg_first = d_rows + 2 * n; w.walkers = seg_first[n]; w.segmented = segmented ? 1u : 0u;
-        w.off = d_off; w.slot = d_slot; w.out = ws->rp_positions.as<gbwt_hip_reference_position>(); w.flags = d_flags;
-        launch_refpos_paths(rows, d_rows + n, d_off, d_slot, ws->rp_paths.as<gbwt_hip_reference_path>(), s);
+        w.off = d_off; w.slot = d_slot; w.out = ws->refpos.positions.as<gbwt_hip_reference_position>(); w.flags = d_flags;
+        launch_refpos_paths(rows, d_rows + n, d_off, d_slot, ws->refpos.paths.as<gbwt_hip_reference_path>(), s);
         launch_refpos_walk(d, rows, w, d.desc_raw != nullptr && d.blocks != nullptr, s);
-        HIP_CHECK(hipEventRecord(ws->rev[2], s));
+        HIP_CHECK(hipEventRecord(ws->refpos.ev[2], s));
         HIP_CHECK(hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventElapsedTime(&ws->rp_select_ms, ws->rev[0], ws->rev[1]));
-        HIP_CHECK(hipEventElapsedTime(&ws->rp_offsets_ms, ws->rev[1], ws->rev[2]));
-        ws->rp_timed = true;
+        HIP_CHECK(hipEventElapsedTime(&ws->refpos.select_ms, ws->refpos.ev[0], ws->refpos.ev[1]));
+        HIP_CHECK(hipEventElapsedTime(&ws->refpos.offsets_ms, ws->refpos.ev[1], ws->refpos.ev[2]));
+        ws->refpos.timed = true;
         if (flags[REFPOS_FLAG_MISMATCH] != 0)
             return fail(GBWT_HIP_DEVICE_ERROR, "a walker of the positions met another node than the extracted row holds, or no successor inside a row (an inconsistent index)");
-        ws->rp_total = total;
-        ws->rp_key.assign(path_ids, path_ids + n);
-        ws->rp_interval = interval;
-        ws->rp_cached = true;
+        ws->refpos.total = total;
+        ws->refpos.memo.store({{path_ids, n * sizeof(uint64_t)}}, {static_cast<int64_t>(interval)});
         return GBWT_HIP_OK;
     } catch (const InvalidData &e) {
         return fail(GBWT_HIP_BAD_ARGUMENT, e.what());
@@ -227,9 +225,9 @@ gbwt_hip_status gbwt_hip_path_positions_device(const gbwt_hip_index *ix, gbwt_hi
     if (!d_paths || !d_positions || !total) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     const gbwt_hip_status st = positions_compute(ix, ws, path_ids, n, interval);
     if (st != GBWT_HIP_OK) return st;
-    *d_paths = ws->rp_paths.as<gbwt_hip_reference_path>();
-    *d_positions = ws->rp_positions.as<gbwt_hip_reference_position>();
-    *total = ws->rp_total;
+    *d_paths = ws->refpos.paths.as<gbwt_hip_reference_path>();
+    *d_positions = ws->refpos.positions.as<gbwt_hip_reference_position>();
+    *total = ws->refpos.total;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
@@ -241,16 +239,16 @@ gbwt_hip_status gbwt_hip_path_positions(const gbwt_hip_index *ix, gbwt_hip_works
     if (!total) return fail(GBWT_HIP_BAD_ARGUMENT, "null total");
     const gbwt_hip_status st = positions_compute(ix, ws, path_ids, n, interval);
     if (st != GBWT_HIP_OK) return st;
-    *total = ws->rp_total;
+    *total = ws->refpos.total;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         if (out_paths && n) {
-            HIP_CHECK(hipMemcpyAsync(out_paths, ws->rp_paths.ptr, n * sizeof(gbwt_hip_reference_path), hipMemcpyDeviceToHost, ws->stream));
+            HIP_CHECK(hipMemcpyAsync(out_paths, ws->refpos.paths.ptr, n * sizeof(gbwt_hip_reference_path), hipMemcpyDeviceToHost, ws->stream));
             HIP_CHECK(hipStreamSynchronize(ws->stream));
         }
         if (!out_positions) return GBWT_HIP_OK;
-        if (positions_capacity < ws->rp_total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the positions");
-        if (ws->rp_total) copy_to_host(ws, out_positions, ws->rp_positions.ptr, ws->rp_total * sizeof(gbwt_hip_reference_position));
+        if (positions_capacity < ws->refpos.total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the positions");
+        if (ws->refpos.total) copy_to_host(ws, out_positions, ws->refpos.positions.ptr, ws->refpos.total * sizeof(gbwt_hip_reference_position));
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         return status_of(e);
@@ -282,19 +280,19 @@ gbwt_hip_status gbwt_hip_reference_positions(const gbwt_hip_index *ix, gbwt_hip_
 
 gbwt_hip_status gbwt_hip_last_positions_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *select_ms, float *offsets_ms) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->rp_timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for positions on this workspace");
-    if (walk_ms) *walk_ms = ws->rp_walk_ms;
-    if (select_ms) *select_ms = ws->rp_select_ms;
-    if (offsets_ms) *offsets_ms = ws->rp_offsets_ms;
+    if (!ws || !ws->refpos.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for positions on this workspace");
+    if (walk_ms) *walk_ms = ws->refpos.walk_ms;
+    if (select_ms) *select_ms = ws->refpos.select_ms;
+    if (offsets_ms) *offsets_ms = ws->refpos.offsets_ms;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
 
 gbwt_hip_status gbwt_hip_last_positions_rounds(const gbwt_hip_workspace *ws, uint32_t *rounds, uint32_t *launches) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->rp_timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for positions on this workspace");
-    if (rounds) *rounds = ws->rp_rounds;
-    if (launches) *launches = ws->rp_launches;
+    if (!ws || !ws->refpos.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for positions on this workspace");
+    if (rounds) *rounds = ws->refpos.rounds;
+    if (launches) *launches = ws->refpos.launches;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }

@@ -37,15 +37,15 @@ uint64_t read_word(const uint64_t *d_word, hipStream_t s) {
 
 void scan(gbwt_hip_workspace *ws, const uint64_t *d_lengths, uint64_t *d_offsets, uint64_t n, hipStream_t s) {
     const size_t temp = std::max<size_t>(scan_temp_bytes(std::max<uint64_t>(n, 1)), 16);
-    ws->scan_temp.reserve(temp);
-    if (n) launch_scan(d_lengths, d_offsets, n, ws->scan_temp.ptr, temp, s);
+    ws->scratch.scan_temp.reserve(temp);
+    if (n) launch_scan(d_lengths, d_offsets, n, ws->scratch.scan_temp.ptr, temp, s);
     else HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), s));
 }
 
 const char *const NEEDS_GFA = "segments, links and graph lines need a GBZ opened with GBWT_HIP_OPEN_GFA";
 
-// The rows of a request, computed once into the workspace: edge rows (tp_off / tp_edges) or, links != 0, link rows (tp_loff / tp_links);
-// tp_valid, tp_total.  The request is remembered: the fill call after a size query finds its rows here.
+// The rows of a request, computed once into the workspace: edge rows (edges.off / edges.edges) or, links != 0, link rows (edges.loff / edges.links);
+// edges.valid, edges.total.  The request is remembered: the fill call after a size query finds its rows here.
 gbwt_hip_status rows_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const uint64_t *ids, const uint8_t *orientations, uint64_t n, int predecessors, int links) {
     if (!ix || !ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
     if (n && (!ids || !orientations)) return fail(GBWT_HIP_BAD_ARGUMENT, "null ids / orientations");
@@ -53,66 +53,62 @@ gbwt_hip_status rows_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, c
     if (links && (!ix->host.is_gbz || !(ix->caps & GBWT_HIP_OPEN_GFA))) return fail(GBWT_HIP_BAD_ARGUMENT, NEEDS_GFA);
     predecessors = predecessors ? 1 : 0;
     const size_t id_bytes = n * sizeof(uint64_t);
-    if (ws->tp_cached && ws->tp_links_request == links && ws->tp_predecessors == predecessors && ws->tp_n == n && ws->tp_key.size() == id_bytes + n &&
-        (n == 0 || (std::memcmp(ws->tp_key.data(), ids, id_bytes) == 0 && std::memcmp(ws->tp_key.data() + id_bytes, orientations, n) == 0)))
-        return GBWT_HIP_OK;
-    ws->tp_cached = false;
+    if (ws->edges.memo.matches({{ids, id_bytes}, {orientations, n}}, {links, predecessors, static_cast<int64_t>(n)})) return GBWT_HIP_OK;
+    ws->edges.memo.drop();
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
         const uint64_t rows = std::max<uint64_t>(n, 1);
-        ws->tp_ids.reserve(rows * sizeof(uint64_t));
-        ws->tp_orient.reserve(rows);
-        ws->tp_counts.reserve(rows * sizeof(uint64_t));
-        ws->tp_off.reserve((rows + 1) * sizeof(uint64_t));
-        ws->tp_valid.reserve(rows);
-        ws->tp_big.reserve((rows + 1) * sizeof(uint32_t));
-        for (auto &e : ws->qev) if (!e) HIP_CHECK(hipEventCreate(&e));
+        ws->edges.ids.reserve(rows * sizeof(uint64_t));
+        ws->edges.orient.reserve(rows);
+        ws->edges.counts.reserve(rows * sizeof(uint64_t));
+        ws->edges.off.reserve((rows + 1) * sizeof(uint64_t));
+        ws->edges.valid.reserve(rows);
+        ws->edges.big.reserve((rows + 1) * sizeof(uint32_t));
+        ws->query.ev.ensure();
         const GraphTables tables = links ? graph_tables(ix, false) : GraphTables{};
         if (links) {
-            ws->tp_seg.reserve(rows * (sizeof(uint64_t) + 1));
-            uint8_t *d_seg_orient = ws->tp_seg.as<uint8_t>() + rows * sizeof(uint64_t);
+            ws->edges.seg.reserve(rows * (sizeof(uint64_t) + 1));
+            uint8_t *d_seg_orient = ws->edges.seg.as<uint8_t>() + rows * sizeof(uint64_t);
             if (n) {
-                HIP_CHECK(hipMemcpyAsync(ws->tp_seg.ptr, ids, id_bytes, hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipMemcpyAsync(ws->edges.seg.ptr, ids, id_bytes, hipMemcpyHostToDevice, s));
                 HIP_CHECK(hipMemcpyAsync(d_seg_orient, orientations, n, hipMemcpyHostToDevice, s));
             }
-            HIP_CHECK(hipEventRecord(ws->qev[0], s));
-            launch_link_queries(tables, ws->tp_seg.as<uint64_t>(), d_seg_orient, n, predecessors != 0, ws->tp_ids.as<uint64_t>(), ws->tp_orient.as<uint8_t>(), s);
+            HIP_CHECK(hipEventRecord(ws->query.ev[0], s));
+            launch_link_queries(tables, ws->edges.seg.as<uint64_t>(), d_seg_orient, n, predecessors != 0, ws->edges.ids.as<uint64_t>(), ws->edges.orient.as<uint8_t>(), s);
         } else {
             if (n) {
-                HIP_CHECK(hipMemcpyAsync(ws->tp_ids.ptr, ids, id_bytes, hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipMemcpyAsync(ws->tp_orient.ptr, orientations, n, hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipMemcpyAsync(ws->edges.ids.ptr, ids, id_bytes, hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipMemcpyAsync(ws->edges.orient.ptr, orientations, n, hipMemcpyHostToDevice, s));
             }
-            HIP_CHECK(hipEventRecord(ws->qev[0], s));
+            HIP_CHECK(hipEventRecord(ws->query.ev[0], s));
         }
-        launch_edge_count(ix->dev, ws->tp_ids.as<uint64_t>(), ws->tp_orient.as<uint8_t>(), n, predecessors != 0, ws->tp_counts.as<uint64_t>(), ws->tp_valid.as<uint8_t>(), s);
-        scan(ws, ws->tp_counts.as<uint64_t>(), ws->tp_off.as<uint64_t>(), n, s);
+        launch_edge_count(ix->dev, ws->edges.ids.as<uint64_t>(), ws->edges.orient.as<uint8_t>(), n, predecessors != 0, ws->edges.counts.as<uint64_t>(), ws->edges.valid.as<uint8_t>(), s);
+        scan(ws, ws->edges.counts.as<uint64_t>(), ws->edges.off.as<uint64_t>(), n, s);
         HIP_CHECK(hipGetLastError());
-        uint64_t total = read_word(ws->tp_off.as<uint64_t>() + n, s);
-        ws->tp_edges.reserve(std::max<uint64_t>(total, 1) * sizeof(uint64_t));
-        if (links) ws->tp_rows.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
-        launch_edge_fill(ix->dev, ws->tp_ids.as<uint64_t>(), ws->tp_orient.as<uint8_t>(), n, predecessors != 0, ws->tp_off.as<uint64_t>(), ws->tp_edges.as<uint64_t>(),
-                         links ? ws->tp_rows.as<uint32_t>() : nullptr, ws->tp_big.as<uint32_t>(), s);
+        uint64_t total = read_word(ws->edges.off.as<uint64_t>() + n, s);
+        ws->edges.edges.reserve(std::max<uint64_t>(total, 1) * sizeof(uint64_t));
+        if (links) ws->edges.rows.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
+        launch_edge_fill(ix->dev, ws->edges.ids.as<uint64_t>(), ws->edges.orient.as<uint8_t>(), n, predecessors != 0, ws->edges.off.as<uint64_t>(), ws->edges.edges.as<uint64_t>(),
+                         links ? ws->edges.rows.as<uint32_t>() : nullptr, ws->edges.big.as<uint32_t>(), s);
         if (links) {
-            ws->tp_cut.reserve(rows * sizeof(uint64_t));
-            ws->tp_loff.reserve((rows + 1) * sizeof(uint64_t));
-            launch_link_cut(tables, ws->tp_off.as<uint64_t>(), ws->tp_edges.as<uint64_t>(), ws->tp_rows.as<uint32_t>(), n, total, ws->tp_cut.as<uint64_t>(), s);
-            scan(ws, ws->tp_cut.as<uint64_t>(), ws->tp_loff.as<uint64_t>(), n, s);
+            ws->edges.cut.reserve(rows * sizeof(uint64_t));
+            ws->edges.loff.reserve((rows + 1) * sizeof(uint64_t));
+            launch_link_cut(tables, ws->edges.off.as<uint64_t>(), ws->edges.edges.as<uint64_t>(), ws->edges.rows.as<uint32_t>(), n, total, ws->edges.cut.as<uint64_t>(), s);
+            scan(ws, ws->edges.cut.as<uint64_t>(), ws->edges.loff.as<uint64_t>(), n, s);
             HIP_CHECK(hipGetLastError());
-            const uint64_t kept = read_word(ws->tp_loff.as<uint64_t>() + n, s);
-            ws->tp_links.reserve(std::max<uint64_t>(kept, 1) * sizeof(uint64_t));
-            launch_link_write(tables, ws->tp_off.as<uint64_t>(), ws->tp_edges.as<uint64_t>(), ws->tp_rows.as<uint32_t>(), total, ws->tp_cut.as<uint64_t>(),
-                              ws->tp_loff.as<uint64_t>(), ws->tp_links.as<uint64_t>(), s);
+            const uint64_t kept = read_word(ws->edges.loff.as<uint64_t>() + n, s);
+            ws->edges.links.reserve(std::max<uint64_t>(kept, 1) * sizeof(uint64_t));
+            launch_link_write(tables, ws->edges.off.as<uint64_t>(), ws->edges.edges.as<uint64_t>(), ws->edges.rows.as<uint32_t>(), total, ws->edges.cut.as<uint64_t>(),
+                              ws->edges.loff.as<uint64_t>(), ws->edges.links.as<uint64_t>(), s);
             total = kept;
         }
-        HIP_CHECK(hipEventRecord(ws->qev[1], s));
-        ws->query_timed = true;
+        HIP_CHECK(hipEventRecord(ws->query.ev[1], s));
+        ws->query.timed = true;
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
-        ws->tp_key.resize(id_bytes + n);
-        if (n) { std::memcpy(ws->tp_key.data(), ids, id_bytes); std::memcpy(ws->tp_key.data() + id_bytes, orientations, n); }
-        ws->tp_links_request = links; ws->tp_predecessors = predecessors; ws->tp_n = n; ws->tp_total = total;
-        ws->tp_cached = true;
+        ws->edges.n = n; ws->edges.total = total;
+        ws->edges.memo.store({{ids, id_bytes}, {orientations, n}}, {links, predecessors, static_cast<int64_t>(n)});
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         return status_of(e);
@@ -126,17 +122,17 @@ gbwt_hip_status rows_to_host(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, c
     out_offsets[0] = 0;
     const gbwt_hip_status st = rows_compute(ix, ws, ids, orientations, n, predecessors, links);
     if (st != GBWT_HIP_OK) return st;
-    *total = ws->tp_total;
+    *total = ws->edges.total;
     if (n == 0) return GBWT_HIP_OK;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
-        HIP_CHECK(hipMemcpyAsync(out_offsets, (links ? ws->tp_loff : ws->tp_off).ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(valid, ws->tp_valid.ptr, n, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(out_offsets, (links ? ws->edges.loff : ws->edges.off).ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(valid, ws->edges.valid.ptr, n, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (!out) return GBWT_HIP_OK;
         if (capacity < *total) return fail(GBWT_HIP_CAPACITY, links ? "output capacity too small for the links" : "output capacity too small for the edges");
-        if (*total) copy_to_host(ws, out, (links ? ws->tp_links : ws->tp_edges).ptr, *total * sizeof(uint64_t));
+        if (*total) copy_to_host(ws, out, (links ? ws->edges.links : ws->edges.edges).ptr, *total * sizeof(uint64_t));
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         return status_of(e);
@@ -149,10 +145,10 @@ gbwt_hip_status rows_device(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, co
     *out = gbwt_hip_edge_rows{nullptr, nullptr, nullptr, 0, 0};
     const gbwt_hip_status st = rows_compute(ix, ws, ids, orientations, n, predecessors, links);
     if (st != GBWT_HIP_OK) return st;
-    out->d_offsets = (links ? ws->tp_loff : ws->tp_off).as<uint64_t>();
-    out->d_edges = (links ? ws->tp_links : ws->tp_edges).as<uint64_t>();
-    out->d_valid = ws->tp_valid.as<uint8_t>();
-    out->total = ws->tp_total;
+    out->d_offsets = (links ? ws->edges.loff : ws->edges.off).as<uint64_t>();
+    out->d_edges = (links ? ws->edges.links : ws->edges.edges).as<uint64_t>();
+    out->d_valid = ws->edges.valid.as<uint8_t>();
+    out->total = ws->edges.total;
     out->n = n;
     return GBWT_HIP_OK;
 }
@@ -163,8 +159,8 @@ void graph_lines_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const Gr
     const bool translated = t.segments != 0;
     const uint64_t domain = translated ? t.segments : g.slots, queries = 2 * domain;
     if (queries >= 0xFFFFFFFFull) throw Unsupported("too many nodes for the graph lines (32-bit row numbers)");
-    if (const std::string *rs = h.tag("reference_samples")) ws->gt_header = "H\tVN:Z:1.1\tRS:Z:" + *rs + "\n";      // write_gfa_header, src/bin/gbunzip.rs:193-203
-    else ws->gt_header = "H\tVN:Z:1.1\n";
+    if (const std::string *rs = h.tag("reference_samples")) ws->graph_text.header = "H\tVN:Z:1.1\tRS:Z:" + *rs + "\n";      // write_gfa_header, src/bin/gbunzip.rs:193-203
+    else ws->graph_text.header = "H\tVN:Z:1.1\n";
     DeviceBuffer flags, rank, sizes, ids, orient, counts, off, valid, big, cut, lines;
     // 1. the items of the S-lines: the nodes that exist, or the segments whose first node does (GBZ::segment_iter)
     flags.reserve(std::max<uint64_t>(domain, 1) * sizeof(uint64_t));
@@ -174,12 +170,12 @@ void graph_lines_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const Gr
     scan(ws, flags.as<uint64_t>(), rank.as<uint64_t>(), domain, s);
     HIP_CHECK(hipGetLastError());
     const uint64_t items = read_word(rank.as<uint64_t>() + domain, s);
-    ws->gt_items.reserve(std::max<uint64_t>(items, 1) * sizeof(uint64_t));
-    ws->gt_soff.reserve((items + 1) * sizeof(uint64_t));
+    ws->graph_text.items.reserve(std::max<uint64_t>(items, 1) * sizeof(uint64_t));
+    ws->graph_text.soff.reserve((items + 1) * sizeof(uint64_t));
     sizes.reserve(std::max<uint64_t>(items, 1) * sizeof(uint64_t));
-    launch_scatter_ids(rank.as<uint64_t>(), domain, translated ? 0 : g.min_node, ws->gt_items.as<uint64_t>(), s);
-    launch_segment_line_sizes(t, ws->gt_items.as<uint64_t>(), items, translated, sizes.as<uint64_t>(), s);
-    scan(ws, sizes.as<uint64_t>(), ws->gt_soff.as<uint64_t>(), items, s);
+    launch_scatter_ids(rank.as<uint64_t>(), domain, translated ? 0 : g.min_node, ws->graph_text.items.as<uint64_t>(), s);
+    launch_segment_line_sizes(t, ws->graph_text.items.as<uint64_t>(), items, translated, sizes.as<uint64_t>(), s);
+    scan(ws, sizes.as<uint64_t>(), ws->graph_text.soff.as<uint64_t>(), items, s);
     // 2. the edge rows of every (node | segment, orientation), with the row of every edge
     ids.reserve(std::max<uint64_t>(queries, 1) * sizeof(uint64_t));
     orient.reserve(std::max<uint64_t>(queries, 1));
@@ -192,60 +188,60 @@ void graph_lines_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const Gr
     launch_edge_count(ix->dev, ids.as<uint64_t>(), orient.as<uint8_t>(), queries, false, counts.as<uint64_t>(), valid.as<uint8_t>(), s);
     scan(ws, counts.as<uint64_t>(), off.as<uint64_t>(), queries, s);
     HIP_CHECK(hipGetLastError());
-    const uint64_t sbytes = read_word(ws->gt_soff.as<uint64_t>() + items, s);
+    const uint64_t sbytes = read_word(ws->graph_text.soff.as<uint64_t>() + items, s);
     const uint64_t edges = read_word(off.as<uint64_t>() + queries, s);
-    ws->gt_edges.reserve(std::max<uint64_t>(edges, 1) * sizeof(uint64_t));
-    ws->gt_rows.reserve(std::max<uint64_t>(edges, 1) * sizeof(uint32_t));
-    ws->gt_loff.reserve((edges + 1) * sizeof(uint64_t));
-    launch_edge_fill(ix->dev, ids.as<uint64_t>(), orient.as<uint8_t>(), queries, false, off.as<uint64_t>(), ws->gt_edges.as<uint64_t>(), ws->gt_rows.as<uint32_t>(),
+    ws->graph_text.edges.reserve(std::max<uint64_t>(edges, 1) * sizeof(uint64_t));
+    ws->graph_text.rows.reserve(std::max<uint64_t>(edges, 1) * sizeof(uint32_t));
+    ws->graph_text.loff.reserve((edges + 1) * sizeof(uint64_t));
+    launch_edge_fill(ix->dev, ids.as<uint64_t>(), orient.as<uint8_t>(), queries, false, off.as<uint64_t>(), ws->graph_text.edges.as<uint64_t>(), ws->graph_text.rows.as<uint32_t>(),
                      big.as<uint32_t>(), s);
     // 3. the sizes of the L-lines: with a translation a row ends at its first node without a segment (LinkIter)
     if (translated) {
         cut.reserve(std::max<uint64_t>(queries, 1) * sizeof(uint64_t));
-        launch_link_cut(t, off.as<uint64_t>(), ws->gt_edges.as<uint64_t>(), ws->gt_rows.as<uint32_t>(), queries, edges, cut.as<uint64_t>(), s);
+        launch_link_cut(t, off.as<uint64_t>(), ws->graph_text.edges.as<uint64_t>(), ws->graph_text.rows.as<uint32_t>(), queries, edges, cut.as<uint64_t>(), s);
     }
     sizes.reserve(std::max<uint64_t>(edges, 1) * sizeof(uint64_t));
     lines.reserve(sizeof(uint64_t));
     HIP_CHECK(hipMemsetAsync(lines.ptr, 0, sizeof(uint64_t), s));
-    launch_link_line_sizes(t, g, translated, off.as<uint64_t>(), ws->gt_edges.as<uint64_t>(), ws->gt_rows.as<uint32_t>(), edges, translated ? cut.as<uint64_t>() : nullptr,
+    launch_link_line_sizes(t, g, translated, off.as<uint64_t>(), ws->graph_text.edges.as<uint64_t>(), ws->graph_text.rows.as<uint32_t>(), edges, translated ? cut.as<uint64_t>() : nullptr,
                            sizes.as<uint64_t>(), lines.as<uint64_t>(), s);
-    scan(ws, sizes.as<uint64_t>(), ws->gt_loff.as<uint64_t>(), edges, s);
+    scan(ws, sizes.as<uint64_t>(), ws->graph_text.loff.as<uint64_t>(), edges, s);
     HIP_CHECK(hipGetLastError());
-    ws->gt_lbytes = read_word(ws->gt_loff.as<uint64_t>() + edges, s);
-    ws->gt_links = read_word(lines.as<uint64_t>(), s);
-    ws->gt_item_count = items; ws->gt_edge_count = edges; ws->gt_sbytes = sbytes; ws->gt_translated = translated;
-    ws->gt_sized = true;                                   // (the scratch buffers go here: hipFree waits for the stream)
+    ws->graph_text.lbytes = read_word(ws->graph_text.loff.as<uint64_t>() + edges, s);
+    ws->graph_text.links = read_word(lines.as<uint64_t>(), s);
+    ws->graph_text.item_count = items; ws->graph_text.edge_count = edges; ws->graph_text.sbytes = sbytes; ws->graph_text.translated = translated;
+    ws->graph_text.sized = true;                                   // (the scratch buffers go here: hipFree waits for the stream)
 }
 
 gbwt_hip_status graph_lines_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, bool format_again) {
     if (!ix || !ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
     if (!ix->host.is_gbz || !(ix->caps & GBWT_HIP_OPEN_GFA)) return fail(GBWT_HIP_BAD_ARGUMENT, NEEDS_GFA);
-    if (ws->gt_text_valid && !format_again) return GBWT_HIP_OK;
+    if (ws->graph_text.text_valid && !format_again) return GBWT_HIP_OK;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         ensure_labels(ix);
         hipStream_t s = ws->stream;
-        for (auto &e : ws->gt_ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+        ws->graph_text.ev.ensure();
         const GraphTables t = graph_tables(ix, true);
         const ComponentGeometry g = graph_geometry(ix->dev);
-        ws->gt_text_valid = false;
-        ws->gt_timed = false;
-        HIP_CHECK(hipEventRecord(ws->gt_ev[0], s));
-        ws->gt_sized_now = !ws->gt_sized;
-        if (!ws->gt_sized) graph_lines_size(ix, ws, t, g, s);
-        HIP_CHECK(hipEventRecord(ws->gt_ev[1], s));
-        const uint64_t head = ws->gt_header.size();
-        ws->gt_text.reserve(head + ws->gt_sbytes + ws->gt_lbytes + 16);
-        HIP_CHECK(hipMemcpyAsync(ws->gt_text.ptr, ws->gt_header.data(), head, hipMemcpyHostToDevice, s));
-        launch_segment_lines(t, ws->gt_items.as<uint64_t>(), ws->gt_item_count, ws->gt_translated, ws->gt_soff.as<uint64_t>(), head, ws->gt_sbytes, ws->gt_text.as<char>(), s);
-        HIP_CHECK(hipEventRecord(ws->gt_ev[2], s));
-        launch_link_lines(t, g, ws->gt_translated, ws->gt_edges.as<uint64_t>(), ws->gt_rows.as<uint32_t>(), ws->gt_edge_count, ws->gt_loff.as<uint64_t>(), head + ws->gt_sbytes,
-                          ws->gt_text.as<char>(), s);
-        HIP_CHECK(hipEventRecord(ws->gt_ev[3], s));
+        ws->graph_text.text_valid = false;
+        ws->graph_text.timed = false;
+        HIP_CHECK(hipEventRecord(ws->graph_text.ev[0], s));
+        ws->graph_text.sized_now = !ws->graph_text.sized;
+        if (!ws->graph_text.sized) graph_lines_size(ix, ws, t, g, s);
+        HIP_CHECK(hipEventRecord(ws->graph_text.ev[1], s));
+        const uint64_t head = ws->graph_text.header.size();
+        ws->graph_text.text.reserve(head + ws->graph_text.sbytes + ws->graph_text.lbytes + 16);
+        HIP_CHECK(hipMemcpyAsync(ws->graph_text.text.ptr, ws->graph_text.header.data(), head, hipMemcpyHostToDevice, s));
+        launch_segment_lines(t, ws->graph_text.items.as<uint64_t>(), ws->graph_text.item_count, ws->graph_text.translated, ws->graph_text.soff.as<uint64_t>(), head, ws->graph_text.sbytes, ws->graph_text.text.as<char>(), s);
+        HIP_CHECK(hipEventRecord(ws->graph_text.ev[2], s));
+        launch_link_lines(t, g, ws->graph_text.translated, ws->graph_text.edges.as<uint64_t>(), ws->graph_text.rows.as<uint32_t>(), ws->graph_text.edge_count, ws->graph_text.loff.as<uint64_t>(), head + ws->graph_text.sbytes,
+                          ws->graph_text.text.as<char>(), s);
+        HIP_CHECK(hipEventRecord(ws->graph_text.ev[3], s));
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
-        ws->gt_text_valid = true;
-        ws->gt_timed = true;
+        ws->graph_text.text_valid = true;
+        ws->graph_text.timed = true;
         return GBWT_HIP_OK;
     } catch (const InvalidData &e) {
         return fail(GBWT_HIP_BAD_ARGUMENT, e.what());
@@ -361,7 +357,7 @@ gbwt_hip_status gbwt_hip_graph_lines_device(const gbwt_hip_index *ix, gbwt_hip_w
     *out = gbwt_hip_graph_text{nullptr, 0, 0, 0, 0, 0};
     const gbwt_hip_status st = graph_lines_compute(ix, ws, true);
     if (st != GBWT_HIP_OK) return st;
-    *out = gbwt_hip_graph_text{ws->gt_text.as<char>(), ws->gt_header.size(), ws->gt_sbytes, ws->gt_lbytes, ws->gt_item_count, ws->gt_links};
+    *out = gbwt_hip_graph_text{ws->graph_text.text.as<char>(), ws->graph_text.header.size(), ws->graph_text.sbytes, ws->graph_text.lbytes, ws->graph_text.item_count, ws->graph_text.links};
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
@@ -372,12 +368,12 @@ gbwt_hip_status gbwt_hip_graph_lines(const gbwt_hip_index *ix, gbwt_hip_workspac
     *total = 0;
     const gbwt_hip_status st = graph_lines_compute(ix, ws, false);
     if (st != GBWT_HIP_OK) return st;
-    *total = ws->gt_header.size() + ws->gt_sbytes + ws->gt_lbytes;
+    *total = ws->graph_text.header.size() + ws->graph_text.sbytes + ws->graph_text.lbytes;
     if (!out) return GBWT_HIP_OK;
     if (capacity < *total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the graph lines");
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        copy_to_host(ws, out, ws->gt_text.ptr, *total);
+        copy_to_host(ws, out, ws->graph_text.text.ptr, *total);
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         return status_of(e);
@@ -387,11 +383,11 @@ gbwt_hip_status gbwt_hip_graph_lines(const gbwt_hip_index *ix, gbwt_hip_workspac
 
 gbwt_hip_status gbwt_hip_last_graph_ms(const gbwt_hip_workspace *ws, float *size_ms, float *segments_ms, float *links_ms) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->gt_timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed graph lines request on this workspace");
+    if (!ws || !ws->graph_text.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed graph lines request on this workspace");
     float ms[3] = {0, 0, 0};
     for (int k = 0; k < 3; k++)
-        if (hipEventElapsedTime(&ms[k], ws->gt_ev[k], ws->gt_ev[k + 1]) != hipSuccess) return fail(GBWT_HIP_DEVICE_ERROR, "hipEventElapsedTime failed");
-    if (size_ms) *size_ms = ws->gt_sized_now ? ms[0] : 0.0f;
+        if (hipEventElapsedTime(&ms[k], ws->graph_text.ev[k], ws->graph_text.ev[k + 1]) != hipSuccess) return fail(GBWT_HIP_DEVICE_ERROR, "hipEventElapsedTime failed");
+    if (size_ms) *size_ms = ws->graph_text.sized_now ? ms[0] : 0.0f;
     if (segments_ms) *segments_ms = ms[1];
     if (links_ms) *links_ms = ms[2];
     return GBWT_HIP_OK;

@@ -388,22 +388,22 @@ gbwt_hip_status gbwt_hip_comm_last(const gbwt_hip_comm *comm, gbwt_hip_comm_stat
 
 gbwt_hip_status gbwt_hip_gather_rows(gbwt_hip_comm *comm, const gbwt_hip_index *ix, gbwt_hip_workspace *ws, int root, int interleaved, gbwt_hip_paths *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!comm || !ix || !ws || ws->index != ix || !ws->timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
+    if (!comm || !ix || !ws || ws->index != ix || !ws->extract.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident extraction on this workspace");
     if (out) *out = gbwt_hip_paths{nullptr, nullptr, 0, 0};
     if (comm->device != ix->device) return fail(GBWT_HIP_BAD_ARGUMENT, "communicator and index are on different devices");
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        const uint64_t n = ws->last_n;
-        ws->lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
-        if (n) hipLaunchKernelGGL(k_row_lengths, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, comm->stream, ws->offsets.as<uint64_t>(), n, ws->lengths.as<uint64_t>());
+        const uint64_t n = ws->extract.last_n;
+        ws->extract.lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+        if (n) hipLaunchKernelGGL(k_row_lengths, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, comm->stream, ws->extract.offsets.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>());
     } catch (const HipError &e) {
         return gbwt_hip::status_of(e);
     }
     const uint64_t *offsets = nullptr;
     const void *payload = nullptr;
     uint64_t rows = 0, units = 0;
-    const gbwt_hip_status st = gather(comm, ws->lengths.as<uint64_t>(), ws->last_n, ws->nodes.ptr, ws->last_total, sizeof(uint32_t), root, interleaved,
-                                      ws->nodes.reserved != 0, &offsets, &payload, &rows, &units);
+    const gbwt_hip_status st = gather(comm, ws->extract.lengths.as<uint64_t>(), ws->extract.last_n, ws->extract.nodes.ptr, ws->extract.last_total, sizeof(uint32_t), root, interleaved,
+                                      ws->extract.nodes.reserved != 0, &offsets, &payload, &rows, &units);
     if (st == GBWT_HIP_OK && out) *out = gbwt_hip_paths{offsets, static_cast<const uint32_t *>(payload), units, rows};
     return st;
     GBWT_HIP_GUARD_END
@@ -411,23 +411,23 @@ gbwt_hip_status gbwt_hip_gather_rows(gbwt_hip_comm *comm, const gbwt_hip_index *
 
 gbwt_hip_status gbwt_hip_gather_lines(gbwt_hip_comm *comm, const gbwt_hip_index *ix, gbwt_hip_workspace *ws, int root, int interleaved, gbwt_hip_lines *out) {
     GBWT_HIP_GUARD_BEGIN
-    if (!comm || !ix || !ws || ws->index != ix || !ws->lines_cached || ws->lines_slot != 0)
+    if (!comm || !ix || !ws || ws->index != ix || !ws->lines.memo.valid() || ws->lines.slot != 0)
         return fail(GBWT_HIP_BAD_ARGUMENT, "no device-resident GFA lines on this workspace (gbwt_hip_path_lines_device first)");
     if (interleaved == GBWT_HIP_GATHER_PARTS) return fail(GBWT_HIP_BAD_ARGUMENT, "GFA lines are not cut into parts: shard them by path");
     if (out) *out = gbwt_hip_lines{nullptr, nullptr, 0, 0};
     if (comm->device != ix->device) return fail(GBWT_HIP_BAD_ARGUMENT, "communicator and index are on different devices");
-    const uint64_t n = ws->lines_key.size();
+    const uint64_t n = ws->lines.n;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        ws->lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
-        if (n) hipLaunchKernelGGL(k_row_lengths, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, comm->stream, ws->gfa_b.as<uint64_t>(), n, ws->lengths.as<uint64_t>());
+        ws->extract.lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+        if (n) hipLaunchKernelGGL(k_row_lengths, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, comm->stream, ws->lines.b.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>());
     } catch (const HipError &e) {
         return gbwt_hip::status_of(e);
     }
     const uint64_t *offsets = nullptr;
     const void *payload = nullptr;
     uint64_t rows = 0, units = 0;
-    const gbwt_hip_status st = gather(comm, ws->lengths.as<uint64_t>(), n, n ? ws->gfa_text.ptr : nullptr, ws->lines_total, 1, root, interleaved, false, &offsets, &payload, &rows, &units);
+    const gbwt_hip_status st = gather(comm, ws->extract.lengths.as<uint64_t>(), n, n ? ws->lines.text.ptr : nullptr, ws->lines.total, 1, root, interleaved, false, &offsets, &payload, &rows, &units);
     if (st == GBWT_HIP_OK && out) *out = gbwt_hip_lines{static_cast<const char *>(payload), offsets, units, rows};
     return st;
     GBWT_HIP_GUARD_END

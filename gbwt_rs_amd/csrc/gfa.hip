@@ -741,8 +741,8 @@ void fill_line_cache_at_open(gbwt_hip_index &ix) {
 }
 }  // namespace gbwt_hip
 
-// The lines of a batch of paths, formatted ONCE into device memory (the text buffer of `slot`: ws->gfa_text or gfa_text2; line k at
-// [line_start[k], line_start[k + 1]), offsets also on the device in ws->gfa_b).  The request is remembered in the workspace: the fill call that
+// The lines of a batch of paths, formatted ONCE into device memory (the text buffer of `slot`: ws->lines.text or text2; line k at
+// [line_start[k], line_start[k + 1]), offsets also on the device in ws->lines.b).  The request is remembered in the workspace: the fill call that
 // follows a size query, and the copy-out of gbwt_hip_path_lines after gbwt_hip_path_lines_device, find the text there.
 //
 // Everything between the walk and the text stays on the device (round 4): chunk counts, per-chunk sizes, their scans, the line lengths --
@@ -755,19 +755,18 @@ static gbwt_hip_status path_lines_compute(const gbwt_hip_index *ix, gbwt_hip_wor
     if (n && !path_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null path_ids");
     if (mode < 0 || mode > 2) return fail(GBWT_HIP_BAD_ARGUMENT, "mode must be 0 (P-lines), 1 (W-lines) or 2 (P-lines with PanSN names)");
     const int p_lines = mode != 1 ? 1 : 0;
-    if (ws->lines_cached && ws->lines_mode == mode && ws->lines_slot == slot && ws->lines_key.size() == n &&
-        (n == 0 || std::memcmp(ws->lines_key.data(), path_ids, n * sizeof(uint64_t)) == 0))
-        return GBWT_HIP_OK;
-    ws->lines_cached = false;
+    const auto remember = [&] { ws->lines.memo.store({{path_ids, n * sizeof(uint64_t)}}, {mode, slot}); ws->lines.n = n; ws->lines.slot = slot; };
+    if (ws->lines.memo.matches({{path_ids, n * sizeof(uint64_t)}}, {mode, slot})) return GBWT_HIP_OK;
+    ws->lines.memo.drop();
     try {
         require_gfa_capable(ix);
         const HostIndex &h = ix->host;
         const bool translated = h.has_translation && !h.segment_starts.empty();
         for (uint64_t k = 0; k < n; k++)
             if (path_ids[k] >= h.path_names.size()) return fail(GBWT_HIP_BAD_ARGUMENT, "path id out of range");
-        ws->lines_total = 0;
+        ws->lines.total = 0;
         if (n == 0) {
-            ws->lines_key.clear(); ws->lines_mode = mode; ws->lines_slot = slot; ws->lines_cached = true;
+            remember();
             return GBWT_HIP_OK;
         }
         // 1. forward sequences of the paths (GBZ::path(id, Forward), src/bin/gbunzip.rs:462, 532)
@@ -778,32 +777,32 @@ static gbwt_hip_status path_lines_compute(const gbwt_hip_index *ix, gbwt_hip_wor
         if (st != GBWT_HIP_OK) return st;
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
-        for (auto &e : ws->gev) if (!e) HIP_CHECK(hipEventCreate(&e));
-        HIP_CHECK(hipEventRecord(ws->gev[0], s));
-        const uint64_t *d_seq_ids = ws->seq_ids.as<uint64_t>();         // (the extraction has left the ids on the device)
+        ws->lines.ev.ensure();
+        HIP_CHECK(hipEventRecord(ws->lines.ev[0], s));
+        const uint64_t *d_seq_ids = ws->extract.seq_ids.as<uint64_t>();         // (the extraction has left the ids on the device)
         // 2. size of every line: chunks of LINE_CHUNK positions, a wave per chunk, scans over the chunks.  Every row has at least one chunk
         // and at most len / LINE_CHUNK + 1: the launches and scans below run over that bound, the kernels read the count from the device.
         const uint64_t chunks_cap = paths.total / LINE_CHUNK + n;
         if (chunks_cap > 0x7FFFFFFFull) return fail(GBWT_HIP_UNSUPPORTED, "too many line chunks in one batch: format fewer paths per call");
         const size_t tb = scan_temp_bytes(std::max(n, chunks_cap));
-        ws->gfa_a.reserve(2 * n * sizeof(uint64_t));
-        ws->gfa_b.reserve((n + 1) * sizeof(uint64_t));
-        ws->gfa_chunk_first.reserve(2 * (n + 1) * sizeof(uint64_t));
-        ws->gfa_chunks.reserve((3 * chunks_cap + 3 * (chunks_cap + 1)) * sizeof(uint64_t) + (chunks_cap + 1) * sizeof(uint32_t));
-        ws->scan_temp.reserve(std::max<size_t>(tb, 16));
-        ws->gfa_valid.reserve(std::max<uint64_t>(n, 16));
-        uint64_t *d_line_len = ws->gfa_a.as<uint64_t>(), *d_line_end = d_line_len + n, *d_line_start = ws->gfa_b.as<uint64_t>();
-        uint64_t *d_chunk_first = ws->gfa_chunk_first.as<uint64_t>(), *d_chunk_counts = d_chunk_first + (n + 1);
-        uint64_t *d_chunk_text = ws->gfa_chunks.as<uint64_t>(), *d_chunk_seq = d_chunk_text + chunks_cap, *d_chunk_bad = d_chunk_seq + chunks_cap;
+        ws->scratch.a.reserve(2 * n * sizeof(uint64_t));
+        ws->lines.b.reserve((n + 1) * sizeof(uint64_t));
+        ws->scratch.chunk_first.reserve(2 * (n + 1) * sizeof(uint64_t));
+        ws->scratch.chunks.reserve((3 * chunks_cap + 3 * (chunks_cap + 1)) * sizeof(uint64_t) + (chunks_cap + 1) * sizeof(uint32_t));
+        ws->scratch.scan_temp.reserve(std::max<size_t>(tb, 16));
+        ws->lines.valid.reserve(std::max<uint64_t>(n, 16));
+        uint64_t *d_line_len = ws->scratch.a.as<uint64_t>(), *d_line_end = d_line_len + n, *d_line_start = ws->lines.b.as<uint64_t>();
+        uint64_t *d_chunk_first = ws->scratch.chunk_first.as<uint64_t>(), *d_chunk_counts = d_chunk_first + (n + 1);
+        uint64_t *d_chunk_text = ws->scratch.chunks.as<uint64_t>(), *d_chunk_seq = d_chunk_text + chunks_cap, *d_chunk_bad = d_chunk_seq + chunks_cap;
         uint64_t *d_text_before = d_chunk_bad + chunks_cap, *d_seq_before = d_text_before + (chunks_cap + 1), *d_bad_before = d_seq_before + (chunks_cap + 1);
         uint32_t *d_chunk_path = reinterpret_cast<uint32_t *>(d_bad_before + (chunks_cap + 1));
-        uint8_t *d_valid = translated ? ws->gfa_valid.as<uint8_t>() : nullptr;
+        uint8_t *d_valid = translated ? ws->lines.valid.as<uint8_t>() : nullptr;
         const LineHeaders hdr{ix->line_prefix[mode].as<uint8_t>(), ix->line_prefix_off[mode].as<uint64_t>(), mode == 1 ? ix->line_fragment.as<uint32_t>() : nullptr};
         // the line cache of the index (filled at open): nothing below reads a node id before the formatter does
         const bool all_cached = !translated && ix->lc_state == 1;
         const LineCache cache{ix->lc_chunk_first.as<uint64_t>(), ix->lc_text.as<uint64_t>(), ix->lc_path.as<uint64_t>()};
         hipLaunchKernelGGL(k_chunk_counts, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, paths.d_offsets, n, d_chunk_counts);
-        launch_scan(d_chunk_counts, d_chunk_first, n, ws->scan_temp.ptr, tb, s);
+        launch_scan(d_chunk_counts, d_chunk_first, n, ws->scratch.scan_temp.ptr, tb, s);
         hipLaunchKernelGGL(k_chunk_paths, dim3(static_cast<unsigned>((chunks_cap + 255) / 256)), dim3(256), 0, s, d_chunk_first, n, chunks_cap, d_chunk_path);
         const unsigned stat_blocks = static_cast<unsigned>((chunks_cap + 3) / 4);
         if (all_cached) {
@@ -812,18 +811,18 @@ static gbwt_hip_status path_lines_compute(const gbwt_hip_index *ix, gbwt_hip_wor
             if (translated) {
                 hipLaunchKernelGGL(k_chunk_stats_segments, dim3(stat_blocks), dim3(256), 0, s, paths.d_offsets, paths.d_nodes, n, d_chunk_first, d_chunk_path, chunks_cap,
                                    segment_tables(ix), p_lines, d_chunk_text, d_chunk_seq, d_chunk_bad);
-                launch_scan(d_chunk_bad, d_bad_before, chunks_cap, ws->scan_temp.ptr, tb, s);
+                launch_scan(d_chunk_bad, d_bad_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s);
             } else {
                 hipLaunchKernelGGL(k_chunk_stats, dim3(stat_blocks), dim3(256), 0, s, paths.d_offsets, paths.d_nodes, n, d_chunk_first, d_chunk_path, chunks_cap,
                                    ix->label_len.as<uint32_t>(), static_cast<uint64_t>(h.sequences_labels.size()),
                                    static_cast<uint32_t>(h.alphabet_offset + 1), p_lines, d_chunk_text, d_chunk_seq);
             }
-            launch_scan(d_chunk_text, d_text_before, chunks_cap, ws->scan_temp.ptr, tb, s);
-            launch_scan(d_chunk_seq, d_seq_before, chunks_cap, ws->scan_temp.ptr, tb, s);
+            launch_scan(d_chunk_text, d_text_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s);
+            launch_scan(d_chunk_seq, d_seq_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s);
             hipLaunchKernelGGL(k_line_sizes, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, d_seq_ids, d_chunk_first, n, d_text_before, d_seq_before,
                                translated ? d_bad_before : nullptr, hdr, p_lines, d_line_len, d_line_end, d_valid);
         }
-        launch_scan(d_line_len, d_line_start, n, ws->scan_temp.ptr, tb, s);
+        launch_scan(d_line_len, d_line_start, n, ws->scratch.scan_temp.ptr, tb, s);
         uint64_t total = 0;
         std::vector<uint8_t> valid;
         HIP_CHECK(hipMemcpyAsync(&total, d_line_start + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -866,31 +865,28 @@ static gbwt_hip_status path_lines_compute(const gbwt_hip_index *ix, gbwt_hip_wor
             HIP_CHECK(hipMemcpyAsync(d_line_start, line_start.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         }
         // 3. format on the device; the lines the host had to replay are copied into their places
-        DeviceBuffer &text = slot == 0 ? ws->gfa_text : ws->gfa_text2;
+        DeviceBuffer &text = slot == 0 ? ws->lines.text : ws->lines.text2;
         text.reserve(std::max<uint64_t>(total, 16));
         if (translated)
             hipLaunchKernelGGL(k_format_chunks_segments, dim3(static_cast<unsigned>(chunks_cap)), dim3(FORMAT_THREADS), 0, s, paths.d_offsets, paths.d_nodes, n,
                                d_chunk_first, d_chunk_path, d_text_before, segment_tables(ix), p_lines, d_valid, d_line_start, d_seq_ids, hdr, d_line_end, text.as<uint8_t>());
         else {
             const auto kernel = k_format_chunks<4>;   // (eight positions per thread: five waves per SIMD, 23 % slower)
-            ws->gfa_plan.reserve(chunks_cap * sizeof(ChunkPlan));
+            ws->scratch.plan.reserve(chunks_cap * sizeof(ChunkPlan));
             hipLaunchKernelGGL(k_plan_chunks, dim3(static_cast<unsigned>((chunks_cap + 255) / 256)), dim3(256), 0, s, paths.d_offsets, n, d_chunk_first, d_chunk_path, chunks_cap,
-                               d_text_before, p_lines, d_line_start, d_seq_ids, hdr, d_line_end, all_cached ? cache : LineCache{nullptr, nullptr, nullptr}, ws->gfa_plan.as<ChunkPlan>());
-            hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(chunks_cap)), dim3(FORMAT_THREADS), 0, s, paths.d_nodes, n, d_chunk_first, ws->gfa_plan.as<ChunkPlan>(), p_lines,
+                               d_text_before, p_lines, d_line_start, d_seq_ids, hdr, d_line_end, all_cached ? cache : LineCache{nullptr, nullptr, nullptr}, ws->scratch.plan.as<ChunkPlan>());
+            hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(chunks_cap)), dim3(FORMAT_THREADS), 0, s, paths.d_nodes, n, d_chunk_first, ws->scratch.plan.as<ChunkPlan>(), p_lines,
                                d_seq_ids, hdr, d_line_end, text.as<uint8_t>());
         }
         HIP_CHECK(hipGetLastError());
         for (uint64_t k = 0; k < host_lines.size(); k++)
             if (!valid[k] && !host_lines[k].empty())
                 HIP_CHECK(hipMemcpyAsync(text.as<char>() + line_start[k], host_lines[k].data(), host_lines[k].size(), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipEventRecord(ws->gev[1], s));
+        HIP_CHECK(hipEventRecord(ws->lines.ev[1], s));
         HIP_CHECK(hipStreamSynchronize(s));   // the text is there when the call returns (and host_lines / line_start go out of scope)
-        ws->lines_timed = true;
-        ws->lines_total = total;
-        ws->lines_key.assign(path_ids, path_ids + n);
-        ws->lines_mode = mode;
-        ws->lines_slot = slot;
-        ws->lines_cached = true;
+        ws->lines.timed = true;
+        ws->lines.total = total;
+        remember();
         return GBWT_HIP_OK;
     } catch (const InvalidData &e) {
         return fail(GBWT_HIP_BAD_ARGUMENT, e.what());
@@ -907,12 +903,12 @@ static gbwt_hip_status path_lines_impl(const gbwt_hip_index *ix, gbwt_hip_worksp
     *total = 0;
     const gbwt_hip_status st = path_lines_compute(ix, ws, path_ids, n, mode);
     if (st != GBWT_HIP_OK) return st;
-    *total = ws->lines_total;
+    *total = ws->lines.total;
     if (!out || *total == 0) return GBWT_HIP_OK;
     if (capacity < *total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the lines");
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        copy_to_host(ws, out, ws->gfa_text.ptr, *total);
+        copy_to_host(ws, out, ws->lines.text.ptr, *total);
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         return status_of(e);
@@ -1074,9 +1070,9 @@ gbwt_hip_status gbwt_hip_path_lines_device(const gbwt_hip_index *ix, gbwt_hip_wo
     *out = gbwt_hip_lines{nullptr, nullptr, 0, 0};
     const gbwt_hip_status st = path_lines_compute(ix, ws, path_ids, n, mode);
     if (st != GBWT_HIP_OK) return st;
-    out->d_text = n ? ws->gfa_text.as<char>() : nullptr;
-    out->d_line_offsets = n ? ws->gfa_b.as<uint64_t>() : nullptr;
-    out->total = ws->lines_total;
+    out->d_text = n ? ws->lines.text.as<char>() : nullptr;
+    out->d_line_offsets = n ? ws->lines.b.as<uint64_t>() : nullptr;
+    out->total = ws->lines.total;
     out->n = n;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
@@ -1098,31 +1094,31 @@ gbwt_hip_status gbwt_hip_segment_paths(const gbwt_hip_index *ix, gbwt_hip_worksp
         gbwt_hip_paths paths{};
         const gbwt_hip_status st = gbwt_hip_extract_device(ix, ws, seq_ids, n, &paths);
         if (st != GBWT_HIP_OK) return st;
-        ws->lines_cached = false;                                        // (the line buffers of the workspace are used below)
+        ws->lines.memo.drop();                                           // (the line buffers of the workspace are used below)
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
         const uint64_t chunks_cap = paths.total / LINE_CHUNK + n;
         if (chunks_cap > 0x7FFFFFFFull) return fail(GBWT_HIP_UNSUPPORTED, "too many chunks in one batch: ask for fewer paths per call");
         const size_t tb = scan_temp_bytes(std::max(n, chunks_cap));
-        ws->gfa_a.reserve(2 * (n + 1) * sizeof(uint64_t));
-        ws->gfa_chunk_first.reserve(2 * (n + 1) * sizeof(uint64_t));
-        ws->gfa_chunks.reserve((2 * chunks_cap + 2 * (chunks_cap + 1)) * sizeof(uint64_t) + (chunks_cap + 1) * sizeof(uint32_t));
-        ws->scan_temp.reserve(std::max<size_t>(tb, 16));
-        ws->gfa_valid.reserve(std::max<uint64_t>(n, 16));
-        uint64_t *d_row_tokens = ws->gfa_a.as<uint64_t>(), *d_row_start = d_row_tokens + (n + 1);
-        uint64_t *d_chunk_first = ws->gfa_chunk_first.as<uint64_t>(), *d_chunk_counts = d_chunk_first + (n + 1);
-        uint64_t *d_chunk_tokens = ws->gfa_chunks.as<uint64_t>(), *d_chunk_bad = d_chunk_tokens + chunks_cap, *d_tokens_before = d_chunk_bad + chunks_cap,
+        ws->scratch.a.reserve(2 * (n + 1) * sizeof(uint64_t));
+        ws->scratch.chunk_first.reserve(2 * (n + 1) * sizeof(uint64_t));
+        ws->scratch.chunks.reserve((2 * chunks_cap + 2 * (chunks_cap + 1)) * sizeof(uint64_t) + (chunks_cap + 1) * sizeof(uint32_t));
+        ws->scratch.scan_temp.reserve(std::max<size_t>(tb, 16));
+        ws->lines.valid.reserve(std::max<uint64_t>(n, 16));
+        uint64_t *d_row_tokens = ws->scratch.a.as<uint64_t>(), *d_row_start = d_row_tokens + (n + 1);
+        uint64_t *d_chunk_first = ws->scratch.chunk_first.as<uint64_t>(), *d_chunk_counts = d_chunk_first + (n + 1);
+        uint64_t *d_chunk_tokens = ws->scratch.chunks.as<uint64_t>(), *d_chunk_bad = d_chunk_tokens + chunks_cap, *d_tokens_before = d_chunk_bad + chunks_cap,
                  *d_bad_before = d_tokens_before + (chunks_cap + 1);
         uint32_t *d_chunk_path = reinterpret_cast<uint32_t *>(d_bad_before + (chunks_cap + 1));
-        uint8_t *d_valid = ws->gfa_valid.as<uint8_t>();
+        uint8_t *d_valid = ws->lines.valid.as<uint8_t>();
         const SegmentTables tables = segment_tables(ix);
         hipLaunchKernelGGL(k_chunk_counts, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, paths.d_offsets, n, d_chunk_counts);
-        launch_scan(d_chunk_counts, d_chunk_first, n, ws->scan_temp.ptr, tb, s);
+        launch_scan(d_chunk_counts, d_chunk_first, n, ws->scratch.scan_temp.ptr, tb, s);
         hipLaunchKernelGGL(k_chunk_paths, dim3(static_cast<unsigned>((chunks_cap + 255) / 256)), dim3(256), 0, s, d_chunk_first, n, chunks_cap, d_chunk_path);
         hipLaunchKernelGGL(k_segment_chunk_tokens, dim3(static_cast<unsigned>((chunks_cap + 3) / 4)), dim3(256), 0, s, paths.d_offsets, paths.d_nodes, n, d_chunk_first, d_chunk_path, chunks_cap,
                            tables, d_chunk_tokens, d_chunk_bad);
-        launch_scan(d_chunk_tokens, d_tokens_before, chunks_cap, ws->scan_temp.ptr, tb, s);
-        launch_scan(d_chunk_bad, d_bad_before, chunks_cap, ws->scan_temp.ptr, tb, s);
+        launch_scan(d_chunk_tokens, d_tokens_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s);
+        launch_scan(d_chunk_bad, d_bad_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s);
         hipLaunchKernelGGL(k_segment_row_tokens, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, d_chunk_first, n, d_tokens_before, d_bad_before, d_row_tokens, d_valid);
         std::vector<uint64_t> counts(n), offs(n + 1);
         std::vector<uint8_t> valid(n);
@@ -1147,11 +1143,11 @@ gbwt_hip_status gbwt_hip_segment_paths(const gbwt_hip_index *ix, gbwt_hip_worksp
         *total = out_offsets[n];
         if (!out_tokens || *total == 0) return GBWT_HIP_OK;               // the size query
         if (capacity < *total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the segment tokens");
-        ws->gfa_text.reserve(std::max<uint64_t>(*total, 1) * sizeof(uint64_t));
+        ws->lines.text.reserve(std::max<uint64_t>(*total, 1) * sizeof(uint64_t));
         HIP_CHECK(hipMemcpyAsync(d_row_start, out_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_segment_fill_tokens, dim3(static_cast<unsigned>(chunks_cap)), dim3(FORMAT_THREADS), 0, s, paths.d_offsets, paths.d_nodes, n, d_chunk_first, d_chunk_path,
-                           d_tokens_before, tables, d_valid, d_row_start, ws->gfa_text.as<uint64_t>());
-        HIP_CHECK(hipMemcpyAsync(out_tokens, ws->gfa_text.ptr, *total * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                           d_tokens_before, tables, d_valid, d_row_start, ws->lines.text.as<uint64_t>());
+        HIP_CHECK(hipMemcpyAsync(out_tokens, ws->lines.text.ptr, *total * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         HIP_CHECK(hipGetLastError());
         for (uint64_t k = 0; k < n; k++)
@@ -1165,9 +1161,9 @@ gbwt_hip_status gbwt_hip_segment_paths(const gbwt_hip_index *ix, gbwt_hip_worksp
 
 gbwt_hip_status gbwt_hip_last_lines_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *format_ms) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->lines_timed || !ws->timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed GFA lines request on this workspace");
+    if (!ws || !ws->lines.timed || !ws->extract.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed GFA lines request on this workspace");
     float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, ws->ev[0], ws->ev[1]) != hipSuccess || hipEventElapsedTime(&b, ws->gev[0], ws->gev[1]) != hipSuccess)
+    if (hipEventElapsedTime(&a, ws->extract.ev[0], ws->extract.ev[1]) != hipSuccess || hipEventElapsedTime(&b, ws->lines.ev[0], ws->lines.ev[1]) != hipSuccess)
         return fail(GBWT_HIP_DEVICE_ERROR, "hipEventElapsedTime failed");
     if (walk_ms) *walk_ms = a;
     if (format_ms) *format_ms = b;
@@ -1237,14 +1233,14 @@ gbwt_hip_status gbwt_hip_write_gfa_mode(const gbwt_hip_index *ix, gbwt_hip_works
                 if (!writer.acquire(slot)) { st = GBWT_HIP_IO_ERROR; break; }
                 st = path_lines_compute(ix, ws, ids.data() + b0, nb, pass.line_mode, slot);
                 if (st != GBWT_HIP_OK) break;
-                writer.submit((slot == 0 ? ws->gfa_text : ws->gfa_text2).as<char>(), ws->lines_total, slot);
+                writer.submit((slot == 0 ? ws->lines.text : ws->lines.text2).as<char>(), ws->lines.total, slot);
                 slot ^= 1;
                 b0 += nb;
             }
             if (st != GBWT_HIP_OK) break;
         }
         const gbwt_hip_status wst = writer.finish();
-        ws->lines_cached = false;                            // (both text buffers have been reused)
+        ws->lines.memo.drop();                               // (both text buffers have been reused)
         if (st == GBWT_HIP_OK && wst != GBWT_HIP_OK) return fail(wst, writer.message);
         if (st != GBWT_HIP_OK) return wst != GBWT_HIP_OK ? fail(wst, writer.message) : st;
         if (file.failed) return fail(GBWT_HIP_IO_ERROR, "short write");

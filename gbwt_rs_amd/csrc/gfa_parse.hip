@@ -622,13 +622,7 @@ struct Buf {
     template <class T> T *as() const { return static_cast<T *>(ptr); }
 };
 
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() { HIP_CHECK(hipEventCreate(&e)); }
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    Event(const Event &) = delete;
-    Event &operator=(const Event &) = delete;
-};
+using Event = EventSet<1>;
 
 inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return static_cast<unsigned>(std::max<uint64_t>(1, (items + per_block - 1) / per_block)); }
 
@@ -697,7 +691,7 @@ void GfaDeviceParse::rows() {
     HIP_CHECK(hipMemsetAsync(m.err(), 0xFF, sizeof(u64), s));
     m.offsets.alloc(m.tally, sizeof(uint64_t), false);
     HIP_CHECK(hipMemsetAsync(m.offsets.ptr, 0, sizeof(uint64_t), s));
-    HIP_CHECK(hipEventRecord(e0.e, s));
+    HIP_CHECK(hipEventRecord(e0[0], s));
     if (m.tiles == 0) { HIP_CHECK(hipStreamSynchronize(s)); peak_bytes = m.tally.peak; return; }
 
     // -- structure
@@ -752,7 +746,7 @@ void GfaDeviceParse::rows() {
     hipLaunchKernelGGL(k_gfa_gather_lines, dim3(line_blocks), dim3(THREADS), 0, s, m.nl_pos.as<uint64_t>(), L, m.tab_pos.as<uint64_t>(), m.tables, counts.p_lines,
                        headers.as<uint64_t>(), m.seg_id.as<uint32_t>(), m.seg_line.as<uint32_t>(), m.present.as<uint32_t>(), paths.as<GfaPathLine>());
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e1.e, s));
+    HIP_CHECK(hipEventRecord(e1[0], s));
     path_lines.resize(n_paths);
     if (n_paths) HIP_CHECK(hipMemcpyAsync(path_lines.data(), paths.ptr, n_paths * sizeof(GfaPathLine), hipMemcpyDeviceToHost, s));
     std::vector<uint64_t> h(2 * counts.headers);
@@ -801,18 +795,18 @@ void GfaDeviceParse::rows() {
             HIP_CHECK(hipStreamSynchronize(s));
         }
     }
-    HIP_CHECK(hipEventRecord(e2.e, s));
+    HIP_CHECK(hipEventRecord(e2[0], s));
     u64 word = 0;
     HIP_CHECK(hipMemcpyAsync(&word, m.err(), sizeof(u64), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipEventElapsedTime(&structure_ms, e0.e, e1.e));
-    HIP_CHECK(hipEventElapsedTime(&steps_ms, e1.e, e2.e));
+    HIP_CHECK(hipEventElapsedTime(&structure_ms, e0[0], e1[0]));
+    HIP_CHECK(hipEventElapsedTime(&steps_ms, e1[0], e2[0]));
     if (word != ~u64(0)) { refusal.line = (word >> 8) + 1; refusal.code = static_cast<uint32_t>(word & 0xFF); }
     else if (translated) {
         // the alphabet is all the nodes, visited or not: the mapping of a GBZ has one slot per potential node
         min_node = 2; max_node = static_cast<uint32_t>(2 * total_nodes + 1);
-        HIP_CHECK(hipEventElapsedTime(&names_ms, e_names0.e, e_names1.e));
-        HIP_CHECK(hipEventElapsedTime(&expand_ms, e_expand0.e, e_expand1.e));
+        HIP_CHECK(hipEventElapsedTime(&names_ms, e_names0[0], e_names1[0]));
+        HIP_CHECK(hipEventElapsedTime(&expand_ms, e_expand0[0], e_expand1[0]));
     } else if (counts.steps) build_node_range(m.nodes.as<uint32_t>(), counts.steps, min_node, max_node, s);
     // what only the steps needed
     m.tile_nl.release(); m.tile_p.release(); m.tile_w.release(); m.nl_pos.release(); m.tab_pos.release(); m.first_tab.release(); m.present.release();
@@ -831,7 +825,7 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
     if (T + 1 > GFA_MAX_LINES) throw Unsupported("more than 2^31 - 2 steps are not supported");
 
     // -- names: the plan of the segments and the table of their names
-    HIP_CHECK(hipEventRecord(e_names0.e, s));
+    HIP_CHECK(hipEventRecord(e_names0[0], s));
     const uint32_t bits = gfa_bucket_bits(S);
     const uint64_t buckets = (uint64_t(1) << bits) + 1;
     Buf hash_in, rank_in;
@@ -860,7 +854,7 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
     HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_gfa_name_buckets, dim3(blocks_for(buckets, THREADS)), dim3(THREADS), 0, s, m.hash.as<uint64_t>(), S, bits, m.bucket.as<uint32_t>());
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e_names1.e, s));
+    HIP_CHECK(hipEventRecord(e_names1[0], s));
     out.table_bytes = S * (2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) + buckets * sizeof(uint32_t);
 
     // -- steps: (segment, orientation) and the node count of every token
@@ -881,7 +875,7 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
     out.chopped_segments = chopped;
 
     // -- expand: every step becomes the nodes of its segment
-    HIP_CHECK(hipEventRecord(e_expand0.e, s));
+    HIP_CHECK(hipEventRecord(e_expand0[0], s));
     out.row_nodes = 0;
     m.offsets.alloc(m.tally, (n_paths + 1) * sizeof(uint64_t), false);
     if (word == ~u64(0)) {
@@ -898,7 +892,7 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
             HIP_CHECK(hipGetLastError());
         }
     }
-    HIP_CHECK(hipEventRecord(e_expand1.e, s));
+    HIP_CHECK(hipEventRecord(e_expand1[0], s));
     HIP_CHECK(hipStreamSynchronize(s));        // (step_off, step_seg and node_off go)
     m.hash.release(); m.rank.release(); m.bucket.release();
 }
@@ -911,7 +905,7 @@ void GfaDeviceParse::labels(Strings &out, uint64_t &graph_nodes) {
     if (row_nodes == 0) return;
     const uint64_t min_id = min_node / 2, slots = max_node / 2 - min_id + 1, S = counts.segments;       // (translated: nodes 1 .. total_nodes)
     Event e0, e1;
-    HIP_CHECK(hipEventRecord(e0.e, s));
+    HIP_CHECK(hipEventRecord(e0[0], s));
     Buf slot_off, slot_src, bytes;
     slot_off.alloc(m.tally, (slots + 1) * sizeof(uint64_t)); slot_src.alloc(m.tally, slots * sizeof(uint64_t));
     HIP_CHECK(hipMemsetAsync(slot_off.ptr, 0, (slots + 1) * sizeof(uint64_t), s));
@@ -933,7 +927,7 @@ void GfaDeviceParse::labels(Strings &out, uint64_t &graph_nodes) {
                            bytes.as<uint8_t>());
         HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipEventRecord(e1.e, s));
+    HIP_CHECK(hipEventRecord(e1[0], s));
     out.offsets.resize(slots + 1);
     out.bytes.resize(total);
     HIP_CHECK(hipMemcpyAsync(out.offsets.data(), slot_off.ptr, (slots + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -941,7 +935,7 @@ void GfaDeviceParse::labels(Strings &out, uint64_t &graph_nodes) {
     u64 nodes = 0;
     HIP_CHECK(hipMemcpyAsync(&nodes, m.counters() + CNT_GRAPH_NODES, sizeof(u64), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipEventElapsedTime(&labels_ms, e0.e, e1.e));
+    HIP_CHECK(hipEventElapsedTime(&labels_ms, e0[0], e1[0]));
     graph_nodes = nodes;
     peak_bytes = m.tally.peak;
 }

@@ -1,6 +1,6 @@
-// hip_raii.hpp -- the small owners the construction, the merge and the removal share (build.hip, capi_build.hip, capi_gfa_build.hip,
-// merge.hip, capi_merge.hip, remove.hip, capi_remove.hip): a stream, a set of events, a workspace of the C ABI with the rows of a rebuild
-// in it, and the host clock of the *_info structs.
+// hip_raii.hpp -- the small owners of the library: a stream, a set of events and a few words of pinned host memory (workspaces, the
+// construction, the merge, the removal, the locate build, the GFA parse, the components), a workspace of the C ABI with the rows of a
+// rebuild in it, and the host clock of the *_info structs.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,25 +8,45 @@
 #include <chrono>
 
 #include "../../include/gbwt_hip.h"
-#include "capi_internal.hpp"
+#include "capi_status.hpp"
 
 namespace gbwt_hip {
+
+// How an owner that a workspace holds is made: by the first request that needs it, not with the workspace (gbwt_hip_workspace_create
+// stays cheap, and a family that is never asked for costs nothing)
+struct OnFirstUse {};
 
 struct Stream {
     hipStream_t s = nullptr;
     Stream() { HIP_CHECK(hipStreamCreate(&s)); }
+    explicit Stream(OnFirstUse) {}
+    void create(unsigned flags) { HIP_CHECK(hipStreamCreateWithFlags(&s, flags)); }
     ~Stream() { if (s) (void)hipStreamDestroy(s); }
     Stream(const Stream &) = delete;
     Stream &operator=(const Stream &) = delete;
+    operator hipStream_t() const { return s; }
 };
 
 template <int N>
 struct EventSet {
     hipEvent_t e[N] = {};
-    EventSet() { for (auto &x : e) HIP_CHECK(hipEventCreate(&x)); }
+    EventSet() { ensure(); }
+    explicit EventSet(OnFirstUse) {}
+    void ensure() { for (auto &x : e) if (!x) HIP_CHECK(hipEventCreate(&x)); }
     ~EventSet() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
     EventSet(const EventSet &) = delete;
     EventSet &operator=(const EventSet &) = delete;
+    hipEvent_t operator[](int i) const { return e[i]; }
+};
+
+// Four words of pinned host memory, made by the first request that reads a total back while the device goes on
+struct PinnedWords {
+    uint64_t *p = nullptr;
+    void ensure() { if (!p) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&p), 4 * sizeof(uint64_t))); }
+    PinnedWords() = default;
+    ~PinnedWords() { if (p) (void)hipHostFree(p); }
+    PinnedWords(const PinnedWords &) = delete;
+    PinnedWords &operator=(const PinnedWords &) = delete;
 };
 
 struct Workspace {

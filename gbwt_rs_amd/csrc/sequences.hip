@@ -212,25 +212,25 @@ __global__ void __launch_bounds__(BASES_THREADS) k_bases(const uint32_t *nodes, 
 namespace gbwt_hip {
 
 Labels labels_of(const gbwt_hip_index *ix) {
-    return Labels{ix->label_bytes.as<uint8_t>(), ix->label_off.as<uint64_t>(), static_cast<uint64_t>(ix->host.sequences_labels.size()),
+    return Labels{ix->labels.bytes.as<uint8_t>(), ix->labels.off.as<uint64_t>(), static_cast<uint64_t>(ix->host.sequences_labels.size()),
                   static_cast<uint32_t>(ix->host.alphabet_offset + 1)};
 }
 
 // The node labels in HBM, made once per handle by the first request for bases (any thread, any workspace).  A failure marks nothing:
 // the next request tries again.
 void ensure_labels(const gbwt_hip_index *ix) {
-    ix->labels_built.ensure([ix]() {
+    ix->labels.built.ensure([ix]() {
         const Strings &s = ix->host.sequences_labels;
         HIP_CHECK(hipSetDevice(ix->device));
         const uint64_t bytes = s.bytes.size(), offsets = s.offsets.size();
-        ix->label_bytes.reserve(bytes + LABEL_PAD);
-        ix->label_off.reserve(offsets * sizeof(uint64_t));
-        if (bytes) HIP_CHECK(hipMemcpy(ix->label_bytes.ptr, s.bytes.data(), bytes, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(ix->label_bytes.as<uint8_t>() + bytes, 0, LABEL_PAD));
-        HIP_CHECK(hipMemcpy(ix->label_off.ptr, s.offsets.data(), offsets * sizeof(uint64_t), hipMemcpyHostToDevice));
+        ix->labels.bytes.reserve(bytes + LABEL_PAD);
+        ix->labels.off.reserve(offsets * sizeof(uint64_t));
+        if (bytes) HIP_CHECK(hipMemcpy(ix->labels.bytes.ptr, s.bytes.data(), bytes, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(ix->labels.bytes.as<uint8_t>() + bytes, 0, LABEL_PAD));
+        HIP_CHECK(hipMemcpy(ix->labels.off.ptr, s.offsets.data(), offsets * sizeof(uint64_t), hipMemcpyHostToDevice));
         uint64_t longest = 0;
         for (uint64_t k = 0; k + 1 < offsets; k++) longest = std::max<uint64_t>(longest, s.offsets[k + 1] - s.offsets[k]);
-        ix->max_label_len = longest;
+        ix->labels.max_len = longest;
     });
 }
 
@@ -244,11 +244,11 @@ void require_bases_capable(const gbwt_hip_index *ix) {
 // k_bases counts the bytes of a batch of BATCH positions, the slack of its units included, in 32 bits (after ensure_labels)
 static const char *const LABELS_TOO_LONG = "node labels too long for the bases kernel (32-bit offsets inside a batch of 1 024 positions)";
 static bool labels_fit_a_batch(const gbwt_hip_index *ix) {
-    return static_cast<uint64_t>(BATCH) * ix->max_label_len + 16 * BASES_THREADS + 16 <= 0xFFFFFFFFull;
+    return static_cast<uint64_t>(BATCH) * ix->labels.max_len + 16 * BASES_THREADS + 16 <= 0xFFFFFFFFull;
 }
 
-// The bases of a batch of paths, computed ONCE into device memory (text buffer of `slot`: ws->seq_text or seq_text2; row k at
-// [offsets[k], offsets[k + 1]) of ws->seq_offsets).  The request is remembered in the workspace: the fill call after a size query, and the
+// The bases of a batch of paths, computed ONCE into device memory (text buffer of `slot`: ws->bases.text or text2; row k at
+// [offsets[k], offsets[k + 1]) of ws->bases.offsets).  The request is remembered in the workspace: the fill call after a size query, and the
 // copy-out of gbwt_hip_path_sequences after gbwt_hip_path_sequences_device, find the bases there.
 static gbwt_hip_status sequences_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int reverse, int endmarker,
                                          int slot = 0) {
@@ -256,22 +256,20 @@ static gbwt_hip_status sequences_compute(const gbwt_hip_index *ix, gbwt_hip_work
     if (n && !path_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null path_ids");
     if (endmarker < -1 || endmarker > 255) return fail(GBWT_HIP_BAD_ARGUMENT, "endmarker must be -1 (none) or a byte value 0..255");
     reverse = reverse ? 1 : 0;
-    if (ws->seq_cached && ws->seq_reverse == reverse && ws->seq_endmarker == endmarker && ws->seq_slot == slot && ws->seq_key.size() == n &&
-        (n == 0 || std::memcmp(ws->seq_key.data(), path_ids, n * sizeof(uint64_t)) == 0))
-        return GBWT_HIP_OK;
-    ws->seq_cached = false;
-    ws->seq_timed = false;
+    if (ws->bases.memo.matches({{path_ids, n * sizeof(uint64_t)}}, {reverse, endmarker, slot})) return GBWT_HIP_OK;
+    ws->bases.memo.drop();
+    ws->bases.timed = false;
     try {
         require_bases_capable(ix);
         const HostIndex &h = ix->host;
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
-        ws->seq_offsets.reserve((n + 1) * sizeof(uint64_t));
-        ws->seq_total = 0;
+        ws->bases.offsets.reserve((n + 1) * sizeof(uint64_t));
+        ws->bases.total = 0;
         if (n == 0) {
-            HIP_CHECK(hipMemsetAsync(ws->seq_offsets.ptr, 0, sizeof(uint64_t), s));
+            HIP_CHECK(hipMemsetAsync(ws->bases.offsets.ptr, 0, sizeof(uint64_t), s));
             HIP_CHECK(hipStreamSynchronize(s));
-            ws->seq_key.clear(); ws->seq_reverse = reverse; ws->seq_endmarker = endmarker; ws->seq_slot = slot; ws->seq_cached = true;
+            ws->bases.memo.store({{nullptr, 0}}, {reverse, endmarker, slot});
             return GBWT_HIP_OK;
         }
         ensure_labels(ix);
@@ -287,60 +285,56 @@ static gbwt_hip_status sequences_compute(const gbwt_hip_index *ix, gbwt_hip_work
         gbwt_hip_paths paths{};
         const gbwt_hip_status st = gbwt_hip_extract_device(ix, ws, seq_ids.data(), n, &paths);
         if (st != GBWT_HIP_OK) return st;
-        for (auto &e : ws->sev) if (!e) HIP_CHECK(hipEventCreate(&e));
-        if (!ws->pinned_words) HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ws->pinned_words), 4 * sizeof(uint64_t)));
-        HIP_CHECK(hipEventRecord(ws->sev[0], s));
-        const uint64_t *d_seq_ids = ws->seq_ids.as<uint64_t>();         // (the extraction has left the ids on the device)
+        ws->bases.ev.ensure();
+        ws->extract.pinned_words.ensure();
+        HIP_CHECK(hipEventRecord(ws->bases.ev[0], s));
+        const uint64_t *d_seq_ids = ws->extract.seq_ids.as<uint64_t>();         // (the extraction has left the ids on the device)
         // 2. sizes.  Chunks of SEQ_CHUNK positions (at least one per row, at most len / SEQ_CHUNK + 1): launches and scans run over that bound.
         const uint64_t chunks_cap = paths.total / SEQ_CHUNK + n;
         if (chunks_cap > 0x7FFFFFFFull) return fail(GBWT_HIP_UNSUPPORTED, "too many chunks in one batch: ask for fewer paths per call");
         const size_t tb = scan_temp_bytes(std::max(n, chunks_cap) + 1);
-        ws->gfa_a.reserve(n * sizeof(uint64_t));
-        ws->gfa_chunk_first.reserve(2 * (n + 1) * sizeof(uint64_t));
-        ws->gfa_chunks.reserve((2 * chunks_cap + 1) * sizeof(uint64_t) + (chunks_cap + 1) * sizeof(uint32_t));
-        ws->gfa_plan.reserve(chunks_cap * sizeof(SeqPlan));
-        ws->scan_temp.reserve(std::max<size_t>(tb, 16));
-        uint64_t *d_row_len = ws->gfa_a.as<uint64_t>(), *d_row_start = ws->seq_offsets.as<uint64_t>();
-        uint64_t *d_chunk_first = ws->gfa_chunk_first.as<uint64_t>(), *d_chunk_counts = d_chunk_first + (n + 1);
-        uint64_t *d_chunk_bases = ws->gfa_chunks.as<uint64_t>(), *d_bases_before = d_chunk_bases + chunks_cap;
+        ws->scratch.a.reserve(n * sizeof(uint64_t));
+        ws->scratch.chunk_first.reserve(2 * (n + 1) * sizeof(uint64_t));
+        ws->scratch.chunks.reserve((2 * chunks_cap + 1) * sizeof(uint64_t) + (chunks_cap + 1) * sizeof(uint32_t));
+        ws->scratch.plan.reserve(chunks_cap * sizeof(SeqPlan));
+        ws->scratch.scan_temp.reserve(std::max<size_t>(tb, 16));
+        uint64_t *d_row_len = ws->scratch.a.as<uint64_t>(), *d_row_start = ws->bases.offsets.as<uint64_t>();
+        uint64_t *d_chunk_first = ws->scratch.chunk_first.as<uint64_t>(), *d_chunk_counts = d_chunk_first + (n + 1);
+        uint64_t *d_chunk_bases = ws->scratch.chunks.as<uint64_t>(), *d_bases_before = d_chunk_bases + chunks_cap;
         uint32_t *d_chunk_path = reinterpret_cast<uint32_t *>(d_bases_before + (chunks_cap + 1));
         const Labels labels = labels_of(ix);
         const unsigned row_blocks = static_cast<unsigned>((n + 255) / 256), chunk_waves = static_cast<unsigned>((chunks_cap + 3) / 4);
-        launch_chunk_plan(paths.d_offsets, n, chunks_cap, d_chunk_counts, d_chunk_first, d_chunk_path, ws->scan_temp.ptr, tb, s);
+        launch_chunk_plan(paths.d_offsets, n, chunks_cap, d_chunk_counts, d_chunk_first, d_chunk_path, ws->scratch.scan_temp.ptr, tb, s);
         const auto chunk_pass = [&]() {
             hipLaunchKernelGGL(k_chunk_bases, dim3(chunk_waves), dim3(256), 0, s, paths.d_offsets, paths.d_nodes, n, d_chunk_first, d_chunk_path, chunks_cap, labels, d_chunk_bases);
-            launch_scan(d_chunk_bases, d_bases_before, chunks_cap, ws->scan_temp.ptr, tb, s);
+            launch_scan(d_chunk_bases, d_bases_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s);
         };
         // The host waits once, for the total that sizes the text buffer.  With the line cache the rows are sized without a node read and the
         // total leaves before the pass that places the chunks inside their rows: the host's wait and allocation run under that pass.
         if (!cacheable) chunk_pass();
         hipLaunchKernelGGL(k_row_bytes, dim3(row_blocks), dim3(256), 0, s, d_seq_ids, n, h.sequences, cacheable ? ix->lc_path.as<uint64_t>() : nullptr, d_chunk_first,
                            d_bases_before, endmarker, d_row_len);
-        launch_scan(d_row_len, d_row_start, n, ws->scan_temp.ptr, tb, s);
-        HIP_CHECK(hipMemcpyAsync(ws->pinned_words, d_row_start + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipEventRecord(ws->sev[1], s));
+        launch_scan(d_row_len, d_row_start, n, ws->scratch.scan_temp.ptr, tb, s);
+        HIP_CHECK(hipMemcpyAsync(ws->extract.pinned_words.p, d_row_start + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipEventRecord(ws->bases.ev[1], s));
         if (cacheable) chunk_pass();
-        HIP_CHECK(hipEventSynchronize(ws->sev[1]));                      // the one wait of a request
+        HIP_CHECK(hipEventSynchronize(ws->bases.ev[1]));                      // the one wait of a request
         HIP_CHECK(hipGetLastError());
-        const uint64_t total = ws->pinned_words[0];
+        const uint64_t total = ws->extract.pinned_words.p[0];
         // 3. the bases
-        DeviceBuffer &text = slot == 0 ? ws->seq_text : ws->seq_text2;
+        DeviceBuffer &text = slot == 0 ? ws->bases.text : ws->bases.text2;
         text.reserve(std::max<uint64_t>(total, 16));
         hipLaunchKernelGGL(k_plan_bases, dim3(static_cast<unsigned>((chunks_cap + 255) / 256)), dim3(256), 0, s, paths.d_offsets, n, d_seq_ids, h.sequences, d_chunk_first,
-                           d_chunk_path, chunks_cap, d_bases_before, d_row_start, endmarker, ws->gfa_plan.as<SeqPlan>());
-        HIP_CHECK(hipEventRecord(ws->sev[1], s));
-        hipLaunchKernelGGL(k_bases, dim3(static_cast<unsigned>(chunks_cap)), dim3(BASES_THREADS), 0, s, paths.d_nodes, n, d_chunk_first, ws->gfa_plan.as<SeqPlan>(), labels,
+                           d_chunk_path, chunks_cap, d_bases_before, d_row_start, endmarker, ws->scratch.plan.as<SeqPlan>());
+        HIP_CHECK(hipEventRecord(ws->bases.ev[1], s));
+        hipLaunchKernelGGL(k_bases, dim3(static_cast<unsigned>(chunks_cap)), dim3(BASES_THREADS), 0, s, paths.d_nodes, n, d_chunk_first, ws->scratch.plan.as<SeqPlan>(), labels,
                            endmarker, text.as<uint8_t>());
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(ws->sev[2], s));
+        HIP_CHECK(hipEventRecord(ws->bases.ev[2], s));
         HIP_CHECK(hipStreamSynchronize(s));
-        ws->seq_timed = true;
-        ws->seq_total = total;
-        ws->seq_key.assign(path_ids, path_ids + n);
-        ws->seq_reverse = reverse;
-        ws->seq_endmarker = endmarker;
-        ws->seq_slot = slot;
-        ws->seq_cached = true;
+        ws->bases.timed = true;
+        ws->bases.total = total;
+        ws->bases.memo.store({{path_ids, n * sizeof(uint64_t)}}, {reverse, endmarker, slot});
         return GBWT_HIP_OK;
     } catch (const InvalidData &e) {
         return fail(GBWT_HIP_BAD_ARGUMENT, e.what());
@@ -359,9 +353,9 @@ gbwt_hip_status gbwt_hip_path_sequences_device(const gbwt_hip_index *ix, gbwt_hi
     *out = gbwt_hip_lines{nullptr, nullptr, 0, 0};
     const gbwt_hip_status st = sequences_compute(ix, ws, path_ids, n, reverse, endmarker);
     if (st != GBWT_HIP_OK) return st;
-    out->d_text = ws->seq_text.as<char>();
-    out->d_line_offsets = ws->seq_offsets.as<uint64_t>();
-    out->total = ws->seq_total;
+    out->d_text = ws->bases.text.as<char>();
+    out->d_line_offsets = ws->bases.offsets.as<uint64_t>();
+    out->total = ws->bases.total;
     out->n = n;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
@@ -375,13 +369,13 @@ gbwt_hip_status gbwt_hip_path_sequences(const gbwt_hip_index *ix, gbwt_hip_works
     *total = 0;
     const gbwt_hip_status st = sequences_compute(ix, ws, path_ids, n, reverse, endmarker);
     if (st != GBWT_HIP_OK) return st;
-    *total = ws->seq_total;
+    *total = ws->bases.total;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
-        if (out_offsets) HIP_CHECK(hipMemcpy(out_offsets, ws->seq_offsets.ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (out_offsets) HIP_CHECK(hipMemcpy(out_offsets, ws->bases.offsets.ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
         if (!out || *total == 0) return GBWT_HIP_OK;
         if (capacity < *total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the bases");
-        copy_to_host(ws, out, ws->seq_text.ptr, *total);
+        copy_to_host(ws, out, ws->bases.text.ptr, *total);
         return GBWT_HIP_OK;
     } catch (const HipError &e) {
         return status_of(e);
@@ -410,10 +404,10 @@ gbwt_hip_status gbwt_hip_node_sequence(const gbwt_hip_index *ix, uint64_t node_i
 
 gbwt_hip_status gbwt_hip_last_sequences_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *sizes_ms, float *bases_ms) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->seq_timed || !ws->timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for bases on this workspace");
+    if (!ws || !ws->bases.timed || !ws->extract.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for bases on this workspace");
     float a = 0, b = 0, c = 0;
-    if (hipEventElapsedTime(&a, ws->ev[0], ws->ev[1]) != hipSuccess || hipEventElapsedTime(&b, ws->sev[0], ws->sev[1]) != hipSuccess ||
-        hipEventElapsedTime(&c, ws->sev[1], ws->sev[2]) != hipSuccess)
+    if (hipEventElapsedTime(&a, ws->extract.ev[0], ws->extract.ev[1]) != hipSuccess || hipEventElapsedTime(&b, ws->bases.ev[0], ws->bases.ev[1]) != hipSuccess ||
+        hipEventElapsedTime(&c, ws->bases.ev[1], ws->bases.ev[2]) != hipSuccess)
         return fail(GBWT_HIP_DEVICE_ERROR, "hipEventElapsedTime failed");
     if (walk_ms) *walk_ms = a;
     if (sizes_ms) *sizes_ms = b;
@@ -486,9 +480,9 @@ gbwt_hip_status gbwt_hip_write_sequences(const gbwt_hip_index *ix, gbwt_hip_work
             if (!writer.acquire(slot)) { st = GBWT_HIP_IO_ERROR; break; }
             st = sequences_compute(ix, ws, ids.data() + b0, nb, 0, endmarker, slot);
             if (st != GBWT_HIP_OK) break;
-            writer.submit((slot == 0 ? ws->seq_text : ws->seq_text2).as<char>(), ws->seq_total, slot);
+            writer.submit((slot == 0 ? ws->bases.text : ws->bases.text2).as<char>(), ws->bases.total, slot);
             offs.resize(nb + 1);
-            HIP_CHECK(hipMemcpy(offs.data(), ws->seq_offsets.ptr, (nb + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(offs.data(), ws->bases.offsets.ptr, (nb + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
             lines.clear();
             for (uint64_t k = 0; k < nb; k++) {
                 const uint64_t p = ids[b0 + k];
@@ -506,7 +500,7 @@ gbwt_hip_status gbwt_hip_write_sequences(const gbwt_hip_index *ix, gbwt_hip_work
             b0 += nb;
         }
         const gbwt_hip_status wst = writer.finish();
-        ws->seq_cached = false;                              // (both text buffers have been reused)
+        ws->bases.memo.drop();                               // (both text buffers have been reused)
         if (st == GBWT_HIP_OK && wst != GBWT_HIP_OK) return fail(wst, writer.message);
         if (st != GBWT_HIP_OK) return wst != GBWT_HIP_OK ? fail(wst, writer.message) : st;
         if (file.failed || names.failed) return fail(GBWT_HIP_IO_ERROR, "short write");

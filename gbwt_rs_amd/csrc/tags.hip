@@ -200,14 +200,14 @@ void require_fits(std::initializer_list<std::pair<const DeviceBuffer *, uint64_t
                           std::to_string(free_bytes) + " are free"};
 }
 
-void drop_plan(gbwt_hip_workspace *ws) { ws->tag_planned = false; ws->tag_timed = false; ws->tag_key.clear(); ws->tag_rows.clear(); ws->tag_positions = 0; ws->tag_text_len = 0; }
+void drop_plan(gbwt_hip_workspace *ws) { ws->tags.plan_key.drop(); ws->tags.timed = false; ws->tags.rows.clear(); ws->tags.positions = 0; ws->tags.text_len = 0; }
 
 // The plan of a list of path ids (see the top of the file), made unless the workspace holds it
 gbwt_hip_status tags_plan(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n) {
     if (!ix || !ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
     if (n && !path_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null path_ids");
-    if (ws->tag_planned && ws->tag_key.size() == n && (n == 0 || std::memcmp(ws->tag_key.data(), path_ids, n * sizeof(uint64_t)) == 0)) {
-        ws->tag_gather_ms = 0;
+    if (ws->tags.plan_key.matches({{path_ids, n * sizeof(uint64_t)}}, {})) {
+        ws->tags.gather_ms = 0;
         return GBWT_HIP_OK;
     }
     drop_plan(ws);
@@ -221,19 +221,20 @@ gbwt_hip_status tags_plan(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, cons
         }
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
-        for (auto &e : ws->tev) if (!e) HIP_CHECK(hipEventCreate(&e));
-        ws->tag_state.reserve(sizeof(TagState));
-        ws->tag_walk_ms = ws->tag_plan_ms = ws->tag_gather_ms = 0;
+        ws->tags.ev.ensure();
+        ws->tags.state.reserve(sizeof(TagState));
+        ws->tags.walk_ms = ws->tags.plan_ms = ws->tags.gather_ms = 0;
         if (n == 0) {                                // an empty text: nothing to look anything up in
-            ws->tag_rows.assign(1, 0);
-            ws->tag_planned = ws->tag_timed = true;
+            ws->tags.rows.assign(1, 0);
+            ws->tags.plan_key.store({{nullptr, 0}}, {});
+            ws->tags.timed = true;
             return GBWT_HIP_OK;
         }
         ensure_labels(ix);
         gbwt_hip_paths paths{};
         const gbwt_hip_status st = gbwt_hip_extract_device(ix, ws, seq_ids.data(), n, &paths);
         if (st != GBWT_HIP_OK) return st;
-        HIP_CHECK(hipEventElapsedTime(&ws->tag_walk_ms, ws->ev[0], ws->ev[1]));
+        HIP_CHECK(hipEventElapsedTime(&ws->tags.walk_ms, ws->extract.ev[0], ws->extract.ev[1]));
         const uint64_t positions = paths.total + n;
         // GBWT_HIP_TAG_SCAN_PIECE (positions per launch of the scan) and GBWT_HIP_TAG_WIDE (64-bit hints whatever the size) let tests reach what
         // only plans of 2^30 and 2^32 positions reach otherwise; read when a plan is made
@@ -242,45 +243,45 @@ gbwt_hip_status tags_plan(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, cons
         const char *force_wide = std::getenv("GBWT_HIP_TAG_WIDE");
         const bool wide = positions > 0xFFFFFFFFull || (force_wide && std::atoi(force_wide) != 0);
         DeviceBuffer lengths;                        // the label lengths in front of the scan: scratch of the plan
-        require_fits({{&ws->tag_node, positions * sizeof(uint32_t)}, {&ws->tag_off, (positions + 1) * sizeof(uint64_t)}, {&lengths, positions * sizeof(uint64_t)}}, "the tag plan");
-        ws->tag_node.reserve(positions * sizeof(uint32_t));
-        ws->tag_off.reserve((positions + 1) * sizeof(uint64_t));
+        require_fits({{&ws->tags.node, positions * sizeof(uint32_t)}, {&ws->tags.off, (positions + 1) * sizeof(uint64_t)}, {&lengths, positions * sizeof(uint64_t)}}, "the tag plan");
+        ws->tags.node.reserve(positions * sizeof(uint32_t));
+        ws->tags.off.reserve((positions + 1) * sizeof(uint64_t));
         lengths.reserve(positions * sizeof(uint64_t));
         const size_t tb = scan_temp_bytes(std::min(positions, scan_piece));
-        ws->scan_temp.reserve(std::max<size_t>(tb, 16));
-        ws->gfa_a.reserve((n + 1) * sizeof(uint64_t));
-        uint64_t *d_len = lengths.as<uint64_t>(), *d_off = ws->tag_off.as<uint64_t>(), *d_rows = ws->gfa_a.as<uint64_t>();
+        ws->scratch.scan_temp.reserve(std::max<size_t>(tb, 16));
+        ws->scratch.a.reserve((n + 1) * sizeof(uint64_t));
+        uint64_t *d_len = lengths.as<uint64_t>(), *d_off = ws->tags.off.as<uint64_t>(), *d_rows = ws->scratch.a.as<uint64_t>();
         const auto blocks = [](uint64_t items) { return dim3(static_cast<unsigned>((items + 255) / 256)); };
-        HIP_CHECK(hipEventRecord(ws->tev[0], s));
-        hipLaunchKernelGGL(k_tag_positions, blocks(positions), dim3(256), 0, s, paths.d_offsets, paths.d_nodes, n, positions, labels_of(ix), ws->tag_node.as<uint32_t>(), d_len);
+        HIP_CHECK(hipEventRecord(ws->tags.ev[0], s));
+        hipLaunchKernelGGL(k_tag_positions, blocks(positions), dim3(256), 0, s, paths.d_offsets, paths.d_nodes, n, positions, labels_of(ix), ws->tags.node.as<uint32_t>(), d_len);
         for (uint64_t at = 0; at < positions; at += scan_piece) {
             const uint64_t piece = std::min(scan_piece, positions - at);
-            uint64_t *saved = ws->tag_state.as<TagState>()->last;          // (a word nobody reads before the next request clears the state)
+            uint64_t *saved = ws->tags.state.as<TagState>()->last;          // (a word nobody reads before the next request clears the state)
             if (at != 0) hipLaunchKernelGGL(k_tag_carry, dim3(1), dim3(1), 0, s, d_len, d_off, at, saved, 0);
-            launch_scan(d_len + at, d_off + at, piece, ws->scan_temp.ptr, tb, s);
+            launch_scan(d_len + at, d_off + at, piece, ws->scratch.scan_temp.ptr, tb, s);
             if (at != 0) hipLaunchKernelGGL(k_tag_carry, dim3(1), dim3(1), 0, s, d_len, d_off, at, saved, 1);
         }
         hipLaunchKernelGGL(k_tag_rows, blocks(n + 1), dim3(256), 0, s, paths.d_offsets, n, d_off, positions, d_rows);
-        ws->tag_rows.resize(n + 1);
-        HIP_CHECK(hipMemcpyAsync(ws->tag_rows.data(), d_rows, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        ws->tags.rows.resize(n + 1);
+        HIP_CHECK(hipMemcpyAsync(ws->tags.rows.data(), d_rows, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));          // the one wait of a plan: the text length sizes the top level
         HIP_CHECK(hipGetLastError());
         lengths.release();
-        const uint64_t text_len = ws->tag_rows[n], hints = ((text_len - 1) >> TAG_SHIFT) + 2;
+        const uint64_t text_len = ws->tags.rows[n], hints = ((text_len - 1) >> TAG_SHIFT) + 2;
         const uint64_t top_bytes = hints * (wide ? sizeof(uint64_t) : sizeof(uint32_t));
-        require_fits({{&ws->tag_top, top_bytes}}, "the top level of the tag plan");
-        ws->tag_top.reserve(top_bytes);
-        if (wide) hipLaunchKernelGGL(k_tag_top<uint64_t>, blocks(hints), dim3(256), 0, s, d_off, positions, hints, ws->tag_top.as<uint64_t>());
-        else hipLaunchKernelGGL(k_tag_top<uint32_t>, blocks(hints), dim3(256), 0, s, d_off, positions, hints, ws->tag_top.as<uint32_t>());
-        HIP_CHECK(hipEventRecord(ws->tev[1], s));
+        require_fits({{&ws->tags.top, top_bytes}}, "the top level of the tag plan");
+        ws->tags.top.reserve(top_bytes);
+        if (wide) hipLaunchKernelGGL(k_tag_top<uint64_t>, blocks(hints), dim3(256), 0, s, d_off, positions, hints, ws->tags.top.as<uint64_t>());
+        else hipLaunchKernelGGL(k_tag_top<uint32_t>, blocks(hints), dim3(256), 0, s, d_off, positions, hints, ws->tags.top.as<uint32_t>());
+        HIP_CHECK(hipEventRecord(ws->tags.ev[1], s));
         HIP_CHECK(hipStreamSynchronize(s));
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventElapsedTime(&ws->tag_plan_ms, ws->tev[0], ws->tev[1]));
-        ws->tag_positions = positions;
-        ws->tag_text_len = text_len;
-        ws->tag_wide = wide;
-        ws->tag_key.assign(path_ids, path_ids + n);
-        ws->tag_planned = ws->tag_timed = true;
+        HIP_CHECK(hipEventElapsedTime(&ws->tags.plan_ms, ws->tags.ev[0], ws->tags.ev[1]));
+        ws->tags.positions = positions;
+        ws->tags.text_len = text_len;
+        ws->tags.wide = wide;
+        ws->tags.plan_key.store({{path_ids, n * sizeof(uint64_t)}}, {});
+        ws->tags.timed = true;
         return GBWT_HIP_OK;
     } catch (const InvalidData &e) {
         return fail(GBWT_HIP_BAD_ARGUMENT, e.what());
@@ -297,12 +298,12 @@ void launch_tags(gbwt_hip_workspace *ws, const uint64_t *d_sa, uint64_t count, u
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ws->index->device));
     const uint64_t tiles = (count + TAG_TILE - 1) / TAG_TILE;
     const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(tiles, 8ull * static_cast<unsigned>(std::max(cus, 1))));   // eight workgroups per CU: what its registers hold
-    TagState *state = ws->tag_state.as<TagState>();
-    if (ws->tag_wide) {
-        const TagMap<uint64_t> m{ws->tag_top.as<uint64_t>(), ws->tag_off.as<uint64_t>(), ws->tag_node.as<uint32_t>(), ws->tag_text_len};
+    TagState *state = ws->tags.state.as<TagState>();
+    if (ws->tags.wide) {
+        const TagMap<uint64_t> m{ws->tags.top.as<uint64_t>(), ws->tags.off.as<uint64_t>(), ws->tags.node.as<uint32_t>(), ws->tags.text_len};
         hipLaunchKernelGGL(k_tags<uint64_t>, dim3(grid), dim3(TAG_THREADS), 0, ws->stream, d_sa, count, m, d_tags, state, has_prev ? 1u : 0u, parity);
     } else {
-        const TagMap<uint32_t> m{ws->tag_top.as<uint32_t>(), ws->tag_off.as<uint64_t>(), ws->tag_node.as<uint32_t>(), ws->tag_text_len};
+        const TagMap<uint32_t> m{ws->tags.top.as<uint32_t>(), ws->tags.off.as<uint64_t>(), ws->tags.node.as<uint32_t>(), ws->tags.text_len};
         hipLaunchKernelGGL(k_tags<uint32_t>, dim3(grid), dim3(TAG_THREADS), 0, ws->stream, d_sa, count, m, d_tags, state, has_prev ? 1u : 0u, parity);
     }
     HIP_CHECK(hipGetLastError());
@@ -312,17 +313,17 @@ void launch_tags(gbwt_hip_workspace *ws, const uint64_t *d_sa, uint64_t count, u
 gbwt_hip_status gather_once(gbwt_hip_workspace *ws, const uint64_t *d_sa, uint64_t count, uint64_t *d_tags, uint64_t *runs) {
     if (runs) *runs = 0;
     if (count == 0) return GBWT_HIP_OK;
-    if (ws->tag_text_len == 0) return fail(GBWT_HIP_INVALID_DATA, "suffix array value out of range: the text of no paths is empty");
+    if (ws->tags.text_len == 0) return fail(GBWT_HIP_INVALID_DATA, "suffix array value out of range: the text of no paths is empty");
     hipStream_t s = ws->stream;
     TagState state{};
-    HIP_CHECK(hipMemsetAsync(ws->tag_state.ptr, 0, sizeof(TagState), s));
-    HIP_CHECK(hipEventRecord(ws->tev[0], s));
+    HIP_CHECK(hipMemsetAsync(ws->tags.state.ptr, 0, sizeof(TagState), s));
+    HIP_CHECK(hipEventRecord(ws->tags.ev[0], s));
     launch_tags(ws, d_sa, count, d_tags, false, 0);
-    HIP_CHECK(hipEventRecord(ws->tev[1], s));
-    HIP_CHECK(hipMemcpyAsync(&state, ws->tag_state.ptr, sizeof(TagState), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipEventRecord(ws->tags.ev[1], s));
+    HIP_CHECK(hipMemcpyAsync(&state, ws->tags.state.ptr, sizeof(TagState), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipEventElapsedTime(&ws->tag_gather_ms, ws->tev[0], ws->tev[1]));
-    if (state.bad) return fail(GBWT_HIP_INVALID_DATA, "suffix array value out of range: the text has " + std::to_string(ws->tag_text_len) + " positions");
+    HIP_CHECK(hipEventElapsedTime(&ws->tags.gather_ms, ws->tags.ev[0], ws->tags.ev[1]));
+    if (state.bad) return fail(GBWT_HIP_INVALID_DATA, "suffix array value out of range: the text has " + std::to_string(ws->tags.text_len) + " positions");
     if (runs) *runs = state.runs;
     return GBWT_HIP_OK;
 }
@@ -362,20 +363,20 @@ gbwt_hip_status gbwt_hip_tags(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, 
     if (runs) *runs = 0;
     const gbwt_hip_status st = tags_plan(ix, ws, path_ids, n);
     if (st != GBWT_HIP_OK) return st;
-    if (expected_len) *expected_len = ws->tag_text_len;
+    if (expected_len) *expected_len = ws->tags.text_len;
     if (!sa && !tags) return GBWT_HIP_OK;            // the size query
     if (count && (!sa || !tags)) return fail(GBWT_HIP_BAD_ARGUMENT, "null suffix array / tags");
     if (count == 0) return GBWT_HIP_OK;
     try {
         HIP_CHECK(hipSetDevice(ix->device));
         if (count > (~uint64_t(0)) / 16) return fail(GBWT_HIP_CAPACITY, "suffix array too large for device memory");
-        require_fits({{&ws->tag_sa, count * sizeof(uint64_t)}, {&ws->tag_out, count * sizeof(uint64_t)}}, "the suffix array and its tags");
-        ws->tag_sa.reserve(count * sizeof(uint64_t));
-        ws->tag_out.reserve(count * sizeof(uint64_t));
-        HIP_CHECK(hipMemcpyAsync(ws->tag_sa.ptr, sa, count * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
-        const gbwt_hip_status gst = gather_once(ws, ws->tag_sa.as<uint64_t>(), count, ws->tag_out.as<uint64_t>(), runs);
+        require_fits({{&ws->tags.sa, count * sizeof(uint64_t)}, {&ws->tags.out, count * sizeof(uint64_t)}}, "the suffix array and its tags");
+        ws->tags.sa.reserve(count * sizeof(uint64_t));
+        ws->tags.out.reserve(count * sizeof(uint64_t));
+        HIP_CHECK(hipMemcpyAsync(ws->tags.sa.ptr, sa, count * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+        const gbwt_hip_status gst = gather_once(ws, ws->tags.sa.as<uint64_t>(), count, ws->tags.out.as<uint64_t>(), runs);
         if (gst != GBWT_HIP_OK) return gst;          // (the caller's tags are untouched)
-        copy_to_host(ws, tags, ws->tag_out.ptr, count * sizeof(uint64_t));
+        copy_to_host(ws, tags, ws->tags.out.ptr, count * sizeof(uint64_t));
         return GBWT_HIP_OK;
     } catch (const OutOfMemory &e) {
         return fail(GBWT_HIP_CAPACITY, e.what);
@@ -427,11 +428,11 @@ gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *ix, gbwt_hip_work
         const gbwt_hip_status st = tags_plan(ix, ws, ids.data(), ids.size());
         if (st != GBWT_HIP_OK) return st;
         for (size_t k = 0; k < ids.size(); k++) {
-            const uint64_t walked = ws->tag_rows[k + 1] - ws->tag_rows[k] - 1;
+            const uint64_t walked = ws->tags.rows[k + 1] - ws->tags.rows[k] - 1;
             if (walked != lens[k])
                 return fail(GBWT_HIP_INVALID_DATA, "Invalid length for path " + std::to_string(ids[k]) + ": expected " + std::to_string(lens[k]) + ", got " + std::to_string(walked));
         }
-        const uint64_t expected_len = ws->tag_text_len;
+        const uint64_t expected_len = ws->tags.text_len;
         // 3. the suffix array: sa_skip values skipped, expected_len read
         PositionalFile sa_file, out;
         sa_file.fd = ::open(sa_path.c_str(), O_RDONLY);
@@ -444,11 +445,11 @@ gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *ix, gbwt_hip_work
         if (const char *v = std::getenv("GBWT_HIP_TAG_BATCH_MIB")) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10)) << 20;
         const uint64_t batch = std::min<uint64_t>(std::max<uint64_t>(budget / sizeof(uint64_t), 1), expected_len);
         HIP_CHECK(hipSetDevice(ix->device));
-        require_fits({{&ws->tag_sa, batch * sizeof(uint64_t)}, {&ws->tag_sa2, batch * sizeof(uint64_t)}, {&ws->tag_out, batch * sizeof(uint64_t)}, {&ws->tag_out2, batch * sizeof(uint64_t)}},
+        require_fits({{&ws->tags.sa, batch * sizeof(uint64_t)}, {&ws->tags.sa2, batch * sizeof(uint64_t)}, {&ws->tags.out, batch * sizeof(uint64_t)}, {&ws->tags.out2, batch * sizeof(uint64_t)}},
                      "the batches of the tag array");
-        for (DeviceBuffer *b : {&ws->tag_sa, &ws->tag_sa2, &ws->tag_out, &ws->tag_out2}) b->reserve(batch * sizeof(uint64_t));
+        for (DeviceBuffer *b : {&ws->tags.sa, &ws->tags.sa2, &ws->tags.out, &ws->tags.out2}) b->reserve(batch * sizeof(uint64_t));
         std::vector<uint64_t> values(batch);
-        HIP_CHECK(hipMemsetAsync(ws->tag_state.ptr, 0, sizeof(TagState), ws->stream));
+        HIP_CHECK(hipMemsetAsync(ws->tags.state.ptr, 0, sizeof(TagState), ws->stream));
         out.fd = ::open(tags_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (out.fd < 0) return fail(GBWT_HIP_IO_ERROR, "cannot create " + tags_path);
         gbwt_hip_status result = GBWT_HIP_OK;
@@ -474,15 +475,15 @@ gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *ix, gbwt_hip_work
                     }
                     if (got < cnt * sizeof(uint64_t)) { result = GBWT_HIP_IO_ERROR; message = "short read from " + sa_path; break; }
                     if (!writer.acquire(slot)) { result = GBWT_HIP_IO_ERROR; break; }   // (the writer's own message, below)
-                    uint64_t *d_sa = (slot == 0 ? ws->tag_sa : ws->tag_sa2).as<uint64_t>(), *d_tags = (slot == 0 ? ws->tag_out : ws->tag_out2).as<uint64_t>();
+                    uint64_t *d_sa = (slot == 0 ? ws->tags.sa : ws->tags.sa2).as<uint64_t>(), *d_tags = (slot == 0 ? ws->tags.out : ws->tags.out2).as<uint64_t>();
                     HIP_CHECK(hipMemcpyAsync(d_sa, values.data(), cnt * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-                    HIP_CHECK(hipEventRecord(ws->tev[0], s));
+                    HIP_CHECK(hipEventRecord(ws->tags.ev[0], s));
                     launch_tags(ws, d_sa, cnt, d_tags, batches != 0, batches & 1u);
-                    HIP_CHECK(hipEventRecord(ws->tev[1], s));
-                    HIP_CHECK(hipMemcpyAsync(&state, ws->tag_state.ptr, sizeof(TagState), hipMemcpyDeviceToHost, s));
+                    HIP_CHECK(hipEventRecord(ws->tags.ev[1], s));
+                    HIP_CHECK(hipMemcpyAsync(&state, ws->tags.state.ptr, sizeof(TagState), hipMemcpyDeviceToHost, s));
                     HIP_CHECK(hipStreamSynchronize(s));
                     float ms = 0;
-                    HIP_CHECK(hipEventElapsedTime(&ms, ws->tev[0], ws->tev[1]));
+                    HIP_CHECK(hipEventElapsedTime(&ms, ws->tags.ev[0], ws->tags.ev[1]));
                     gather_ms += ms;
                     if (state.bad) {
                         result = GBWT_HIP_INVALID_DATA;
@@ -499,7 +500,7 @@ gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *ix, gbwt_hip_work
             if (wst != GBWT_HIP_OK && (result == GBWT_HIP_OK || message.empty())) { result = wst; message = writer.message; }
         }
         if (result == GBWT_HIP_OK && out.failed) { result = GBWT_HIP_IO_ERROR; message = "short write to " + tags_path; }
-        ws->tag_gather_ms = gather_ms;
+        ws->tags.gather_ms = gather_ms;
         if (result != GBWT_HIP_OK) {
             (void)::unlink(tags_path.c_str());      // nothing half written stays behind
             return fail(result, message);
@@ -518,10 +519,10 @@ gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *ix, gbwt_hip_work
 
 gbwt_hip_status gbwt_hip_last_tags_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *plan_ms, float *gather_ms) {
     GBWT_HIP_GUARD_BEGIN
-    if (!ws || !ws->tag_timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for tags on this workspace");
-    if (walk_ms) *walk_ms = ws->tag_walk_ms;
-    if (plan_ms) *plan_ms = ws->tag_plan_ms;
-    if (gather_ms) *gather_ms = ws->tag_gather_ms;
+    if (!ws || !ws->tags.timed) return fail(GBWT_HIP_BAD_ARGUMENT, "no timed request for tags on this workspace");
+    if (walk_ms) *walk_ms = ws->tags.walk_ms;
+    if (plan_ms) *plan_ms = ws->tags.plan_ms;
+    if (gather_ms) *gather_ms = ws->tags.gather_ms;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }

@@ -331,7 +331,7 @@ def test_rccl_gather_between_ranks():
 
 def test_rccl_send_from_a_mapped_rows_buffer():
     """The same with a batch whose rows exceed 4 GiB per rank, i.e. rows that the workspace has rebuilt from 2 GiB chunks of the
-    virtual-memory API (capi_internal.hpp: DeviceBuffer): RCCL sends straight out of that mapping."""
+    virtual-memory API (device_buffer.hpp: DeviceBuffer): RCCL sends straight out of that mapping."""
     world = gpus()
     if world < 2:
         pytest.skip("one GPU on this box: ranks need devices of their own for RCCL point-to-point")

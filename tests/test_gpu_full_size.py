@@ -229,7 +229,7 @@ def test_widths_beyond_u32_are_refused_at_open():
 @pytest.mark.parametrize("after", [0, 2, 5])
 def test_vmm_policy_after_field(monkeypatch, after):
     """GBWT_HIP_VMM = <chunk MiB>:<spread>:<min MiB>:<after>: a rows buffer of at least <min> that has served <after> requests as one
-    hipMalloc is rebuilt from spread physical chunks (capi_internal.hpp: DeviceBuffer::reserve); after = 0 spreads at once.  The fourth
+    hipMalloc is rebuilt from spread physical chunks (device_buffer.hpp: DeviceBuffer::reserve); after = 0 spreads at once.  The fourth
     field was not parsed until round 4.  Results are the same before and after the rebuild, and the memory comes back."""
     monkeypatch.setenv("GBWT_HIP_VMM", f"64:2:64:{after}")
     s = S.Synth.chain(sites=20000, haplotypes=600, alleles=2, model=S.MOSAIC, founders=8, switch_rate=0.01, seed=4)

@@ -854,7 +854,7 @@ def test_headline_full_size():
     lean.close()
     # The 13.3 GB of rows start as one hipMalloc and are rebuilt from spread 2 GiB chunks (virtual-memory API) when the workspace
     # serves its third request of that size; every byte must come back when the workspace goes -- one hipMemUnmap per mapped chunk,
-    # hipMemAddressFree, hipMemRelease (capi_internal.hpp: DeviceBuffer::release) -- and when it regrows.
+    # hipMemAddressFree, hipMemRelease (device_buffer.hpp: DeviceBuffer::release) -- and when it regrows.
     free_before = G.device_memory(0)[0]
     view = dev.another_workspace()
     for _ in range(4):                                     # the third one rebuilds the rows from spread chunks
