@@ -17,8 +17,206 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "extract_plan.hpp"
 
 using namespace gbwt_hip;
+
+namespace {
+
+// One request of gbwt_hip_extract_part_device, as its steps pass it on
+struct Request {
+    const gbwt_hip_index *ix;
+    gbwt_hip_workspace *ws;
+    const uint64_t *seq_ids;
+    uint64_t n;
+    uint32_t part, parts;
+    size_t temp_bytes;         // of scratch.scan_temp, for a scan over n lengths
+    gbwt_hip_paths *out;
+};
+
+// THE finish of every request that succeeds: what copy_result / path_sums / copy_path trust, the memo of whole rows (gbwt_hip_extract's
+// fill call asks for whole rows: a part of them is never stored), and the caller's view of the rows
+gbwt_hip_status finish(const Request &r, uint64_t total, bool store_memo) {
+    ExtractState &e = r.ws->extract;
+    e.timed = true; e.last_n = r.n; e.last_total = total;
+    if (store_memo) e.memo.store({{r.seq_ids, r.n * sizeof(uint64_t)}}, {});
+    r.out->d_offsets = e.offsets.as<uint64_t>(); r.out->d_nodes = e.nodes.as<uint32_t>(); r.out->total = total; r.out->n = r.n;
+    return GBWT_HIP_OK;
+}
+
+// n empty rows: an empty CSR with all its events, so that the times of the request can be asked for like any other's
+gbwt_hip_status empty_rows(const Request &r, bool store_memo) {
+    ExtractState &e = r.ws->extract;
+    hipStream_t s = r.ws->stream;
+    HIP_CHECK(hipMemsetAsync(e.offsets.ptr, 0, (r.n + 1) * sizeof(uint64_t), s));
+    e.nodes.reserve(sizeof(uint32_t));
+    HIP_CHECK(hipEventRecord(e.ev[0], s)); HIP_CHECK(hipEventRecord(e.ev[1], s)); HIP_CHECK(hipEventRecord(e.ev[2], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return finish(r, 0, store_memo);
+}
+
+// The walk of a direct request between ev[0] and ev[1], the end of the request (ev[2]) and the host's wait for it
+void walk_and_wait(ExtractState &e, const DeviceIndex &dev, const WalkArgs &a, bool walk, hipStream_t s) {
+    HIP_CHECK(hipEventRecord(e.ev[0], s));
+    if (walk) launch_walk(dev, a, s);
+    HIP_CHECK(hipEventRecord(e.ev[1], s));
+    HIP_CHECK(hipEventRecord(e.ev[2], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+}
+
+PlanIndex plan_index(const gbwt_hip_index *ix) {
+    PlanIndex p;
+    p.sequences = ix->host.sequences; p.size = ix->host.size; p.records = ix->stats.records;
+    p.has_samples = ix->dev.samples != nullptr;
+    p.max_samples = ix->max_samples; p.sample_coarse = ix->sample_coarse; p.uniform_samples = ix->uniform_samples; p.uniform_len = ix->uniform_len;
+    p.sample_counts = ix->sample_counts.data(); p.n_sample_counts = ix->sample_counts.size();
+    p.orientation_pairs = ix->orientation_pairs; p.lean = ix->lean_extract; p.packed_blocks = ix->packed_blocks;
+    return p;
+}
+
+// Lengths known: offsets first, then every lane writes into its row; in a bidirectional index two walkers per sequence, one from each
+// end.  Every decision is extract_plan.hpp's; here are the launches, the copies and the waits.
+gbwt_hip_status direct_rows(const Request &r) {
+    const gbwt_hip_index *ix = r.ix;
+    ExtractState &e = r.ws->extract;
+    const ExtractKnobs &knobs = r.ws->knobs;
+    hipStream_t s = r.ws->stream;
+    const uint64_t n = r.n;
+    const PlanIndex pi = plan_index(ix);
+    const IdSummary ids = summarize_ids(r.seq_ids, n, pi);
+    const uint64_t capacity = e.nodes.bytes / sizeof(uint32_t);
+    const RowsPlan rows = plan_rows(knobs, pi, ids, n, r.part, r.parts, capacity);
+    if (rows.empty_part) return empty_rows(r, false);
+    DeviceIndex strided = ix->dev; strided.sample_stride = rows.stride;
+    if (rows.parted) { strided.sample_part = r.part; strided.sample_parts = r.parts; }
+    // lengths, offsets and extremes: one launch for the batch sizes there are, else a memset and three
+    if (!rows.fused_offsets && !launch_row_offsets(strided, e.seq_ids.as<uint64_t>(), n, e.lengths.as<uint64_t>(), e.offsets.as<uint64_t>(), e.counters.as<uint32_t>(), s)) {
+        HIP_CHECK(hipMemsetAsync(e.counters.ptr, 0, 4 * sizeof(uint32_t), s));
+        if (rows.parted) launch_part_lengths(strided, e.seq_ids.as<uint64_t>(), n, e.lengths.as<uint64_t>(), e.counters.as<uint32_t>(), s);
+        else launch_gather_lengths(ix->dev.seq_len, ix->dev.n_sequences, e.seq_ids.as<uint64_t>(), n, e.lengths.as<uint64_t>(), e.counters.as<uint32_t>(), s);
+        launch_scan(e.lengths.as<uint64_t>(), e.offsets.as<uint64_t>(), n, r.ws->scratch.scan_temp.ptr, r.temp_bytes, s);
+    }
+    uint64_t total = rows.total;
+    uint32_t max_len = rows.max_len;
+    if (rows.defer) {
+        e.pinned_words.ensure();
+        HIP_CHECK(hipMemcpyAsync(e.pinned_words.p, e.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    } else if (!rows.all_valid) {
+        uint32_t extremes[2] = {0, 0};   // the longest row, ~(the shortest)
+        HIP_CHECK(hipMemcpyAsync(&total, e.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(extremes, e.counters.ptr, sizeof(extremes), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        max_len = extremes[0];
+    }
+    e.nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
+    const WalkPlan p = plan_walk(knobs, pi, rows, ids.ids_valid, n, r.part, r.parts, max_len, capacity);
+    if (p.refused)
+        return fail(GBWT_HIP_UNSUPPORTED, "this handle was opened for extraction only and has given its raw descriptors back: walks that do not start from sequence samples (GBWT_HIP_SEGMENTS=0, more than 2^31 - 1 rows) need GBWT_HIP_OPEN_ALL");
+    WalkArgs a{};
+    a.seq_ids = e.seq_ids.as<uint64_t>(); a.n = n;
+    a.mode = knobs.walk_mode;
+    a.segments = p.segments;
+    uint64_t walkers = p.walkers;
+    if (p.same_segments) a.walkers = walkers;
+    if (p.needs_order) {
+        const size_t ob = walker_order_temp_bytes(n), sb = scan_temp_bytes(a.segments);
+        e.order_keys.reserve(2 * n * sizeof(uint32_t)); e.order_rows.reserve(2 * n * sizeof(uint32_t));
+        e.order_counts.reserve(a.segments * sizeof(uint64_t)); e.order_level.reserve((a.segments + 1ull) * sizeof(uint64_t));
+        e.order_temp.reserve(std::max<size_t>(std::max(ob, sb), 16));
+        const uint32_t *sorted_rows = nullptr;
+        launch_walker_order(strided, e.seq_ids.as<uint64_t>(), n, a.segments, e.order_keys.as<uint32_t>(), e.order_rows.as<uint32_t>(),
+                            e.order_counts.as<uint64_t>(), e.order_level.as<uint64_t>(), e.order_temp.ptr, ob, &sorted_rows, s);
+        launch_scan(e.order_counts.as<uint64_t>(), e.order_level.as<uint64_t>(), a.segments, e.order_temp.ptr, sb, s);
+        HIP_CHECK(hipMemcpyAsync(&walkers, e.order_level.as<uint64_t>() + a.segments, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        a.sorted_rows = sorted_rows; a.level = e.order_level.as<uint64_t>(); a.walkers = walkers;
+    }
+    a.paths_per_wave = p.paths_per_wave;
+    a.helper_lanes = 64u;
+    a.wide_addresses = p.wide_addresses;
+    a.ring_slots = p.ring_slots;
+    a.helper_naps = p.helper_naps;
+    a.out_nodes = e.nodes.as<uint32_t>(); a.out_offsets = e.offsets.as<uint64_t>();
+    a.xcd_map = p.xcd_map;
+    a.uniform_loop = p.uniform_loop;
+    a.catch_up = p.catch_up;
+    a.gather_reach = p.gather_reach;
+    a.all4 = p.all4;
+    a.headroom = p.headroom;
+    a.packed_blocks = p.packed_blocks;
+    a.row_piece = p.row_piece;
+    a.debug = p.debug;
+    a.both_ends = p.both_ends;
+    a.capacity = p.capacity;
+    if (p.uniform_len) { a.uniform_len = p.uniform_len; a.fill_offsets = e.offsets.as<uint64_t>(); }
+    DeviceIndex dev = a.packed_blocks ? ix->dev : with_cblocks(ix);
+    dev.sample_stride = strided.sample_stride; dev.sample_part = strided.sample_part; dev.sample_parts = strided.sample_parts;
+    walk_and_wait(e, dev, a, !rows.parted || (total != 0 && walkers != 0), s);   // (a part of nothing but empty stretches: no walkers)
+    if (rows.defer) {
+        total = e.pinned_words.p[0];
+        if (total > capacity) {                              // the rows were too small and nobody walked: make them, walk
+            e.nodes.reserve(total * sizeof(uint32_t));
+            a.out_nodes = e.nodes.as<uint32_t>(); a.capacity = 0;
+            walk_and_wait(e, dev, a, walkers != 0, s);
+        }
+    }
+    return finish(r, total, !rows.parted);
+}
+
+// No sequence lengths, GBWT_HIP_DIRECT=0 or a tuned walk mode: whole rows into a pool of blocks, then compacted into the CSR
+gbwt_hip_status pool_rows(const Request &r) {
+    const gbwt_hip_index *ix = r.ix;
+    ExtractState &e = r.ws->extract;
+    const ExtractKnobs &knobs = r.ws->knobs;
+    hipStream_t s = r.ws->stream;
+    const uint64_t n = r.n;
+    if (ix->lean_extract) return fail(GBWT_HIP_UNSUPPORTED, "this handle was opened for extraction only and has given its raw descriptors back: the pool-output walk modes need GBWT_HIP_OPEN_ALL");
+    // The pool-output kernels walk whole rows and cannot cut them: as the header says for rows that cannot be cut, the LAST part is the
+    // whole row and every earlier part is n empty rows -- never the whole row from every part (a gather of parts would then hold every
+    // row `parts` times).
+    if (r.parts > 1 && r.part + 1 < r.parts) return empty_rows(r, false);
+    uint64_t pool_blocks = plan_pool_blocks(plan_index(ix), n, POOL_BLOCK_NODES);
+    uint32_t flags = 0;
+    WalkArgs a{};
+    const DeviceIndex dev = knobs.walk_mode == WALK_TWO_STEP ? with_cblocks(ix) : ix->dev;   // the pool-output kernel walks on the full-width two-step blocks
+    for (int attempt = 0; attempt < 8; attempt++) {
+        if (pool_blocks >= POOL_NONE) return fail(GBWT_HIP_UNSUPPORTED, "path pool would exceed 2^32 blocks");
+        e.pool.reserve(pool_blocks * POOL_BLOCK_NODES * sizeof(uint32_t));
+        e.next.reserve(pool_blocks * sizeof(uint32_t));
+        a.seq_ids = e.seq_ids.as<uint64_t>(); a.n = n;
+        a.pool = e.pool.as<uint32_t>(); a.next = e.next.as<uint32_t>(); a.pool_blocks = static_cast<uint32_t>(pool_blocks);
+        a.counter = e.counters.as<uint32_t>(); a.flags = e.counters.as<uint32_t>() + 1;
+        a.head = e.head.as<uint32_t>(); a.lengths = e.lengths.as<uint64_t>();
+        a.mode = knobs.walk_mode; a.small_record = knobs.small_record;
+        a.paths_per_wave = plan_pool_paths_per_wave(knobs, n);
+        a.pack16 = ix->stats.max_record_len < 65536 ? 1u : 0u;
+        a.helper_lanes = 64u;
+        a.wide_addresses = knobs.wide_addresses;
+        HIP_CHECK(hipMemsetAsync(e.counters.ptr, 0, 4 * sizeof(uint32_t), s));
+        HIP_CHECK(hipEventRecord(e.ev[0], s));
+        launch_walk(dev, a, s);
+        HIP_CHECK(hipEventRecord(e.ev[1], s));
+        HIP_CHECK(hipMemcpyAsync(&flags, a.flags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        launch_scan(a.lengths, e.offsets.as<uint64_t>(), n, r.ws->scratch.scan_temp.ptr, r.temp_bytes, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        if (!(flags & FLAG_POOL_OVERFLOW)) break;
+        pool_blocks *= 2;  // duplicate ids can exceed the distinct-id bound: grow and walk again
+    }
+    if (flags & FLAG_POOL_OVERFLOW) return fail(GBWT_HIP_DEVICE_ERROR, "path pool overflow");
+    uint64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, e.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    e.nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
+    launch_compact(a, e.offsets.as<uint64_t>(), e.nodes.as<uint32_t>(), s);
+    HIP_CHECK(hipEventRecord(e.ev[2], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    return finish(r, total, true);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -35,10 +233,6 @@ gbwt_hip_status gbwt_hip_workspace_create(const gbwt_hip_index *index, gbwt_hip_
     ws->stream.create(hipStreamNonBlocking);
     ws->extract.ev.ensure();
     ws->extract.counters.reserve(4 * sizeof(uint32_t));
-    // optional overrides for experiments / tests (same meaning as gbwt_hip_workspace_tune)
-    if (const char *v = std::getenv("GBWT_HIP_WALK_MODE")) { int m = std::atoi(v); if (m >= 0 && m <= 3) ws->walk_mode = static_cast<uint32_t>(m); }
-    if (const char *v = std::getenv("GBWT_HIP_PATHS_PER_WAVE")) { int p = std::atoi(v); if (p >= 0 && p <= 64) ws->paths_per_wave = static_cast<uint32_t>(p); }
-    if (const char *v = std::getenv("GBWT_HIP_SMALL_RECORD")) { long r = std::atol(v); if (r >= 0) ws->small_record = static_cast<uint32_t>(r); }
     *out = ws.release();
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
@@ -49,7 +243,7 @@ void gbwt_hip_workspace_destroy(gbwt_hip_workspace *ws) { delete ws; }
 gbwt_hip_status gbwt_hip_workspace_tune(gbwt_hip_workspace *ws, uint32_t walk_mode, uint32_t paths_per_wave, uint32_t small_record) {
     GBWT_HIP_GUARD_BEGIN
     if (!ws || walk_mode > WALK_ONE_STEP || paths_per_wave > 64) return fail(GBWT_HIP_BAD_ARGUMENT, "bad tuning values");
-    ws->walk_mode = walk_mode; ws->paths_per_wave = paths_per_wave; ws->small_record = small_record;
+    ws->knobs.walk_mode = walk_mode; ws->knobs.paths_per_wave = paths_per_wave; ws->knobs.small_record = small_record;
     return GBWT_HIP_OK;
     GBWT_HIP_GUARD_END
 }
@@ -64,271 +258,36 @@ gbwt_hip_status gbwt_hip_extract_device(const gbwt_hip_index *ix, gbwt_hip_works
 gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const uint64_t *seq_ids, uint64_t n,
                                              uint32_t part, uint32_t parts, gbwt_hip_paths *out) {
     GBWT_HIP_GUARD_BEGIN
+    // 1. the workspace of this handle -- 2. and what copy_result / path_sums / copy_path trust of it: gone whatever becomes of this request,
+    // one that is refused for its other arguments included, and set again only by finish()
     if (!ix || !ws || ws->index != ix || !out) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
+    ExtractState &e = ws->extract;
+    e.memo.drop();
+    e.timed = false; e.last_n = 0; e.last_total = 0;
     if (n && !seq_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null seq_ids");
     if (parts == 0 || part >= parts) return fail(GBWT_HIP_BAD_ARGUMENT, "part must be < parts");
     if (!(ix->caps & GBWT_HIP_OPEN_EXTRACT)) return fail(GBWT_HIP_BAD_ARGUMENT, "the handle was not opened for extraction (GBWT_HIP_OPEN_EXTRACT)");
     // GBWT::sequence: id >= sequences -> no iterator (src/gbwt.rs:254-256).  "Not found" is a value here as well: such an id
     // gets an empty row (the kernels test the id), the rest of the batch is extracted; callers tell None from an empty
     // sequence by id < sequences.
-    ws->extract.memo.drop();
-    ws->extract.timed = false; ws->extract.last_n = 0; ws->extract.last_total = 0;   // what copy_result / path_sums / copy_path trust: set again only when this call succeeds
     try {
+        // 3. the ids on the device, room for what every body needs
         HIP_CHECK(hipSetDevice(ix->device));
         hipStream_t s = ws->stream;
-        ws->extract.seq_ids.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
-        ws->extract.lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
-        ws->extract.offsets.reserve((n + 1) * sizeof(uint64_t));
-        ws->extract.head.reserve(std::max<uint64_t>(n, 1) * sizeof(uint32_t));
-        size_t temp_bytes = n ? scan_temp_bytes(n) : 0;
-        ws->scratch.scan_temp.reserve(std::max<size_t>(temp_bytes, 16));
-        // Pool bound for distinct ids: all sequences together hold size - sequences nodes
-        // (src/gbwt.rs:108-122), and every path wastes less than one block.
-        const uint64_t all_nodes = ix->host.size >= ix->host.sequences ? ix->host.size - ix->host.sequences : 0;
-        uint64_t pool_blocks = all_nodes / POOL_BLOCK_NODES + n + 1;
-        HIP_CHECK(hipEventRecord(ws->extract.ev[3], s));   // everything the extraction puts on the stream lies between ev[3] and ev[2]
-        if (n) HIP_CHECK(hipMemcpyAsync(ws->extract.seq_ids.ptr, seq_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        const ExtractKnobs &knobs = ws->knobs;
-        if (n && ix->dev.seq_len && ws->walk_mode == WALK_TWO_STEP && knobs.direct != 0) {
-            // Lengths known: offsets first, then every lane writes into its row; in a bidirectional index two walkers per
-            // sequence, one from each end.
-            bool ids_valid = true;
-            for (uint64_t k = 0; k < n && ids_valid; k++) ids_valid = seq_ids[k] < ix->host.sequences;
-            // ONE PART OF EVERY ROW (gbwt_hip_extract_part_device; round 4): rows are cut where their walkers start anyway, at sequence samples.
-            // An index without samples (GBWT_HIP_SAMPLE_INTERVAL=0, GBWT_HIP_SEGMENTS=0) cannot cut: the last part is the whole row there.
-            const bool can_cut = ix->dev.samples != nullptr && ix->max_samples > 0 && knobs.segments != 0 && n <= 0x7FFFFFFFull;
-            if (parts > 1 && !can_cut && part + 1 < parts) {
-                HIP_CHECK(hipMemsetAsync(ws->extract.offsets.ptr, 0, (n + 1) * sizeof(uint64_t), s));
-                ws->extract.nodes.reserve(sizeof(uint32_t));
-                HIP_CHECK(hipEventRecord(ws->extract.ev[0], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[1], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                ws->extract.timed = true; ws->extract.last_n = n; ws->extract.last_total = 0;
-                out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = 0; out->n = n;
-                return GBWT_HIP_OK;
-            }
-            const bool parted = parts > 1 && can_cut;
-            // a walker per `stride` samples of a row (fine samples, gbwt_hip_open): about 2.9 million walkers for the biggest batches, no segments
-            // shorter than two samples unless the batch is so small that it needs every walker it can get
-            uint32_t stride = static_cast<uint32_t>(std::max(1, knobs.sample_stride));
-            if (knobs.sample_stride < 0 && can_cut && ix->sample_coarse > 1) {
-                uint64_t fine = 0;
-                for (uint64_t k = 0; k < n; k++) if (seq_ids[k] < ix->host.sequences) fine += ix->sample_counts[seq_ids[k]];
-                if (parted) fine /= parts;
-                const uint64_t want = (fine + 1450000) / 2900000;
-                stride = static_cast<uint32_t>(std::min<uint64_t>(2 * ix->sample_coarse, std::max<uint64_t>(want, fine >= 524288 ? 2 : 1)));
-            }
-            DeviceIndex strided = ix->dev; strided.sample_stride = stride;
-            if (parted) { strided.sample_part = part; strided.sample_parts = parts; }
-            // every row of one, known length (the headline's shape, config 5): no table of offsets is needed to walk, and the walk kernel
-            // writes the one the caller gets (WalkArgs::uniform_len) -- nothing is launched in front of it
-            const bool all_valid = ids_valid && ix->uniform_len != 0 && !parted;
-            const bool fused_offsets = all_valid && knobs.fused_offsets != 0;
-            // lengths, offsets and extremes: one launch for the batch sizes there are, else a memset and three
-            if (!fused_offsets && !launch_row_offsets(strided, ws->extract.seq_ids.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>(), ws->extract.offsets.as<uint64_t>(), ws->extract.counters.as<uint32_t>(), s)) {
-                HIP_CHECK(hipMemsetAsync(ws->extract.counters.ptr, 0, 4 * sizeof(uint32_t), s));
-                if (parted) launch_part_lengths(strided, ws->extract.seq_ids.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>(), ws->extract.counters.as<uint32_t>(), s);
-                else launch_gather_lengths(ix->dev.seq_len, ix->dev.n_sequences, ws->extract.seq_ids.as<uint64_t>(), n, ws->extract.lengths.as<uint64_t>(), ws->extract.counters.as<uint32_t>(), s);
-                launch_scan(ws->extract.lengths.as<uint64_t>(), ws->extract.offsets.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, temp_bytes, s);
-            }
-            uint64_t total = 0;
-            uint32_t extremes[2] = {0, 0};   // the longest row, ~(the shortest)
-            // every row of the batch with the same number of samples (the forward sequences of haplotypes over one reference frame: the
-            // headline's shape): walker w = segment * n + row, no order to compute -- and nothing the host has to ask the device for
-            uint32_t common = ix->uniform_samples;
-            if (can_cut && ids_valid && common == 0 && n != 0) {
-                common = ix->sample_counts[seq_ids[0]];
-                for (uint64_t k = 1; k < n && common != 0; k++) if (ix->sample_counts[seq_ids[k]] != common) common = 0;
-            }
-            // ROWS SIZED AFTER THE LAUNCH (round 4): a request that knows its walkers without the device (above) and finds rows in its
-            // workspace does not wait for the total of its row lengths either -- 20 us of a round trip in front of a walk of 0.6 ms: the walk
-            // is launched into the rows that are there with their size as `capacity`, every workgroup looks at offsets[n] first, and
-            // if the rows were too small (the first request of its size) the host makes them and launches again.  One host wait per request.
-            const uint64_t capacity = ws->extract.nodes.bytes / sizeof(uint32_t);
-            const bool defer = knobs.defer_total != 0 && !all_valid && can_cut && ids_valid && common != 0 && capacity != 0;
-            if (all_valid) {
-                // every row has the same, known length: total and extremes without a round trip to the device (the offsets are
-                // still scanned there, behind which the walk is simply enqueued)
-                total = n * static_cast<uint64_t>(ix->uniform_len);
-                extremes[0] = ix->uniform_len; extremes[1] = ~ix->uniform_len;
-            } else if (defer) {
-                ws->extract.pinned_words.ensure();
-                HIP_CHECK(hipMemcpyAsync(ws->extract.pinned_words.p, ws->extract.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                total = capacity;                                  // (stands in until the wait at the end)
-                extremes[0] = 1; extremes[1] = ~1u;                // (a row may have nodes: the walk is a segmented one)
-            } else {
-                HIP_CHECK(hipMemcpyAsync(&total, ws->extract.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipMemcpyAsync(extremes, ws->extract.counters.ptr, sizeof(extremes), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-            }
-            const uint32_t max_len = extremes[0];
-            ws->extract.nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
-            WalkArgs a{};
-            a.seq_ids = ws->extract.seq_ids.as<uint64_t>(); a.n = n;
-            a.mode = ws->walk_mode;
-            // many walkers per row when the index has sequence samples (GBWT_HIP_SEGMENTS=0: one walker per end instead)
-            const bool segmented = ix->dev.samples != nullptr && max_len > 0 && n <= 0x7FFFFFFFull && ix->max_samples > 0 && knobs.segments != 0;   // (the walker order sorts 32-bit row numbers)
-            // A lean handle (open_common) has given back the raw descriptors that a walker without a sample to start from reads when it arrives
-            // on its first record (walk_loops.hpp: arrive): whole-row walkers -- GBWT_HIP_SEGMENTS=0, more than 2^31 - 1 rows -- are refused
-            // there like the pool-output modes below, before anything is launched (rows of no nodes have no walker and are served).
-            if (ix->lean_extract && !segmented && max_len > 0)
-                return fail(GBWT_HIP_UNSUPPORTED, "this handle was opened for extraction only and has given its raw descriptors back: walks that do not start from sequence samples (GBWT_HIP_SEGMENTS=0, more than 2^31 - 1 rows) need GBWT_HIP_OPEN_ALL");
-            // the samples lie where the sequences pass checkpoint records, so the number of segments of a row comes from its samples, not from its length
-            a.segments = segmented ? (ix->max_samples + stride - 1) / stride : 0u;
-            if (parted) a.segments = a.segments / parts + 1;          // (no row has more segments in one part)
-            uint64_t walkers = ix->orientation_pairs ? 2 * n : n;
-            const bool same_segments = segmented && ids_valid && common != 0;
-            if (same_segments) {
-                a.segments = (common + stride - 1) / stride;
-                if (parted) a.segments = static_cast<uint32_t>(uint64_t(a.segments) * (part + 1) / parts - uint64_t(a.segments) * part / parts);   // (device_index.hpp: row_segments)
-                walkers = static_cast<uint64_t>(a.segments) * n;   // every row has every segment: no order to compute
-                a.sorted_rows = nullptr; a.level = nullptr; a.walkers = walkers;
-            } else if (segmented) {
-                // rows with different numbers of segments: walkers segment by segment over the rows that have the segment (rows sorted by their segment count)
-                const size_t ob = walker_order_temp_bytes(n), sb = scan_temp_bytes(a.segments);
-                ws->extract.order_keys.reserve(2 * n * sizeof(uint32_t)); ws->extract.order_rows.reserve(2 * n * sizeof(uint32_t));
-                ws->extract.order_counts.reserve(a.segments * sizeof(uint64_t)); ws->extract.order_level.reserve((a.segments + 1ull) * sizeof(uint64_t));
-                ws->extract.order_temp.reserve(std::max<size_t>(std::max(ob, sb), 16));
-                const uint32_t *sorted_rows = nullptr;
-                launch_walker_order(strided, ws->extract.seq_ids.as<uint64_t>(), n, a.segments, ws->extract.order_keys.as<uint32_t>(), ws->extract.order_rows.as<uint32_t>(),
-                                    ws->extract.order_counts.as<uint64_t>(), ws->extract.order_level.as<uint64_t>(), ws->extract.order_temp.ptr, ob, &sorted_rows, s);
-                launch_scan(ws->extract.order_counts.as<uint64_t>(), ws->extract.order_level.as<uint64_t>(), a.segments, ws->extract.order_temp.ptr, sb, s);
-                HIP_CHECK(hipMemcpyAsync(&walkers, ws->extract.order_level.as<uint64_t>() + a.segments, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                a.sorted_rows = sorted_rows; a.level = ws->extract.order_level.as<uint64_t>(); a.walkers = walkers;
-            }
-            // many walkers: the walk is a throughput problem, full waves; few walkers (one or two per row): latency, and
-            // about one workgroup per four SIMDs keeps every workgroup resident (32 KB of LDS each)
-            a.paths_per_wave = ws->paths_per_wave ? ws->paths_per_wave
-                               : segmented ? 64u : static_cast<uint32_t>(std::min<uint64_t>(64, std::max<uint64_t>(16, (walkers + 1023) / 1024)));
-            a.helper_lanes = 64u;
-            a.wide_addresses = knobs.wide_addresses ? 1u : 0u;
-            a.ring_slots = knobs.ring_slots > 0 ? static_cast<uint32_t>(knobs.ring_slots) : (segmented ? 64u : 128u);   // many walkers: smaller rings, more workgroups per CU (7.4 vs 8.1 ms on the headline)
-            // many walkers per CU: a helper that polls less leaves more issue slots and LDS cycles to them (6 until the packed half-blocks
-            // made the walkers faster: 3 / 4 / 6 / 8 / 10 naps = 4.30 / 4.31 / 4.35 / 4.42 / 4.51 ms)
-            a.helper_naps = knobs.helper_naps >= 0 ? static_cast<uint32_t>(knobs.helper_naps) : (segmented ? 4u : 1u);
-            a.out_nodes = ws->extract.nodes.as<uint32_t>(); a.out_offsets = ws->extract.offsets.as<uint64_t>();
-            a.xcd_map = knobs.xcd_map >= 0 ? (knobs.xcd_map ? 1u : 0u) : (segmented ? 1u : 0u);
-            a.uniform_loop = knobs.uniform_loop >= 0 ? (knobs.uniform_loop ? 1u : 0u) : 1u;
-            // (2: single steps on the two-step descriptors + packed half-blocks: what a lean handle has -- and GBWT_HIP_CATCH_UP=2 on any)
-            a.catch_up = knobs.catch_up >= 0 ? static_cast<uint32_t>(std::min(knobs.catch_up, 2)) : 1u;
-            if (ix->lean_extract && a.catch_up == 1u) a.catch_up = 2u;
-            if (a.catch_up == 2u && !(ix->packed_blocks && knobs.packed_blocks != 0)) a.catch_up = ix->lean_extract ? 0u : 1u;
-            // look-ahead in mixed waves where few rows pass a record (fewer than 512 BWT positions per record on average: config 4 has 52, the
-            // headline 3 300 -- there seventy waves share every line and the extra load of the gather loop costs what it saves, round 2)
-            a.gather_reach = knobs.gather_reach >= 0 ? static_cast<uint32_t>(knobs.gather_reach)
-                                                     : (ix->stats.records != 0 && ix->host.size / ix->stats.records < 512 ? 1u : 0u);
-            a.all4 = knobs.all4 != 0 ? 1u : 0u;
-            a.headroom = static_cast<uint32_t>(knobs.headroom);
-            // without packed half-blocks every wave starts on the full-width loops (the packed ones load before they look at GATHER_OK)
-            a.packed_blocks = (ix->packed_blocks && knobs.packed_blocks != 0) ? 1u : 0u;
-            DeviceIndex dev = a.packed_blocks ? ix->dev : with_cblocks(ix);
-            dev.sample_stride = stride; dev.sample_part = strided.sample_part; dev.sample_parts = strided.sample_parts;
-            a.row_piece = knobs.row_piece >= 0 ? static_cast<uint32_t>(knobs.row_piece) : 32u;
-            if (a.ring_slots < 2 * a.row_piece) a.ring_slots = 2 * a.row_piece;   // a walker stops staging 8 slots before its ring is full: a ring of one piece would never hold one
-            // GBWT_HIP_HEADROOM: the walkers wait while more than ring - headroom nodes are pending, the cooperative helper moves whole pieces only:
-            // a headroom above ring - piece would leave a row with fewer than a piece pending and its walker waiting for ever
-            if (a.headroom > a.ring_slots - std::max(a.row_piece, 1u)) a.headroom = a.ring_slots - std::max(a.row_piece, 1u);
-            a.debug = knobs.debug;                               // timing experiments only, see WalkArgs::debug
-            a.both_ends = (ix->orientation_pairs && knobs.both_ends != 0) ? 1u : 0u;
-            a.capacity = defer ? capacity : 0;
-            if (fused_offsets) { a.uniform_len = ix->uniform_len; a.fill_offsets = ws->extract.offsets.as<uint64_t>(); }
-            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s));
-            if (!parted || (total != 0 && walkers != 0)) launch_walk(dev, a, s);   // (a part of nothing but empty stretches: no walkers)
-            HIP_CHECK(hipEventRecord(ws->extract.ev[1], s));
-            HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipGetLastError());
-            if (defer) {
-                total = ws->extract.pinned_words.p[0];
-                if (total > capacity) {                              // the rows were too small and nobody walked: make them, walk
-                    ws->extract.nodes.reserve(total * sizeof(uint32_t));
-                    a.out_nodes = ws->extract.nodes.as<uint32_t>(); a.capacity = 0;
-                    HIP_CHECK(hipEventRecord(ws->extract.ev[0], s));
-                    if (walkers != 0) launch_walk(dev, a, s);
-                    HIP_CHECK(hipEventRecord(ws->extract.ev[1], s));
-                    HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
-                    HIP_CHECK(hipStreamSynchronize(s));
-                    HIP_CHECK(hipGetLastError());
-                }
-            }
-            ws->extract.timed = true; ws->extract.last_n = n; ws->extract.last_total = total;
-            if (!parted) ws->extract.memo.store({{seq_ids, n * sizeof(uint64_t)}}, {});   // (gbwt_hip_extract's fill call asks for whole rows)
-            out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = total; out->n = n;
-            return GBWT_HIP_OK;
-        }
-        if (n == 0) {                                        // nothing asked for: an empty CSR, whatever the handle holds
-            HIP_CHECK(hipMemsetAsync(ws->extract.offsets.ptr, 0, sizeof(uint64_t), s));
-            ws->extract.nodes.reserve(sizeof(uint32_t));
-            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[1], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            ws->extract.timed = true; ws->extract.last_n = 0; ws->extract.last_total = 0;
-            ws->extract.memo.store({{nullptr, 0}}, {});
-            out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = 0; out->n = 0;
-            return GBWT_HIP_OK;
-        }
-        if (ix->lean_extract) return fail(GBWT_HIP_UNSUPPORTED, "this handle was opened for extraction only and has given its raw descriptors back: the pool-output walk modes need GBWT_HIP_OPEN_ALL");
-        // The pool-output kernels (no sequence lengths, GBWT_HIP_DIRECT=0, a tuned walk mode) walk whole rows and cannot cut them: as the
-        // header says for rows that cannot be cut, the LAST part is the whole row and every earlier part is n empty rows -- never the whole
-        // row from every part (a gather of parts would then hold every row `parts` times).
-        if (parts > 1 && part + 1 < parts) {
-            HIP_CHECK(hipMemsetAsync(ws->extract.offsets.ptr, 0, (n + 1) * sizeof(uint64_t), s));
-            ws->extract.nodes.reserve(sizeof(uint32_t));
-            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[1], s)); HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            ws->extract.timed = true; ws->extract.last_n = n; ws->extract.last_total = 0;
-            out->d_offsets = ws->extract.offsets.as<uint64_t>(); out->d_nodes = ws->extract.nodes.as<uint32_t>(); out->total = 0; out->n = n;
-            return GBWT_HIP_OK;
-        }
-        uint32_t flags = 0;
-        WalkArgs a{};
-        const DeviceIndex dev = ws->walk_mode == WALK_TWO_STEP ? with_cblocks(ix) : ix->dev;   // the pool-output kernel walks on the full-width two-step blocks
-        for (int attempt = 0; attempt < 8; attempt++) {
-            if (pool_blocks >= POOL_NONE) return fail(GBWT_HIP_UNSUPPORTED, "path pool would exceed 2^32 blocks");
-            ws->extract.pool.reserve(pool_blocks * POOL_BLOCK_NODES * sizeof(uint32_t));
-            ws->extract.next.reserve(pool_blocks * sizeof(uint32_t));
-            a.seq_ids = ws->extract.seq_ids.as<uint64_t>(); a.n = n;
-            a.pool = ws->extract.pool.as<uint32_t>(); a.next = ws->extract.next.as<uint32_t>(); a.pool_blocks = static_cast<uint32_t>(pool_blocks);
-            a.counter = ws->extract.counters.as<uint32_t>(); a.flags = ws->extract.counters.as<uint32_t>() + 1;
-            a.head = ws->extract.head.as<uint32_t>(); a.lengths = ws->extract.lengths.as<uint64_t>();
-            a.mode = ws->walk_mode; a.small_record = ws->small_record;
-            // automatic: the walk is latency-bound and every lane of a wave runs the same instructions whether it owns a
-            // sequence or not, so owners per wave cost nothing; at least 32 measured best (fewer, fuller waves keep the walks
-            // of an XCD closer together, which is what the look-ahead relies on), more only when there are > 32k sequences
-            a.paths_per_wave = ws->paths_per_wave ? ws->paths_per_wave
-                                                   : static_cast<uint32_t>(std::min<uint64_t>(64, std::max<uint64_t>(32, (n + 1023) / 1024)));
-            a.pack16 = ix->stats.max_record_len < 65536 ? 1u : 0u;
-            a.helper_lanes = 64u;
-            a.wide_addresses = knobs.wide_addresses ? 1u : 0u;
-            HIP_CHECK(hipMemsetAsync(ws->extract.counters.ptr, 0, 4 * sizeof(uint32_t), s));
-            HIP_CHECK(hipEventRecord(ws->extract.ev[0], s));
-            launch_walk(dev, a, s);
-            HIP_CHECK(hipEventRecord(ws->extract.ev[1], s));
-            HIP_CHECK(hipMemcpyAsync(&flags, a.flags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            launch_scan(a.lengths, ws->extract.offsets.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, temp_bytes, s);
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipGetLastError());
-            if (!(flags & FLAG_POOL_OVERFLOW)) break;
-            pool_blocks *= 2;  // duplicate ids can exceed the distinct-id bound: grow and walk again
-        }
-        if (flags & FLAG_POOL_OVERFLOW) return fail(GBWT_HIP_DEVICE_ERROR, "path pool overflow");
-        uint64_t total = 0;
-        HIP_CHECK(hipMemcpyAsync(&total, ws->extract.offsets.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        ws->extract.nodes.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
-        launch_compact(a, ws->extract.offsets.as<uint64_t>(), ws->extract.nodes.as<uint32_t>(), s);
-        HIP_CHECK(hipEventRecord(ws->extract.ev[2], s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        HIP_CHECK(hipGetLastError());
-        ws->extract.timed = true;
-        ws->extract.last_n = n; ws->extract.last_total = total;
-        ws->extract.memo.store({{seq_ids, n * sizeof(uint64_t)}}, {});
-        out->d_offsets = ws->extract.offsets.as<uint64_t>();
-        out->d_nodes = ws->extract.nodes.as<uint32_t>();
-        out->total = total;
-        out->n = n;
-        return GBWT_HIP_OK;
-    } catch (const HipError &e) {
-        return status_of(e);
+        e.seq_ids.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+        e.lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+        e.offsets.reserve((n + 1) * sizeof(uint64_t));
+        e.head.reserve(std::max<uint64_t>(n, 1) * sizeof(uint32_t));
+        const Request r{ix, ws, seq_ids, n, part, parts, n ? scan_temp_bytes(n) : 0, out};
+        ws->scratch.scan_temp.reserve(std::max<size_t>(r.temp_bytes, 16));
+        HIP_CHECK(hipEventRecord(e.ev[3], s));   // everything the extraction puts on the stream lies between ev[3] and ev[2]
+        if (n) HIP_CHECK(hipMemcpyAsync(e.seq_ids.ptr, seq_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        // 4. one of three bodies, 5. each of which ends in finish()
+        if (n == 0) return empty_rows(r, true);              // nothing asked for: an empty CSR, whatever the handle holds
+        if (ix->dev.seq_len && ws->knobs.walk_mode == WALK_TWO_STEP && ws->knobs.direct != 0) return direct_rows(r);
+        return pool_rows(r);
+    } catch (const HipError &err) {
+        return status_of(err);
     }
     GBWT_HIP_GUARD_END
 }

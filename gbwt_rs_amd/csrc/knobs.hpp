@@ -7,6 +7,7 @@
 #include <optional>
 
 #include "device_index.hpp"
+#include "extract_knobs.hpp"   // ExtractKnobs: the settings of a workspace, in plain C++ for extract_plan.hpp
 
 // The GBWT_HIP_* settings of an open, read ONCE by gbwt_hip_open_file_flags / gbwt_hip_open_records_flags before the loader or any thread
 // of the open starts, and kept on the handle: nothing else of an open looks at the environment (getenv is not safe against a concurrent
@@ -55,43 +56,5 @@ struct OpenKnobs {
     static bool lazy_host_records() {
         static const bool lazy = [] { const char *e = std::getenv("GBWT_HIP_LAZY_HOST_RECORDS"); return !(e && e[0] == '0'); }();
         return lazy;
-    }
-};
-
-// The GBWT_HIP_* tuning / measurement switches of an extraction, read ONCE when the workspace is created: gbwt_hip_extract_device
-// itself never looks at the environment (getenv is not safe against a concurrent setenv, and several host threads extract from one
-// index at the same time, each with its own workspace -- include/gbwt_hip.h).  -1 = not set: the library's default for the batch.
-struct ExtractKnobs {
-    int direct = 1, segments = 1, both_ends = 1;             // GBWT_HIP_DIRECT / _SEGMENTS / _BOTH_ENDS (0 switches the feature off)
-    int all4 = 1;                                             // GBWT_HIP_ALL4: 0 = the uniform loop counts every node it stages (rounds 1-3)
-    int sample_stride = -1;                                   // GBWT_HIP_SAMPLE_STRIDE: a walker per this many samples of a row; -1 = by the size of the batch (gbwt_hip_extract_device)
-    int defer_total = 1;                                      // GBWT_HIP_DEFER_TOTAL: 0 = every request waits for the total of its row lengths before it launches the walk (rounds 1-3)
-    int fused_offsets = 1;                                    // GBWT_HIP_FUSED_OFFSETS: 0 = the offsets of a batch of equally long rows come from k_row_offsets in front of the walk, as every batch's did until round 6 (WalkArgs::uniform_len)
-    int ring_slots = -1, helper_naps = -1, xcd_map = -1, uniform_loop = -1, packed_blocks = -1, row_piece = -1, catch_up = -1, headroom = 0;
-    int gather_reach = -1;                                    // GBWT_HIP_GATHER_REACH: look-ahead of mixed waves (WalkArgs::gather_reach); -1 = by the index (rows per record), 0 = none
-    bool wide_addresses = false;                              // GBWT_HIP_WIDE_ADDRESSES set (any value)
-    uint32_t debug = 0;                                       // GBWT_HIP_DEBUG_DRY_ROWS (measurement switches, WalkArgs::debug)
-    unsigned copy_threads = 8;                                // GBWT_HIP_COPY_THREADS
-    uint64_t locate_sort_piece = 0x7FFFFFFFull;               // GBWT_HIP_LOCATE_SORT_PIECE: items of one radix sort of a unique locate request (hipcub counts in int; tests lower it)
-    static ExtractKnobs from_env() {
-        ExtractKnobs k;
-        const auto num = [](const char *name, int unset) { const char *v = std::getenv(name); return v ? std::atoi(v) : unset; };
-        k.direct = num("GBWT_HIP_DIRECT", 1); k.segments = num("GBWT_HIP_SEGMENTS", 1); k.both_ends = num("GBWT_HIP_BOTH_ENDS", 1);
-        k.ring_slots = num("GBWT_HIP_RING_SLOTS", -1); if (k.ring_slots != 32 && k.ring_slots != 64 && k.ring_slots != 128) k.ring_slots = -1;
-        k.helper_naps = std::max(-1, num("GBWT_HIP_HELPER_NAPS", -1));
-        k.xcd_map = num("GBWT_HIP_XCD_MAP", -1); k.uniform_loop = num("GBWT_HIP_UNIFORM_LOOP", -1); k.packed_blocks = num("GBWT_HIP_PACKED_BLOCKS", -1);
-        k.catch_up = num("GBWT_HIP_CATCH_UP", -1);
-        k.gather_reach = std::min(64, std::max(-1, num("GBWT_HIP_GATHER_REACH", -1)));
-        k.sample_stride = num("GBWT_HIP_SAMPLE_STRIDE", -1);
-        k.defer_total = num("GBWT_HIP_DEFER_TOTAL", 1);
-        k.fused_offsets = num("GBWT_HIP_FUSED_OFFSETS", 1);
-        k.all4 = num("GBWT_HIP_ALL4", 1);
-        k.headroom = std::min(32, std::max(0, num("GBWT_HIP_HEADROOM", 0)));
-        k.row_piece = num("GBWT_HIP_ROW_PIECE", -1); if (k.row_piece != 0 && k.row_piece != 16 && k.row_piece != 32) k.row_piece = -1;
-        k.wide_addresses = std::getenv("GBWT_HIP_WIDE_ADDRESSES") != nullptr;
-        k.debug = static_cast<uint32_t>(num("GBWT_HIP_DEBUG_DRY_ROWS", 0));
-        k.copy_threads = static_cast<unsigned>(std::min(64, std::max(1, num("GBWT_HIP_COPY_THREADS", 8))));
-        k.locate_sort_piece = static_cast<uint64_t>(std::max(1, num("GBWT_HIP_LOCATE_SORT_PIECE", 0x7FFFFFFF)));
-        return k;
     }
 };

@@ -162,8 +162,7 @@ struct ScratchState {
 
 struct gbwt_hip_workspace {
     const gbwt_hip_index *index = nullptr;
-    ExtractKnobs knobs;
-    uint32_t walk_mode = gbwt_hip::WALK_TWO_STEP, paths_per_wave = 0, small_record = 16;   // paths_per_wave 0 = automatic
+    ExtractKnobs knobs;              // (with the walk mode, paths per wave and small-record size of gbwt_hip_workspace_tune)
     gbwt_hip::ExtractState extract;
     gbwt_hip::QueryState query;
     gbwt_hip::LinesState lines;

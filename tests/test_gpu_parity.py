@@ -1425,6 +1425,84 @@ def test_rows_sized_after_the_launch(monkeypatch, defer):
         assert np.array_equal(nodes[int(off[k]):int(off[k + 1])], o_nodes[int(o_off[h]):int(o_off[h + 1])])
 
 
+def test_every_exit_of_the_request_leaves_the_same_state(monkeypatch):
+    """gbwt_hip_extract_part_device has seven ways to succeed -- nothing asked, an early part of rows that cannot be cut, a direct request that
+    waits for its total, one that is sized after the launch and fits, one that must grow and launch again, a part of rows, the pool-output
+    walk -- and each leaves the workspace as every other does: the times answer, copy_result gives n + 1 offsets and exactly `total` nodes,
+    the checksums answer for n rows and for no other number.  A part of rows is not remembered as the rows (a gbwt_hip_extract fill call
+    with the same ids gets whole rows), and a request that fails leaves nothing to copy.  The knobs are read when a workspace is made: the
+    two exits that need one (GBWT_HIP_SEGMENTS=0, GBWT_HIP_DIRECT=0) get a fresh workspace of the same handle."""
+    import ctypes as C
+    monkeypatch.setenv("GBWT_HIP_SAMPLE_INTERVAL", "16")
+    rng = random.Random(5)
+    paths = [[2 * rng.randint(1, 40) + rng.randint(0, 1) for _ in range(ln)] for ln in (0, 1, 2, 17, 64, 65, 700)]
+    s = S.Synth.from_paths(paths, bidirectional=True)
+    dev = open_synth(s)
+    L, refused = dev._L, G._lib.GbwtHipError
+
+    def rows_of(ids):
+        return [[] if i >= s.sequences else paths[i // 2] if i % 2 == 0 else kat.reverse_path(paths[i // 2]) for i in ids]
+
+    def settled(out, n, want=None):
+        total = int(out.total)
+        assert int(out.n) == n
+        walk_ms, total_ms = dev.last_kernel_ms()
+        assert walk_ms >= 0 and total_ms >= 0
+        offsets = np.full(n + 2, 12345, dtype=np.uint64)
+        nodes = np.full(total + 1, 0xFFFFFFFF, dtype=np.uint32)
+        G._lib.check(L.gbwt_hip_copy_result(dev._h, dev._ws, offsets.ctypes.data, nodes.ctypes.data, total))
+        assert offsets[0] == 0 and offsets[n] == total and offsets[n + 1] == 12345 and nodes[total] == 0xFFFFFFFF      # n + 1 offsets, `total` nodes
+        assert np.all(np.diff(offsets[:n + 1].astype(np.int64)) >= 0) and (total == 0 or nodes[:total].max() < 0xFFFFFFFF)
+        if total:
+            assert L.gbwt_hip_copy_result(dev._h, dev._ws, offsets.ctypes.data, nodes.ctypes.data, total - 1) == G._lib.CAPACITY
+        got = [[int(v) for v in nodes[int(offsets[k]):int(offsets[k + 1])]] for k in range(n)]
+        if want is not None:
+            assert got == want
+        assert [int(v) for v in dev.path_sums(n)] == [sum(r) for r in got]
+        with pytest.raises(refused):
+            dev.path_sums(n + 1)
+        return got
+
+    everything = np.array(list(range(s.sequences)) + [s.sequences + 3], dtype=np.uint64)
+    whole = rows_of(everything)
+    # nothing asked
+    settled(dev.extract_device([]), 0, [])
+    # an early part of rows that cannot be cut: n empty rows; the last part is the whole rows
+    monkeypatch.setenv("GBWT_HIP_SEGMENTS", "0")
+    dev.new_workspace()
+    settled(dev.extract_part_device(everything, 0, 2), len(everything), [[]] * len(everything))
+    settled(dev.extract_part_device(everything, 1, 2), len(everything), whole)
+    monkeypatch.delenv("GBWT_HIP_SEGMENTS")
+    dev.new_workspace()
+    # a direct request that waits for its total (an id without a sequence: the host does not know the walkers), into a workspace without rows
+    settled(dev.extract_device([4, 8, 99]), 3, rows_of([4, 8, 99]))                       # 2 + 64 nodes: the rows hold 66 now
+    # rows of one sample count: sized after the launch -- they fit (34 nodes), then they do not (1 400: nobody walks, the rows grow, a second launch)
+    settled(dev.extract_device([6, 6]), 2, rows_of([6, 6]))
+    settled(dev.extract_device([12, 12]), 2, rows_of([12, 12]))
+    # a part of rows: the two stretches of every row are the row
+    first = settled(dev.extract_part_device(everything, 0, 2), len(everything))
+    second = settled(dev.extract_part_device(everything, 1, 2), len(everything))
+    assert [a + b for a, b in zip(first, second)] == whole
+    # ... and the part is not remembered as the rows: the fill call of gbwt_hip_extract with the same ids walks, and gets whole rows
+    total = C.c_uint64(0)
+    offsets = np.zeros(len(everything) + 1, dtype=np.uint64)
+    nodes = np.zeros(sum(len(r) for r in whole), dtype=np.uint32)
+    G._lib.check(L.gbwt_hip_extract(dev._h, dev._ws, everything.ctypes.data, everything.size, offsets.ctypes.data, nodes.ctypes.data, nodes.size, C.byref(total)))
+    assert total.value == nodes.size and [[int(v) for v in nodes[int(offsets[k]):int(offsets[k + 1])]] for k in range(len(everything))] == whole
+    # the pool-output walk
+    monkeypatch.setenv("GBWT_HIP_DIRECT", "0")
+    dev.new_workspace()
+    settled(dev.extract_device(everything), len(everything), whole)
+    settled(dev.extract_part_device(everything, 0, 2), len(everything), [[]] * len(everything))
+    # a request that fails leaves nothing to copy, whatever the workspace held
+    with pytest.raises(refused):
+        dev.extract_part_device(everything, 2, 2)
+    with pytest.raises(refused):
+        dev.last_offsets(len(everything))
+    with pytest.raises(refused):
+        dev.last_kernel_ms()
+
+
 def _layered_paths(layers, haplotypes, seed):
     """Paths over a layered graph with layers 1 .. 6 nodes wide, some layers skipped by some haplotypes: outdegrees from 1
     to 12, table records followed directly by table records, by unary records and by outdegree-2 records."""
