@@ -1,4 +1,4 @@
-// batch_writer.hpp -- the pipelined whole-file writer shared by gbwt_hip_write_gfa* (gfa.hip) and gbwt_hip_write_sequences (sequences.hip):
+// batch_writer.hpp -- the pipelined whole-file writer shared by gbwt_hip_write_gfa* (capi_lines.hip) and gbwt_hip_write_sequences (sequences.hip):
 // batches of device text, formatted into two device buffers in turn, leave for a file at known positions while the next batch is made.
 #pragma once
 
@@ -18,24 +18,9 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "positional_file.hpp"
 
 namespace gbwt_hip {
-
-// A file written at positions: every producer knows (or is told, in order) where its bytes go, so several threads write at once --
-// one thread moved config 4's 4.5 GB to /dev/shm at 2.4 GB/s, most of it spent in the page cache's per-page work.
-struct PositionalFile {
-    int fd = -1;
-    std::atomic<int> failed{0};
-    ~PositionalFile() { if (fd >= 0) ::close(fd); }
-    bool write_at(const char *data, size_t bytes, uint64_t at) {
-        while (bytes != 0) {
-            const ssize_t w = ::pwrite(fd, data, bytes, static_cast<off_t>(at));
-            if (w <= 0) { failed = 1; return false; }
-            data += w; bytes -= static_cast<size_t>(w); at += static_cast<uint64_t>(w);
-        }
-        return true;
-    }
-};
 
 // The writer's side of a whole-file write: one thread that first puts out what precedes the batches (`preamble`, host work: the H-, S- and
 // L-lines of a GFA file; returns the bytes it wrote from offset 0 on, nothing when unset), then takes finished batches -- device text -- and

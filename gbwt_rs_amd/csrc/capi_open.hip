@@ -1,7 +1,7 @@
 // capi_open.hip -- the C ABI of libgbwt_hip.so (include/gbwt_hip.h), part 1 of 3: opening an index -- the loader's image to the device, the
 // device passes that build descriptors, rank blocks, tables, sequence lengths and samples (upload), what a handle keeps (open_common) -- and
 // the entry points that open, close and describe a handle.  (capi_extract.hip: workspaces + extraction; capi_query.hip: navigation + search;
-// gfa.hip: GFA lines; comm.hip: the gather.)  There is deliberately no CPU implementation of any compute entry point in this library:
+// capi_lines.hip: GFA lines; comm.hip: the gather.)  There is deliberately no CPU implementation of any compute entry point in this library:
 // without a HIP device they fail with GBWT_HIP_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
@@ -672,7 +672,7 @@ gbwt_hip_status open_common(std::unique_ptr<gbwt_hip_index> ix, gbwt_hip_index *
         ix->host.finish();                // the loader's background work, if any: needed from here on
         if (ix->caps & GBWT_HIP_OPEN_GFA) upload_label_lengths(*ix);
     }
-    // the sizes of every path's GFA line, once (gfa.hip): needs the device passes (samples, descriptors) AND the GFA tables (label lengths)
+    // the sizes of every path's GFA line, once (open_lines.hip): needs the device passes (samples, descriptors) AND the GFA tables (label lengths)
     if (ix->caps & GBWT_HIP_OPEN_GFA) {
         mask_label_lengths(*ix);          // (needs both as well: the label lengths from that thread, the record bytes and starts from this one)
         fill_line_cache_at_open(*ix);

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "gfa_host.hpp"
 #include "topology.hpp"
 
 using namespace gbwt_hip;

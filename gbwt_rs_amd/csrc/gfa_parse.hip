@@ -1,4 +1,4 @@
-// gfa_parse.hip -- GFA text to rows of nodes and node labels on the device: the inverse of the line formatter of gfa.hip.
+// gfa_parse.hip -- GFA text to rows of nodes and node labels on the device: the inverse of the line formatter of lines.hip.
 //
 // Count, scan, fill -- no lane loops over a line.  The text is cut into tiles of GFA_TILE_BYTES, one wave per tile, 16 bytes per lane.
 //   structure  k_gfa_count_structure / k_gfa_record_structure: the positions of every '\n' and '\t' (tile counts, a scan, a fill);

@@ -79,11 +79,11 @@ struct gbwt_hip_index {
     // GFA line headers, one table per line mode (0 = P-line named by the contig, 1 = W-line, 2 = P-line with the PanSN name): for every path of
     // the metadata the bytes of its line up to the node tokens -- for a W-line up to and including "<fragment>\t"; the end coordinate
     // (fragment + summed label lengths, path_to_w_line, src/bin/gbunzip.rs:532-540) is only known once the path has been walked and is
-    // appended by the device.  Built once at open (gfa.hip: upload_label_lengths), so that a request formats its lines without the host.
+    // appended by the device.  Built once at open (open_lines.hip: upload_label_lengths), so that a request formats its lines without the host.
     gbwt_hip::DeviceBuffer line_prefix[3], line_prefix_off[3], line_fragment;
     std::vector<char> host_line_prefix[3];
     std::vector<uint64_t> host_line_prefix_off[3];
-    // LINE CACHE (gfa.hip): what the GFA line of a path is made of -- the text bytes of its node tokens, chunk by chunk, and its summed label
+    // LINE CACHE (open_lines.hip fills it, capi_lines.hip reads it): what the GFA line of a path is made of -- the text bytes of its node tokens, chunk by chunk, and its summed label
     // lengths (the W-line's end coordinate) -- is a property of the index, not of the request.  Round 5 let the first request that formats a
     // path leave them here; since round 6 ONE walk at open fills them for every path (fill_line_cache_at_open; kernels.hpp: LineCacheFill), so
     // that no request sizes a line: the node ids cross HBM twice (written by the walk, read by the formatter), never three times.

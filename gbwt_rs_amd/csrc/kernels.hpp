@@ -127,16 +127,16 @@ void launch_chase_counts(const DeviceIndex &ix, const uint4 *d_summaries, uint64
                          uint32_t *d_overflow, hipStream_t stream);
 void launch_chase_samples(const DeviceIndex &ix, const uint4 *d_summaries, uint64_t n_summaries, const uint4 *d_spans, const uint64_t *d_sample_base,
                           uint4 *d_samples, hipStream_t stream);
-// THE LINE CACHE, FILLED AT OPEN (round 6; gfa.hip: fill_line_cache_at_open).  What the GFA line of a path is made of -- the bytes of its
+// THE LINE CACHE, FILLED AT OPEN (round 6; open_lines.hip: fill_line_cache_at_open).  What the GFA line of a path is made of -- the bytes of its
 // W-line node tokens in front of every GFA_LINE_CHUNK positions, their total, and the summed label lengths (the W-line's end coordinate,
 // src/bin/gbunzip.rs:532-540) -- is a property of the index.  Rounds 1-5 found it per request (a sizing pass over the extracted rows: 12 of
 // the 52 ms of config 4's first request) and, round 5, left it in the handle for later requests of the same path.  Now one walker per
 // SEGMENT of every forward sequence (from one sequence sample to the next: the walkers of an extraction, in plain C++) walks its segment
 // once at open, counting token bytes and label lengths instead of emitting nodes; a scan over the segments of each sequence and one
 // thread per chunk put the numbers where the requests read them.  No request sizes a line any more: the first one is like every other.
-constexpr uint32_t GFA_LINE_CHUNK = 4096;      // path positions per formatting chunk (gfa.hip)
+constexpr uint32_t GFA_LINE_CHUNK = 4096;      // path positions per formatting chunk (lines_plan.hpp: LINE_CHUNK)
 struct LineCacheFill {
-    const uint32_t *label_len;     // [n_labels] label length per potential node (gfa.hip: upload_label_lengths)
+    const uint32_t *label_len;     // [n_labels] label length per potential node (open_lines.hip: upload_label_lengths)
     uint64_t n_labels;
     uint64_t paths;                // path p = sequence 2p (support::encode_path)
     uint32_t max_samples;          // the most samples a forward sequence has

@@ -426,7 +426,7 @@ __global__ void __launch_bounds__(256) k_chase_samples(DeviceIndex ix, const uin
 // ---- the line cache filled at open (kernels.hpp: LineCacheFill) -------------------------------------------------------------------------
 
 // What a W-line makes of one node: '>' or '<' and the decimal digits of the node id (path_to_w_line, src/bin/gbunzip.rs:541-546); a P-line
-// token is as long (digits and '+' / '-') plus the comma in front of all but the first (gfa.hip: cache_p_extra).
+// token is as long (digits and '+' / '-') plus the comma in front of all but the first (lines.hip: cache_p_extra).
 __device__ __forceinline__ uint32_t w_token_bytes(uint32_t node) {
     const uint32_t v = node >> 1;
     return 2u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u) + (v >= 1000000000u);

@@ -22,6 +22,8 @@
 
 #include "batch_writer.hpp"
 #include "capi_internal.hpp"
+#include "gfa_host.hpp"
+#include "lines.hpp"
 
 using namespace gbwt_hip;
 

@@ -56,7 +56,7 @@ struct QueryState {
     RequestKey memo;
 };
 
-// GFA path lines (gfa.hip; comm.hip gathers them): line lengths and starts, the text (text2: the second text buffer of a pipelined
+// GFA path lines (capi_lines.hip; comm.hip gathers them): line lengths and starts, the text (text2: the second text buffer of a pipelined
 // whole-file write).  ev: around the formatting of the last request (behind its walk).  memo: path ids, line mode and text slot.
 struct LinesState {
     DeviceBuffer b, c, text, text2, valid;
@@ -151,7 +151,7 @@ struct LocateState {
 };
 
 // Scratch of any family: the temporary storage of scans and sorts, and the per-row words and chunk plan of a pass over a batch of rows
-// (gfa.hip, sequences.hip, tags.hip).  Nothing in it survives a request: a family sizes and fills it before it reads it, and assumes
+// (capi_lines.hip, sequences.hip, tags.hip).  Nothing in it survives a request: a family sizes and fills it before it reads it, and assumes
 // nothing about it once any other entry point has run on the workspace.
 struct ScratchState {
     DeviceBuffer scan_temp, a, chunk_first, chunks, plan;
@@ -183,12 +183,6 @@ struct gbwt_hip_workspace {
 };
 
 namespace gbwt_hip {
-
-// gfa.hip: the chunk plan of the line formatter (chunks of GFA_LINE_CHUNK positions per row) for other passes over a batch of rows, and
-// GBZ::has_node (src/gbz.rs:286-289) on the host image (makes the host's records on first use: HostIndex::ensure_records)
-void launch_chunk_plan(const uint64_t *d_offsets, uint64_t n, uint64_t chunks_cap, uint64_t *d_chunk_counts, uint64_t *d_chunk_first, uint32_t *d_chunk_path, void *d_temp,
-                       size_t temp_bytes, hipStream_t s);
-bool node_exists(const HostIndex &h, uint64_t node_id);
 
 // Device -> pageable host memory over the workspace's copy threads (GBWT_HIP_COPY_THREADS, default 8), each with two pinned staging
 // buffers and a stream of its own (capi_extract.hip)

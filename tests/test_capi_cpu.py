@@ -302,7 +302,7 @@ def test_format_kernel_keeps_eight_waves_per_simd():
     """k_format_chunks hides its load -> scan -> stage -> store chain behind eight workgroups per CU (eight positions per thread = five waves
     per SIMD measured 23 % slower, profiles/r05_format_stream.txt): at most 64 VGPRs, nothing spilled, LDS for eight workgroups."""
     out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull,
-                          os.path.join(_lib.CSRC, "gfa.hip")], capture_output=True, text=True)
+                          os.path.join(_lib.CSRC, "lines.hip")], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stderr.splitlines()
     at = next(i for i, l in enumerate(lines) if "Function Name" in l and "k_format_chunksILj4E" in l)

@@ -607,3 +607,61 @@ print("RCCL_GATHER_OK")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-c", f"ROOT = {root!r}; PORT = '{port}'\n" + code], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0 and "RCCL_GATHER_OK" in out.stdout, out.stderr[-3000:]
+
+
+def test_lines_request_bookkeeping(tmp_path):
+    """What a lines request leaves in its workspace, and what it must not trust there: the fill behind a size query and the host form behind
+    the device form find the text of the request before them; an empty request, a refused one (bad mode, path id out of range), a
+    gbwt_hip_segment_paths call -- which uses the line buffers -- and a change of line mode each stand between two identical requests, and the
+    second one still gives the oracle's text.  Lines of three chunks (9 000 nodes) without a translation, translation.gbz with one."""
+    import ctypes as C
+    s = S.Synth.chain(sites=4500, haplotypes=12, alleles=2, model=S.MOSAIC, founders=8, switch_rate=0.02, seed=17)
+    path = tmp_path / "synth.gbz"
+    s.save(str(path), as_gbz=True)
+    translation = os.path.join(O.GOLDEN, "translation.gbz")
+
+    def request(dev, ids, mode, capacity=None):
+        """gbwt_hip_path_lines itself: (status, total, text) -- a size query without a capacity"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        total = C.c_uint64(0)
+        buf = C.create_string_buffer(max(1, capacity)) if capacity is not None else None
+        st = dev._L.gbwt_hip_path_lines(dev._h, dev._ws, ids.ctypes.data, ids.size, mode, buf, capacity or 0, C.byref(total))
+        return st, total.value, (buf.raw[:total.value] if buf is not None and st == G._lib.OK else None)
+
+    for file, ids in ((str(path), [11, 1, 7]), (translation, None)):
+        dev, oracle = G.GBZ.load(file), O.OracleGBZ(file)
+        ids = list(range(dev.paths())) if ids is None else ids
+        exp = {mode: oracle.path_lines(ids, mode) for mode in (0, 1, 2)}
+        assert all(len(e) > 0 for e in exp.values())
+        # the size query, then the fill
+        st, total, _ = request(dev, ids, 1)
+        assert (st, total) == (G._lib.OK, len(exp[1]))
+        st, filled, text = request(dev, ids, 1, total)
+        assert (st, filled) == (G._lib.OK, total) and text == exp[1]
+        # the device form, then the host form of the same request
+        lines = dev.path_lines_device(ids, 0)
+        assert (lines.total, lines.n) == (len(exp[0]), len(ids)) and lines.d_text and lines.d_line_offsets
+        assert dev.path_lines(ids, 0) == exp[0]
+        # no paths: nothing, and the request before it is still served right
+        assert request(dev, [], 0, 16) == (G._lib.OK, 0, b"")
+        empty = dev.path_lines_device([], 0)
+        assert (empty.total, empty.n) == (0, 0) and not empty.d_text and not empty.d_line_offsets
+        assert dev.path_lines(ids, 0) == exp[0]
+        # refused requests
+        with pytest.raises(G.GbwtHipError) as e:
+            dev.path_lines(ids, 3)
+        assert e.value.status == G._lib.BAD_ARGUMENT
+        assert dev.path_lines(ids, 0) == exp[0]
+        with pytest.raises(G.GbwtHipError) as e:
+            dev.path_lines(ids[:1] + [dev.paths()], 0)
+        assert e.value.status == G._lib.BAD_ARGUMENT
+        assert dev.path_lines(ids, 0) == exp[0]
+        # segment tokens go through the line buffers of the workspace
+        if file == translation:
+            assert dev.path_lines(ids, 1) == exp[1]
+            off, tokens = dev.segment_paths([0, 3])
+            assert [(int(t) >> 1, int(t) & 1) for t in tokens[int(off[0]):int(off[1])]] == oracle.segment_path(0) and len(tokens) == int(off[2]) > 0
+            assert dev.path_lines(ids, 1) == exp[1]
+        # the three line modes in turn on one workspace, then the first again
+        for mode in (0, 1, 2, 0):
+            assert dev.path_lines(ids, mode) == exp[mode], mode
