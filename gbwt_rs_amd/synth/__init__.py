@@ -162,9 +162,9 @@ class Synth:
 
     def attach_gbz(self, segment_starts=(), seed=1, label_lengths=None):
         """Adds path metadata + node labels (+ a node-to-segment translation) so that the index can be saved as a GBZ.  The labels are 1-3
-        seeded bases per node, or -- with `label_lengths` -- label_lengths[q] seeded bases for potential node q (node id q + 1; one entry per
-        node id up to the largest; ids without a record keep empty labels, a node with a record needs at least one base).  The index must be
-        bidirectional and node id 1 must be on a path."""
+        seeded bases per node, or -- with `label_lengths` -- label_lengths[q] seeded bases for potential node q (node id min_node + q; one entry per
+        node id from the smallest on a path to the largest; ids without a record keep empty labels, a node with a record needs at least one
+        base).  The index must be bidirectional; node id 1 must be on a path only where `segment_starts` asks for a translation."""
         starts = np.array(list(segment_starts) or [0], dtype=np.uint64)
         if label_lengths is None:
             rc = self._L.gbwt_synth_attach_gbz(self._h, starts.ctypes.data, len(segment_starts), seed)

@@ -60,16 +60,17 @@ gbwt_synth *gbwt_synth_chain_labeled(uint64_t sites, uint64_t haplotypes, uint32
  * reverse sequence of every path (src/support.rs:310-314).  No metadata, no graph. */
 gbwt_synth *gbwt_synth_from_paths(const uint64_t *offsets, const uint64_t *nodes, uint64_t n_paths, int bidirectional);
 
-/* Turns a bidirectional index with alphabet offset 1 (e.g. one made by gbwt_synth_from_paths over node ids starting
- * at 1) into a GBZ: path metadata as in gbwt_synth_chain, seeded 1-3 base labels for the nodes that have a record,
- * and -- with n_segments > 0 -- a node-to-segment translation: segment k covers node ids segment_starts[k] up to the
+/* Turns a bidirectional index (e.g. one made by gbwt_synth_from_paths) into a GBZ: path metadata as in gbwt_synth_chain,
+ * seeded 1-3 base labels for the nodes that have a record, and -- with n_segments > 0, which needs alphabet offset 1
+ * (node ids starting at 1) -- a node-to-segment translation: segment k covers node ids segment_starts[k] up to the
  * next start and is named "seg<start>" (src/graph.rs:84-89, 186-218).  Returns 0 on success. */
 int gbwt_synth_attach_gbz(gbwt_synth *s, const uint64_t *segment_starts, uint64_t n_segments, uint64_t seed);
 
-/* The same with chosen label lengths: label_lengths[q] = bases of potential node q (node id q + 1), n_lengths = the potential nodes of the
- * index ((alphabet_size - 1) / 2); the bases are seeded ACGT.  Potential nodes without a record keep empty labels whatever their entry says;
- * a node with a record needs at least one base (return 4).  label_lengths == NULL is gbwt_synth_attach_gbz.  The constraints of above stay:
- * a bidirectional index whose smallest node id is 1 (some path visits node id 1). */
+/* The same with chosen label lengths: label_lengths[q] = bases of potential node q (node id min_node + q, min_node = the smallest node id
+ * on a path = (alphabet_offset + 1) / 2), n_lengths = the potential nodes of the index ((alphabet_size - alphabet_offset) / 2); the bases
+ * are seeded ACGT.  Potential nodes without a record keep empty labels whatever their entry says; a node with a record needs at least one
+ * base (return 4).  label_lengths == NULL is gbwt_synth_attach_gbz.  The index must be bidirectional; its smallest node id must be 1 (some
+ * path visits node id 1) only where a translation is asked for (n_segments > 0, return 1): without one the node ids may start anywhere. */
 int gbwt_synth_attach_gbz_labeled(gbwt_synth *s, const uint64_t *segment_starts, uint64_t n_segments, uint64_t seed, const uint64_t *label_lengths,
                                   uint64_t n_lengths);
 

@@ -551,8 +551,8 @@ int gbwt_synth_attach_gbz(gbwt_synth *g, const uint64_t *segment_starts, uint64_
 
 int gbwt_synth_attach_gbz_labeled(gbwt_synth *g, const uint64_t *segment_starts, uint64_t n_segments, uint64_t seed, const uint64_t *label_lengths, uint64_t n_lengths) {
     gbwt_hip::HostIndex &ix = g->index;
-    if (!ix.bidirectional || ix.alphabet_offset != 1) return 1;   // node id v <-> label v - 1, as the translation assumes
-    if (label_lengths && n_lengths != (ix.alphabet_size > 2 ? (ix.alphabet_size - 1) / 2 : 0)) return 3;   // one length per potential node
+    if (!ix.bidirectional || (n_segments > 0 && ix.alphabet_offset != 1)) return 1;   // node id v <-> label v - 1, as the translation assumes
+    if (label_lengths && n_lengths != (ix.alphabet_size > ix.alphabet_offset + 1 ? (ix.alphabet_size - ix.alphabet_offset) / 2 : 0)) return 3;   // one length per potential node, from the first
     const uint64_t n = ix.sequences / 2;
     ix.has_metadata = true;
     ix.metadata_flags = 7;
