@@ -88,6 +88,16 @@ class GraphText(C.Structure):
                 ("segments", C.c_uint64), ("links", C.c_uint64)]
 
 
+class SuffixArray(C.Structure):
+    _fields_ = [("d_sa", C.c_void_p), ("d_bwt", C.c_void_p), ("total", C.c_uint64), ("bwt_runs", C.c_uint64)]
+
+
+class SuffixArrayInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("peak_scratch_bytes", C.c_uint64), ("planned_scratch_bytes", C.c_uint64), ("bwt_runs", C.c_uint64),
+                ("active", C.c_uint64 * 64), ("rounds", C.c_uint32), ("rank_bits", C.c_uint32), ("text_ms", C.c_float), ("pack_ms", C.c_float),
+                ("rank_ms", C.c_float), ("output_ms", C.c_float), ("round_ms", C.c_float * 64)]
+
+
 class ReferencePath(C.Structure):
     _fields_ = [("path_id", C.c_uint64), ("len", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64)]
 
@@ -210,6 +220,12 @@ SIGNATURES = {
     "gbwt_hip_tags": (_int, [_p, _p, _p, _u64, _p, _u64, _p, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_write_tag_array": (_int, [_p, _p, C.c_char_p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_last_tags_ms": (_int, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gbwt_hip_suffix_array_text": (_int, [_int, _p, _u64, _int, _p, _p, C.POINTER(_u64)]),
+    "gbwt_hip_suffix_array_text_device": (_int, [_int, _p, _u64, _int, _p, _p, _p, C.POINTER(_u64)]),
+    "gbwt_hip_path_suffix_array_device": (_int, [_p, _p, _p, _u64, _int, C.POINTER(SuffixArray)]),
+    "gbwt_hip_path_suffix_array": (_int, [_p, _p, _p, _u64, _int, _p, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gbwt_hip_write_suffix_array": (_int, [_p, _p, C.c_char_p, C.POINTER(_u64)]),
+    "gbwt_hip_last_suffix_array_info": (_int, [_p, C.POINTER(SuffixArrayInfo)]),
     "gbwt_hip_components_device": (_int, [_p, C.POINTER(Components)]),
     "gbwt_hip_weakly_connected_components": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_path_components": (_int, [_p, _p, _u64, _p]),

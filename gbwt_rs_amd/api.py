@@ -15,6 +15,8 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBWT.weakly_connected_components()   GBZ::weakly_connected_components   src/gbz.rs:570-598
   GBZ.select_paths(contig)         gbz-extract's select_paths, src/bin/gbz-extract.rs:196-264
   GBZ.tag_array(ids, sa)           gbz-extract's extract_tag_array, src/bin/gbz-extract.rs:346-371, 408-482 (tags of a suffix array)
+  GBZ.suffix_array(ids) / suffix_array_text(data)   the `base`.sa and `base`.bwt that tag-array mode reads (src/bin/gbz-extract.rs:321-344, 373-406)
+                                   and nothing in the reference writes: suffix array and BWT of a text, built on the device
   GBZ.reference_positions(interval)   GBZ::reference_positions   src/gbz.rs:600-657   (reference_sample_names / reference_paths: 146-196)
   GBWT.node_iter / successors / predecessors        GBZ::node_iter, successors, predecessors   src/gbz.rs:312-353 (EdgeIter 819-892)
   GBZ.node_to_segment / segment_iter / segment_successors / segment_predecessors   src/gbz.rs:370-440 (SegmentIter, LinkIter 896-1016)
@@ -33,7 +35,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BdState, BuildInfo, Components, EdgeRows, GbwtHipError, GfaInfo, GraphText, Lines, Located, LocateInfo, Memory, OpenTimes, Paths, Pos, State, Stats, check
+from ._lib import BdState, BuildInfo, Components, EdgeRows, GbwtHipError, GfaInfo, GraphText, Lines, Located, LocateInfo, Memory, OpenTimes, Paths, Pos, State, Stats, SuffixArray, SuffixArrayInfo, check
 
 FORWARD, REVERSE = 0, 1  # support::Orientation, src/support.rs:30-47
 PATHS_DEFAULT, PATHS_PAN_SN, PATHS_REF_ONLY = 0, 1, 2  # gbunzip's PathMode, src/bin/gbunzip.rs:63-76
@@ -96,6 +98,34 @@ def _ref_or_null(opts):  # an options struct as the library takes it: NULL = the
 
 def _ptr(a):
     return a.ctypes.data if a is not None and a.size else None
+
+
+def _suffix_info(ws):  # gbwt_hip_last_suffix_array_info as a dict: the lists cut to the rounds that ran
+    info = SuffixArrayInfo()
+    check(_lib.lib().gbwt_hip_last_suffix_array_info(ws, C.byref(info)))
+    d = _as_dict(info)
+    kept = min(info.rounds + 1, 64)
+    d["active"], d["round_ms"] = list(info.active[:kept]), list(info.round_ms[:kept])
+    return d
+
+
+def suffix_array_text(data, sentinel=0, device=0, return_bwt=False):
+    """The suffix array of any bytes (gbwt_hip_suffix_array_text; no index): the permutation that orders the suffixes as unsigned byte strings
+    compared to the end of the text, a proper prefix first, as a numpy uint64 array.  return_bwt: (sa, bwt uint8, runs of the bwt), with the
+    byte `sentinel` in front of suffix 0."""
+    text = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    if text.ndim != 1:
+        raise ValueError("data must be one-dimensional")
+    sa = np.zeros(text.size, dtype=np.uint64)
+    bwt = np.zeros(text.size, dtype=np.uint8) if return_bwt else None
+    runs = C.c_uint64(0)
+    check(_lib.lib().gbwt_hip_suffix_array_text(device, _ptr(text), text.size, int(sentinel), _ptr(sa), _ptr(bwt), C.byref(runs)))
+    return (sa, bwt, runs.value) if return_bwt else sa
+
+
+def last_suffix_array_info():
+    """The last suffix_array_text call of the process (gbwt_hip_last_suffix_array_info without a workspace): a dict."""
+    return _suffix_info(None)
 
 
 class GBWT:
@@ -1000,6 +1030,40 @@ class GBZ(GBWT):
         walk, plan, gather = C.c_float(0), C.c_float(0), C.c_float(0)
         check(self._L.gbwt_hip_last_tags_ms(self._ws, C.byref(walk), C.byref(plan), C.byref(gather)))
         return walk.value, plan.value, gather.value
+
+    def suffix_array(self, path_ids, endmarker=0, return_bwt=False):
+        """The suffix array of the text path_sequences(path_ids, FORWARD, endmarker) returns (gbwt_hip_path_suffix_array), built on the device
+        from the bases there: a numpy uint64 array, or with return_bwt (sa, bwt uint8, runs of the bwt); the byte in front of suffix 0 is the
+        endmarker (0 without one)."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        em = self._endmarker(endmarker)
+        total, runs = C.c_uint64(0), C.c_uint64(0)
+        check(self._L.gbwt_hip_path_suffix_array(self._h, self._ws, _ptr(ids), ids.size, em, None, None, 0, C.byref(total), C.byref(runs)))
+        sa = np.zeros(total.value, dtype=np.uint64)
+        bwt = np.zeros(total.value, dtype=np.uint8) if return_bwt else None
+        if total.value:
+            check(self._L.gbwt_hip_path_suffix_array(self._h, self._ws, _ptr(ids), ids.size, em, _ptr(sa), _ptr(bwt), sa.size, C.byref(total), C.byref(runs)))
+        return (sa, bwt, runs.value) if return_bwt else sa
+
+    def suffix_array_device(self, path_ids, endmarker=0):
+        """The same left in HBM: a SuffixArray struct (d_sa u64[total], d_bwt u8[total], total, bwt_runs), valid until the next suffix array
+        request on this workspace; d_sa is an argument for tags_device as it is."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        out = SuffixArray()
+        check(self._L.gbwt_hip_path_suffix_array_device(self._h, self._ws, _ptr(ids), ids.size, self._endmarker(endmarker), C.byref(out)))
+        return out
+
+    def write_suffix_array(self, base):
+        """What stands between `gbz-extract -o base` and `gbz-extract -m tag-array -o base`: reads `base`.names (and the endmarker at the end
+        of `base`), writes `base`.sa and `base`.bwt as write_tag_array(base) and the reference read them; returns the runs of the BWT."""
+        runs = C.c_uint64(0)
+        check(self._L.gbwt_hip_write_suffix_array(self._h, self._ws, os.fsencode(base), C.byref(runs)))
+        return runs.value
+
+    def last_suffix_array_info(self):
+        """The last suffix array built on this workspace (gbwt_hip_last_suffix_array_info): a dict -- n, rounds, active (the active set behind
+        the first keys and behind every round), round_ms, peak_scratch_bytes, planned_scratch_bytes, text_ms, pack_ms, rank_ms, output_ms."""
+        return _suffix_info(self._ws)
 
     # ---- the graph: segments, links, GFA lines -----------------------------------------------------
     def has_translation(self):

@@ -29,6 +29,14 @@ struct HostCopier {
     bool ensure(int device, unsigned threads);
 };
 
+// What a suffix array request needs beside its scratch (suffix_array.hip): events -- [0] .. [7] the text (the caller's), [1] .. [2] the pack, [2] .. [3]
+// the ranking, [3] .. [4] the output, [5] .. [6] one round -- and the pinned words the size of the active set and the runs are read through
+struct SaContext {
+    EventSet<8> ev{OnFirstUse{}};
+    PinnedWords words;
+    void ensure() { ev.ensure(); words.ensure(); }
+};
+
 // Extraction (capi_extract.hip; comm.hip reads the rows).  The rows of the last request -- ids, offsets, nodes -- are what the lines, bases,
 // tags and positions are made from: those families read seq_ids, ev, timed and pinned_words here.  ev[3] .. ev[2]: everything the
 // extraction put on the stream, ev[0] .. ev[1]: its walk; made with the workspace.  memo: the ids of the rows (whole rows only).
@@ -96,6 +104,20 @@ struct TagsState {
     std::vector<uint64_t> rows;
     uint64_t positions = 0, text_len = 0;
     float walk_ms = 0, plan_ms = 0, gather_ms = 0;
+};
+
+// Suffix array and BWT of the text of paths (suffix_array.hip, capi_suffix_array.hip).  The results of the last request: sa holds 16 bytes of
+// lead -- the entry `total` of a .sa file in its second word -- and then the u64 suffix array; bwt 16 bytes of lead -- the byte T[total - 1] of
+// a .bwt file in its last -- and then the BWT: a file is one stretch of either buffer.  The text is the bases family's (ws->bases.text).
+// The scratch of the ranking is the builder's own and gone when a request returns.  ev: see SaContext.  memo: path ids and endmarker.
+struct SuffixState {
+    DeviceBuffer sa, bwt;
+    uint64_t device_bytes() const { return bytes_of({&sa, &bwt}); }
+    SaContext ctx;
+    bool built = false;
+    uint64_t total = 0;
+    gbwt_hip_suffix_array_info info{};
+    RequestKey memo;
 };
 
 // Reference positions (refpos.hip, capi_refpos.hip).  Scratch of the last request, per position (node of its rows): off (u64 bases in front
@@ -168,6 +190,7 @@ struct gbwt_hip_workspace {
     gbwt_hip::LinesState lines;
     gbwt_hip::BasesState bases;
     gbwt_hip::TagsState tags;
+    gbwt_hip::SuffixState suffix;
     gbwt_hip::RefposState refpos;
     gbwt_hip::EdgesState edges;
     gbwt_hip::GraphTextState graph_text;
@@ -176,7 +199,7 @@ struct gbwt_hip_workspace {
     gbwt_hip::HostCopier copier;     // pinned staging of the large device-to-host copies
     gbwt_hip::Stream stream{gbwt_hip::OnFirstUse{}};   // made by gbwt_hip_workspace_create, on the handle's device; the last member: it goes first, before the buffers its work used
     uint64_t device_bytes() const {
-        return extract.device_bytes() + query.device_bytes() + lines.device_bytes() + bases.device_bytes() + tags.device_bytes() + refpos.device_bytes() + edges.device_bytes() +
+        return extract.device_bytes() + query.device_bytes() + lines.device_bytes() + bases.device_bytes() + tags.device_bytes() + suffix.device_bytes() + refpos.device_bytes() + edges.device_bytes() +
                graph_text.device_bytes() + locate.device_bytes() + scratch.device_bytes();
     }
     uint64_t text_bytes() const { return lines.text_bytes() + bases.text_bytes() + graph_text.text_bytes(); }

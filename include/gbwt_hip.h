@@ -389,6 +389,61 @@ gbwt_hip_status gbwt_hip_write_tag_array(const gbwt_hip_index *index, gbwt_hip_w
  * (0 for a size query). */
 gbwt_hip_status gbwt_hip_last_tags_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *plan_ms, float *gather_ms);
 
+/* ---- suffix array and BWT of a text --------------------------------------------------------------------------------------------------
+ * What stands between gbz-extract's two modes: `sequences` writes a text, `tag-array` reads `base`.sa, a suffix array of it, and counts the
+ * runs of `base`.bwt (src/bin/gbz-extract.rs:321-344, 373-406).  For a text T[0, n) of bytes, SA is the permutation of 0 .. n - 1 that
+ * orders the suffixes T[i, n) as unsigned byte strings compared to the end of the text, straight through any endmarkers; a suffix that is
+ * a proper prefix of another is the smaller one (a generic suffix sorter's order for T followed by an implicit smallest sentinel).  All
+ * suffixes differ in length: the order is total, SA is unique, there is no tie-break.  BWT[i] = T[SA[i] - 1], and the sentinel byte of the
+ * call where SA[i] == 0; *bwt_runs = the runs of BWT[0, n) as count_bwt_runs counts them (the first entry starts a run; 0 for n == 0).
+ * Built on the device by prefix doubling over radix sorts that re-sort only the suffixes still tied.  Ranks and positions
+ * are 32 bits inside: n > 2^32 - 2 is GBWT_HIP_UNSUPPORTED before any work; scratch (49 bytes per position and the temporary storage of the
+ * sorts) beyond the free device memory is GBWT_HIP_CAPACITY with the bytes needed.  All scratch is freed before a call returns.
+ *
+ * gbwt_hip_suffix_array_text: any n bytes in host memory, no index: out_sa[n], out_bwt[n] (may be NULL), *bwt_runs (may be NULL).
+ * sentinel: a byte value 0 .. 255. */
+gbwt_hip_status gbwt_hip_suffix_array_text(int device, const void *text, uint64_t n, int sentinel, uint64_t *out_sa, uint8_t *out_bwt, uint64_t *bwt_runs);
+/* The same over the caller's device buffers: d_text[n] is only read, d_sa[n] and d_bwt[n] (may be NULL) are written, nothing outside them.
+ * The work is ordered on `stream` (a hipStream_t; NULL: the default stream) and done when the call returns. */
+gbwt_hip_status gbwt_hip_suffix_array_text_device(int device, const void *d_text, uint64_t n, int sentinel, uint64_t *d_sa, uint8_t *d_bwt, void *stream, uint64_t *bwt_runs);
+
+/* The suffix array of the text of paths (GBZ handles opened with GBWT_HIP_OPEN_EXTRACT): the text is that of
+ * gbwt_hip_path_sequences_device(path_ids, n, forward, endmarker), made by that family on `ws`; endmarker -1 (none) .. 255, the guards of the
+ * bases calls.  The sentinel of the BWT is the endmarker (0 without one).  The results stay on the workspace until the next such request:
+ * d_sa[total] is directly a valid suffix array for gbwt_hip_tags_device on the same workspace. */
+typedef struct {
+    uint64_t *d_sa;      /* [total] */
+    uint8_t *d_bwt;      /* [total] */
+    uint64_t total;      /* the length of the text */
+    uint64_t bwt_runs;
+} gbwt_hip_suffix_array;
+gbwt_hip_status gbwt_hip_path_suffix_array_device(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int endmarker,
+                                                  gbwt_hip_suffix_array *out);
+/* The same copied out: *total always receives the text length; out_sa == NULL and out_bwt == NULL is the size query, and the call that
+ * repeats its request with buffers (capacity: entries either holds) only copies -- nothing is built twice. */
+gbwt_hip_status gbwt_hip_path_suffix_array(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int endmarker, uint64_t *out_sa,
+                                           uint8_t *out_bwt, uint64_t capacity, uint64_t *total, uint64_t *bwt_runs);
+/* The files between the two modes: reads `base`.names as gbwt_hip_write_tag_array does (path ids, and the bases of every path against
+ * the walk), takes the endmarker from the last byte of `base` where that file exists -- its size must be the text's -- and 0 otherwise, and
+ * writes `base`.sa (little-endian u64: the entry `total`, then SA) and `base`.bwt (the byte T[total - 1], then BWT): the entry and the byte
+ * of the implicit sentinel in front, which gbwt_hip_write_tag_array(base, sa_skip = 1) and `gbz-extract -m tag-array -v` skip.  A `base`.sa
+ * and a `base`.bwt that exist are removed once the arguments are through: neither file stays behind a failure, its own or an earlier call's. */
+gbwt_hip_status gbwt_hip_write_suffix_array(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const char *base_path, uint64_t *bwt_runs);
+/* The last suffix array built on `ws`, or with ws == NULL by a gbwt_hip_suffix_array_text* call of this process.  A round sorts the
+ * active set -- the suffixes whose rank is still shared -- once: active[0] is its size behind the sort of the first keys (7 bytes),
+ * active[k] behind round k, which compares 7 * 2^k bytes; rounds = the k that left it empty (entries past 63 are not kept).  round_ms[k]:
+ * device time of that sort and its renumbering (round_ms[0]: the first keys'), by HIP events like text_ms (the bases of the paths, or
+ * the upload of a host text), pack_ms, rank_ms (all rounds) and output_ms.  planned_scratch_bytes: what the plan promised for
+ * peak_scratch_bytes, the most the ranking held at once. */
+typedef struct {
+    uint64_t n, peak_scratch_bytes, planned_scratch_bytes, bwt_runs;
+    uint64_t active[64];
+    uint32_t rounds, rank_bits;
+    float text_ms, pack_ms, rank_ms, output_ms;
+    float round_ms[64];
+} gbwt_hip_suffix_array_info;
+gbwt_hip_status gbwt_hip_last_suffix_array_info(const gbwt_hip_workspace *ws, gbwt_hip_suffix_array_info *out);
+
 /* ---- graph topology: weakly connected components, contig path selection -------------------------------------------------------------
  * GBZ::weakly_connected_components (src/gbz.rs:570-598; known answer src/gbz/tests.rs:503-518): the node ids of the graph that the GBWT
  * records describe, partitioned by "joined through an edge, whatever the orientations" (the successors and predecessors of both

@@ -523,6 +523,22 @@ public:
         check(gbwt_hip_write_tag_array(index_.get(), ws_.get(), base.c_str(), sa_skip, &runs));
         return runs;
     }
+    // The suffix array of the text of these paths (gbwt_hip_path_suffix_array; the bases of every path and one endmarker each, suffixes
+    // compared as unsigned byte strings to the end of the text); `bwt` and `bwt_runs` receive the BWT and its runs
+    std::vector<uint64_t> suffix_array(const std::vector<uint64_t> &path_ids, int endmarker = 0, std::vector<uint8_t> *bwt = nullptr, uint64_t *bwt_runs = nullptr) const {
+        uint64_t total = 0;
+        check(gbwt_hip_path_suffix_array(index_.get(), ws_.get(), path_ids.data(), path_ids.size(), endmarker, nullptr, nullptr, 0, &total, bwt_runs));
+        std::vector<uint64_t> sa(total);
+        if (bwt) bwt->assign(total, 0);
+        if (total) check(gbwt_hip_path_suffix_array(index_.get(), ws_.get(), path_ids.data(), path_ids.size(), endmarker, sa.data(), bwt ? bwt->data() : nullptr, total, &total, bwt_runs));
+        return sa;
+    }
+    // `base`.names (+ `base`) -> `base`.sa and `base`.bwt, what write_tag_array(base) reads; returns the runs of the BWT
+    uint64_t write_suffix_array(const std::string &base) const {
+        uint64_t runs = 0;
+        check(gbwt_hip_write_suffix_array(index_.get(), ws_.get(), base.c_str(), &runs));
+        return runs;
+    }
     // select_paths of gbz-extract (src/bin/gbz-extract.rs:196-264): every path (nullopt), or the paths of the components in which a path
     // with that contig name starts; throws Error with the reference's messages
     std::vector<size_t> select_paths(const std::optional<std::string> &contig = std::nullopt) const {
@@ -599,6 +615,15 @@ private:
 // merge(a, b): GBWT::merge for two GBWT, GBZ::merge for two GBZ
 template <class Index>
 inline Index merge(const Index &a, const Index &b, uint32_t algorithm = GBWT_HIP_MERGE_AUTO, uint32_t flags = GBWT_HIP_OPEN_ALL) { return Index::merge(a, b, algorithm, flags); }
+
+// The suffix array of any bytes, built on `device` (gbwt_hip_suffix_array_text; no index): `bwt` and `bwt_runs` receive the BWT -- with
+// `sentinel` in front of suffix 0 -- and its runs
+inline std::vector<uint64_t> suffix_array_text(const std::string &text, int sentinel = 0, int device = 0, std::vector<uint8_t> *bwt = nullptr, uint64_t *bwt_runs = nullptr) {
+    std::vector<uint64_t> sa(text.size());
+    if (bwt) bwt->assign(text.size(), 0);
+    check(gbwt_hip_suffix_array_text(device, text.data(), text.size(), sentinel, sa.data(), bwt ? bwt->data() : nullptr, bwt_runs));
+    return sa;
+}
 
 // The ordered gather of a sharded extraction (one process per GPU; the reference's writer mutex, src/bin/gbunzip.rs:421-434).  Rank 0 makes
 // the id (Comm::unique_id), every rank constructs a Comm from it (collective), and after gbwt_hip_extract_device / _path_lines_device on
