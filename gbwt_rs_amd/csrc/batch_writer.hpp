@@ -1,5 +1,6 @@
-// batch_writer.hpp -- the pipelined whole-file writer shared by gbwt_hip_write_gfa* (capi_lines.hip) and gbwt_hip_write_sequences (sequences.hip):
-// batches of device text, formatted into two device buffers in turn, leave for a file at known positions while the next batch is made.
+// batch_writer.hpp -- the pipelined whole-file writer shared by gbwt_hip_write_gfa* (capi_lines.hip), gbwt_hip_write_sequences
+// (capi_sequences.hip), gbwt_hip_write_tag_array (capi_tags.hip) and gbwt_hip_write_suffix_array (capi_suffix_array.hip): batches of device
+// text, formatted into two device buffers in turn, leave for a file at known positions while the next batch is made.
 #pragma once
 
 #include <fcntl.h>

@@ -1,6 +1,6 @@
 // capi_suffix_array.hip -- the C ABI of the suffix array family (include/gbwt_hip.h, "suffix array and BWT of a text"): a text in host or
 // device memory without an index, the text of paths on a workspace, and the files between gbz-extract's two modes.  The builder is
-// suffix_array.hip; the text of paths is the bases family's (sequences.hip).
+// suffix_array.hip; the text of paths is the bases family's (capi_sequences.hip); what the files hold is extract_files.hpp.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -13,6 +13,7 @@
 
 #include "batch_writer.hpp"
 #include "capi_internal.hpp"
+#include "extract_files.hpp"
 #include "sa_plan.hpp"
 #include "suffix_array.hpp"
 
@@ -44,7 +45,7 @@ gbwt_hip_status check_text_call(const void *text, uint64_t n, int sentinel, cons
 gbwt_hip_status suffix_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int endmarker) {
     if (!ix || !ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
     if (n && !path_ids) return fail(GBWT_HIP_BAD_ARGUMENT, "null path_ids");
-    if (endmarker < -1 || endmarker > 255) return fail(GBWT_HIP_BAD_ARGUMENT, "endmarker must be -1 (none) or a byte value 0..255");
+    if (!endmarker_valid(endmarker)) return fail(GBWT_HIP_BAD_ARGUMENT, ENDMARKER_RULE);
     SuffixState &f = ws->suffix;
     if (f.memo.matches({{path_ids, n * sizeof(uint64_t)}}, {endmarker})) return GBWT_HIP_OK;
     f.memo.drop();
@@ -78,41 +79,6 @@ gbwt_hip_status suffix_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws,
     } catch (const HipError &e) {
         return status_of(e, "the suffix array");
     }
-}
-
-bool parse_number(const std::string &field, uint64_t &out) {
-    if (field.empty() || field.size() > 19) return false;
-    out = 0;
-    for (char c : field) { if (c < '0' || c > '9') return false; out = 10 * out + static_cast<uint64_t>(c - '0'); }
-    return true;
-}
-
-// `base`.names as gbwt_hip_write_tag_array reads it (read_names, src/bin/gbz-extract.rs:296-318): first tab field = path id, last = bases.
-// (The same reader stands in tags.hip; the two belong in one shared header -- DESIGN.md 4n, "Next".)
-gbwt_hip_status read_names(const std::string &names_path, std::vector<uint64_t> &ids, std::vector<uint64_t> &lens) {
-    FILE *f = std::fopen(names_path.c_str(), "rb");
-    if (!f) return fail(GBWT_HIP_IO_ERROR, "cannot open " + names_path);
-    std::string text;
-    char buffer[1 << 16];
-    size_t got;
-    while ((got = std::fread(buffer, 1, sizeof(buffer), f)) != 0) text.append(buffer, got);
-    const bool broken = std::ferror(f) != 0;
-    std::fclose(f);
-    if (broken) return fail(GBWT_HIP_IO_ERROR, "cannot read " + names_path);
-    for (size_t at = 0; at < text.size();) {
-        size_t nl = text.find('\n', at);
-        if (nl == std::string::npos) nl = text.size();
-        std::string line = text.substr(at, nl - at);
-        if (!line.empty() && line.back() == '\r') line.pop_back();
-        at = nl + 1;
-        const size_t head = line.find('\t'), tail = line.rfind('\t');
-        if (head == std::string::npos) return fail(GBWT_HIP_INVALID_DATA, "Name line missing last field");
-        uint64_t id = 0, len = 0;
-        if (!parse_number(line.substr(0, head), id) || !parse_number(line.substr(tail + 1), len)) return fail(GBWT_HIP_INVALID_DATA, "invalid digit found in string: " + line);
-        ids.push_back(id); lens.push_back(len);
-    }
-    if (ids.empty()) return fail(GBWT_HIP_INVALID_DATA, "No path names found");
-    return GBWT_HIP_OK;
 }
 
 // One stretch of device memory into a new file through the whole-file writer
@@ -241,14 +207,11 @@ gbwt_hip_status gbwt_hip_write_suffix_array(const gbwt_hip_index *ix, gbwt_hip_w
         (void)::unlink(bwt_path.c_str());
         // 1. the names: path id, bases; the text file, where there is one: its size, and the endmarker at its end
         std::vector<uint64_t> ids, lens;
-        gbwt_hip_status st = read_names(base + ".names", ids, lens);
-        if (st != GBWT_HIP_OK) return st;
+        FileCheck names = read_names(base + ".names", ids, lens);
+        if (names.ok()) names = check_paths_exist(ix->host.sequences, ids, lens);
+        if (!names.ok()) return fail(names.status, names.message);
         uint64_t expected_len = 0;
-        for (size_t k = 0; k < ids.size(); k++) {            // GBZ::path gives nothing for such an id: extract_path is the endmarker alone
-            if (ids[k] >= (~uint64_t(0)) / 2 || 2 * ids[k] >= ix->host.sequences)
-                return fail(GBWT_HIP_INVALID_DATA, "Invalid length for path " + std::to_string(ids[k]) + ": expected " + std::to_string(lens[k]) + ", got 0 (no such path)");
-            expected_len += lens[k] + 1;
-        }
+        for (uint64_t len : lens) expected_len += len + 1;
         int endmarker = 0;
         {
             PositionalFile text_file;
@@ -265,16 +228,13 @@ gbwt_hip_status gbwt_hip_write_suffix_array(const gbwt_hip_index *ix, gbwt_hip_w
         }
         // 2. the text, and the walked bases of every path against its line
         gbwt_hip_lines text{};
-        st = gbwt_hip_path_sequences_device(ix, ws, ids.data(), ids.size(), 0, endmarker, &text);
+        gbwt_hip_status st = gbwt_hip_path_sequences_device(ix, ws, ids.data(), ids.size(), 0, endmarker, &text);
         if (st != GBWT_HIP_OK) return st;
         std::vector<uint64_t> rows(ids.size() + 1);
         HIP_CHECK(hipSetDevice(ix->device));
         HIP_CHECK(hipMemcpy(rows.data(), text.d_line_offsets, rows.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < ids.size(); k++) {
-            const uint64_t walked = rows[k + 1] - rows[k] - 1;
-            if (walked != lens[k])
-                return fail(GBWT_HIP_INVALID_DATA, "Invalid length for path " + std::to_string(ids[k]) + ": expected " + std::to_string(lens[k]) + ", got " + std::to_string(walked));
-        }
+        const FileCheck walked = check_walked_lengths(ids, lens, rows.data());
+        if (!walked.ok()) return fail(walked.status, walked.message);
         // 3. the suffix array (the text of step 2 is still the bases family's), and the two files
         st = suffix_compute(ix, ws, ids.data(), ids.size(), endmarker);
         if (st != GBWT_HIP_OK) return st;

@@ -1,4 +1,4 @@
-// labels.hpp -- the node labels of a handle as the kernels see them (sequences.hip, tags.hip, capi_topology.hip).
+// labels.hpp -- the node labels of a handle as the kernels see them (sequences.hip, tags.hip, capi_topology.hip, capi_refpos.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,8 +20,9 @@ __device__ __forceinline__ void label_of(const Labels &L, uint32_t node, uint64_
     lo = L.off[s]; hi = L.off[s + 1];
 }
 
-// sequences.hip: the labels of a handle in HBM (made by the first request that needs them), and the test every entry point for bases and
-// tags starts with (InvalidData for a bare GBWT or a handle without GBWT_HIP_OPEN_EXTRACT)
+// sequences.hip: the labels of a handle in HBM (made by the first request that needs them), and the test every entry point for bases
+// (capi_sequences.hip), tags (capi_tags.hip) and the suffix array of paths (capi_suffix_array.hip) starts with (InvalidData for a bare GBWT
+// or a handle without GBWT_HIP_OPEN_EXTRACT)
 Labels labels_of(const gbwt_hip_index *ix);
 void ensure_labels(const gbwt_hip_index *ix);
 void require_bases_capable(const gbwt_hip_index *ix);

@@ -78,7 +78,7 @@ struct LinesState {
     int slot = 0;
 };
 
-// Bases of paths (sequences.hip): text and row offsets of the last gbwt_hip_path_sequences* request (text2: the second text buffer of a
+// Bases of paths (sequences.hip, capi_sequences.hip): text and row offsets of the last gbwt_hip_path_sequences* request (text2: the second text buffer of a
 // pipelined whole-file write).  ev[0] .. ev[1]: its sizing, ev[1] .. ev[2]: its bases kernel.  memo: path ids, reverse, endmarker, slot.
 struct BasesState {
     DeviceBuffer text, text2, offsets;
@@ -90,7 +90,7 @@ struct BasesState {
     RequestKey memo;
 };
 
-// Tags of a suffix array (tags.hip).  The PLAN of the last list of path ids (plan_key): for every position of the text's walk -- the nodes of
+// Tags of a suffix array (tags.hip, capi_tags.hip).  The PLAN of the last list of path ids (plan_key): for every position of the text's walk -- the nodes of
 // the rows and one endmarker position behind each -- its node (node, u32) and its text offset (off, u64, one more entry = the text length),
 // and the sampled top level (top: the position that holds text offset h << TAG_SHIFT; u32, u64 from 2^32 positions).  rows: the text offset
 // of every row (+ the text length) on the host.  state: run count, last tags and the out-of-range flag of a request; sa* / out*: the
@@ -173,7 +173,7 @@ struct LocateState {
 };
 
 // Scratch of any family: the temporary storage of scans and sorts, and the per-row words and chunk plan of a pass over a batch of rows
-// (capi_lines.hip, sequences.hip, tags.hip).  Nothing in it survives a request: a family sizes and fills it before it reads it, and assumes
+// (capi_lines.hip, capi_sequences.hip, capi_tags.hip).  Nothing in it survives a request: a family sizes and fills it before it reads it, and assumes
 // nothing about it once any other entry point has run on the workspace.
 struct ScratchState {
     DeviceBuffer scan_temp, a, chunk_first, chunks, plan;

@@ -195,6 +195,44 @@ def test_files_chain_sequences_suffix_array_tags(tmp_path):
     failing(_lib.IO_ERROR, "cannot open")
 
 
+def test_one_reader_of_the_names_for_both_modes(tmp_path):
+    """`base`.names is read by one piece of code (csrc/extract_files.hpp): the suffix array mode and the tag-array mode refuse a malformed
+    or mismatching file with the same status and the same words -- before either looks for `base`.sa -- and agree on a reordered one."""
+    path = os.path.join(O.GOLDEN, "example.gbz")
+    dev, oracle = G.GBZ.load(path), O.OracleGBZ(path)
+    n = dev.paths()
+    base = str(tmp_path / "example")
+    dev.write_sequences(base)
+    names = open(base + ".names").read()
+    os.remove(base)                                                           # (so that the lengths are checked against the walk, not the file)
+    lines = names.splitlines()
+    f = lines[2].split("\t")
+    wrong = "\n".join(lines[:2] + ["\t".join(f[:5] + [str(int(f[5]) + 1)])] + lines[3:]) + "\n"
+    cases = [("", "No path names found"),
+             (names.replace("\t", " "), "Name line missing last field"),
+             (f"{n}\tx\ty\t0\t0\t5\n", f"Invalid length for path {n}: expected 5, got 0 (no such path)"),
+             (wrong, f"Invalid length for path 2: expected {int(f[5]) + 1}, got {int(f[5])}")]
+    for text, message in cases:
+        open(base + ".names", "w").write(text)
+        seen = []
+        for call in (dev.write_tag_array, dev.write_suffix_array):
+            with pytest.raises(G.GbwtHipError) as e:
+                call(base)
+            seen.append((e.value.status, dev._L.gbwt_hip_last_error().decode()))
+        assert seen[0] == seen[1] and seen[0] == (_lib.INVALID_DATA, message), seen
+        assert not any(os.path.exists(base + suffix) for suffix in (".sa", ".bwt", ".tags"))
+    # two fields, another order, no final newline: the suffix array one mode writes is the one the other reads to its end
+    open(base + ".names", "w").write("5\t4\n0\tanything\t5")
+    _, data = dev.path_sequences([5, 0], endmarker=0)
+    want = brute(bytes(data))
+    dev.write_suffix_array(base)
+    assert open(base + ".sa", "rb").read() == np.concatenate([[len(data)], want]).astype("<u8").tobytes()
+    part, _ = T.oracle_text(oracle, [5, 0])
+    want_tags = T.gather(part, want)
+    assert dev.write_tag_array(base) == T.runs(want_tags)
+    assert open(base + ".tags", "rb").read() == want_tags.astype("<u8").tobytes()
+
+
 def test_workspace_memo_memory_and_guards():
     path = os.path.join(O.GOLDEN, "example.gbz")
     dev = G.GBZ.load(path)

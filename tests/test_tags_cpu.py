@@ -10,6 +10,7 @@ import numpy as np
 from gbwt_rs_amd import _lib
 import seq_expect as E
 import tags_expect as T
+from test_merge_cpu import sanitized_program
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NEW_SYMBOLS = ["gbwt_hip_tags_device", "gbwt_hip_tags", "gbwt_hip_write_tag_array", "gbwt_hip_last_tags_ms"]
@@ -49,6 +50,17 @@ def test_tag_kernels_compile_without_scratch():
     gather = [name for name in seen if "6k_tagsI" in name]
     assert len(gather) == 2, seen               # 32-bit and 64-bit hints
     assert all(seen[name] <= 64 for name in gather), seen     # eight waves per SIMD
+
+
+def test_extract_files_under_sanitizers(tmp_path):
+    """tests/cpp/extract_files.cpp: the files between gbz-extract's three modes (csrc/extract_files.hpp) on the host.  Every case prints
+    "ok <case>"; sanitized_program refuses a FAIL line, a sanitizer report (exit status) and a missing "done"."""
+    _, lines = sanitized_program(tmp_path, "extract_files")
+    assert lines == ["ok " + case for case in (
+        "writer_line_format", "writer_line_parses_back_names_with_spaces", "two_fields_no_final_newline", "crlf_stripped", "empty_text", "line_without_tab",
+        "empty_line_in_the_middle", "newline_alone", "non_digit_in_id", "non_digit_in_bases", "empty_id_field", "twenty_digits", "nineteen_nines", "file_that_does_not_exist",
+        "path_exists_half_of_sequences", "path_exists_2_63", "path_exists_2_64_minus_1", "path_exists_last_id", "no_such_path_message", "length_mismatch_message",
+        "matching_lengths", "endmarker_argument")] + ["done"]
 
 
 def test_example_known_answer():
