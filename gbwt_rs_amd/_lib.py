@@ -98,6 +98,20 @@ class SuffixArrayInfo(C.Structure):
                 ("rank_ms", C.c_float), ("output_ms", C.c_float), ("round_ms", C.c_float * 64)]
 
 
+FM_COUNT_ONLY = 1     # gbwt_hip_fm_build_* flags
+
+
+class FmIndexInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n", "sigma", "block_rows", "blocks", "primary", "index_bytes", "planned_index_bytes", "sa_bytes", "peak_scratch_bytes",
+                                                "planned_scratch_bytes", "queries", "last_patterns", "last_steps", "last_total")] + \
+               [(name, C.c_uint32) for name in ("packed", "count_only", "path_level", "reserved")] + \
+               [(name, C.c_float) for name in ("suffix_array_ms", "histogram_ms", "codes_ms", "counts_ms", "fill_ms", "narrow_ms", "last_count_ms", "last_fill_ms")]
+
+
+class FmLocated(C.Structure):
+    _fields_ = [("d_offsets", C.c_void_p), ("d_values", C.c_void_p), ("d_ranges", C.c_void_p), ("total", C.c_uint64), ("m", C.c_uint64)]
+
+
 class ReferencePath(C.Structure):
     _fields_ = [("path_id", C.c_uint64), ("len", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64)]
 
@@ -226,6 +240,17 @@ SIGNATURES = {
     "gbwt_hip_path_suffix_array": (_int, [_p, _p, _p, _u64, _int, _p, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_write_suffix_array": (_int, [_p, _p, C.c_char_p, C.POINTER(_u64)]),
     "gbwt_hip_last_suffix_array_info": (_int, [_p, C.POINTER(SuffixArrayInfo)]),
+    "gbwt_hip_fm_build_text": (_int, [_int, _p, _u64, _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_fm_build_text_device": (_int, [_int, _p, _u64, _int, _p, C.c_uint32, _p, C.POINTER(_p)]),
+    "gbwt_hip_path_fm_index": (_int, [_p, _p, _p, _u64, _int, C.c_uint32, C.POINTER(_p)]),
+    "gbwt_hip_fm_close": (None, [_p]),
+    "gbwt_hip_fm_info": (_int, [_p, C.POINTER(FmIndexInfo)]),
+    "gbwt_hip_fm_count": (_int, [_p, _p, _p, _u64, _p]),
+    "gbwt_hip_fm_locate": (_int, [_p, _p, _p, _u64, _p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_fm_graph_positions": (_int, [_p, _p, _p, _p, _p, _u64, _int, _p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_fm_count_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmLocated)]),
+    "gbwt_hip_fm_locate_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmLocated)]),
+    "gbwt_hip_fm_graph_positions_device": (_int, [_p, _p, _p, _p, _p, _u64, _u64, _int, C.POINTER(FmLocated)]),
     "gbwt_hip_components_device": (_int, [_p, C.POINTER(Components)]),
     "gbwt_hip_weakly_connected_components": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_path_components": (_int, [_p, _p, _u64, _p]),

@@ -17,6 +17,8 @@ Method names, argument meaning and None-behaviour follow the Rust API (file:line
   GBZ.tag_array(ids, sa)           gbz-extract's extract_tag_array, src/bin/gbz-extract.rs:346-371, 408-482 (tags of a suffix array)
   GBZ.suffix_array(ids) / suffix_array_text(data)   the `base`.sa and `base`.bwt that tag-array mode reads (src/bin/gbz-extract.rs:321-344, 373-406)
                                    and nothing in the reference writes: suffix array and BWT of a text, built on the device
+  FMIndex.from_text(data) / GBZ.fm_index(ids)      an FM-index over such a text: count / locate / graph_positions of batches of patterns by
+                                   backward search (the reference has no counterpart: what its tag array is made for)
   GBZ.reference_positions(interval)   GBZ::reference_positions   src/gbz.rs:600-657   (reference_sample_names / reference_paths: 146-196)
   GBWT.node_iter / successors / predecessors        GBZ::node_iter, successors, predecessors   src/gbz.rs:312-353 (EdgeIter 819-892)
   GBZ.node_to_segment / segment_iter / segment_successors / segment_predecessors   src/gbz.rs:370-440 (SegmentIter, LinkIter 896-1016)
@@ -126,6 +128,145 @@ def suffix_array_text(data, sentinel=0, device=0, return_bwt=False):
 def last_suffix_array_info():
     """The last suffix_array_text call of the process (gbwt_hip_last_suffix_array_info without a workspace): a dict."""
     return _suffix_info(None)
+
+
+def _patterns_csr(patterns):
+    """Patterns as the library takes them -- (offsets uint64[m + 1], bytes uint8) -- from a list of bytes / str or from such a pair."""
+    if isinstance(patterns, (bytes, bytearray, str)):
+        raise TypeError("patterns must be a list of bytes / str or an (offsets, bytes) pair, not a single pattern")
+    if isinstance(patterns, tuple) and len(patterns) == 2 and isinstance(patterns[0], np.ndarray):
+        offsets = np.ascontiguousarray(patterns[0], dtype=np.uint64)
+        data = patterns[1]
+        data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        if offsets.ndim != 1 or offsets.size == 0 or data.ndim != 1:
+            raise ValueError("an (offsets, bytes) pair holds m + 1 offsets and one-dimensional bytes")
+        if np.any(offsets[1:] < offsets[:-1]) or int(offsets[-1]) > data.size:
+            raise ValueError("pattern offsets must ascend and end inside the bytes")
+        return offsets, data
+    rows = []
+    for p in patterns:
+        if isinstance(p, str):
+            p = p.encode()
+        if not isinstance(p, (bytes, bytearray)):
+            raise TypeError(f"a pattern must be bytes or str, not {type(p).__name__}")
+        rows.append(bytes(p))
+    offsets = np.zeros(len(rows) + 1, dtype=np.uint64)
+    if rows:
+        np.cumsum([len(p) for p in rows], out=offsets[1:])
+    return offsets, np.frombuffer(b"".join(rows), dtype=np.uint8)
+
+
+class FMIndex:
+    """An FM-index over a text on the device (gbwt_hip_fm_*; the reference has no counterpart): count and locate batches of patterns by backward
+    search.  The order is suffix_array_text's; a pattern that does not occur has the range (0, 0), the empty one (0, n).  One thread at a time."""
+
+    def __init__(self, handle, device=0, owner=None):
+        self._L = _lib.lib()
+        self._fm = handle
+        self._device = device
+        self._owner = owner                                # a path-level index: the GBZ it asks for tags, kept alive
+
+    @classmethod
+    def from_text(cls, data, sentinel=0, device=0, count_only=False):
+        """The index of any bytes (gbwt_hip_fm_build_text): the suffix array is built on the device as suffix_array_text builds it.
+        count_only: no suffix array is kept, locate is refused."""
+        text = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        if text.ndim != 1:
+            raise ValueError("data must be one-dimensional")
+        handle = C.c_void_p()
+        check(_lib.lib().gbwt_hip_fm_build_text(device, _ptr(text), text.size, int(sentinel), _lib.FM_COUNT_ONLY if count_only else 0, C.byref(handle)))
+        return cls(handle, device)
+
+    @classmethod
+    def from_device(cls, d_text, n, sentinel=0, d_sa=None, device=0, count_only=False, stream=None):
+        """gbwt_hip_fm_build_text_device: `d_text` (and `d_sa`, u64[n], or None: built by the call) are device pointers (int); only read."""
+        handle = C.c_void_p()
+        check(_lib.lib().gbwt_hip_fm_build_text_device(device, C.c_void_p(int(d_text)), n, int(sentinel), C.c_void_p(int(d_sa)) if d_sa else None,
+                                                       _lib.FM_COUNT_ONLY if count_only else 0, stream, C.byref(handle)))
+        return cls(handle, device)
+
+    def close(self):
+        if self._fm:
+            self._L.gbwt_hip_fm_close(self._fm)
+            self._fm = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def info(self):
+        """gbwt_hip_fm_info as a dict: n, sigma, block_rows, blocks, primary, index_bytes, ..., the build's phase times and the last query's."""
+        info = _lib.FmIndexInfo()
+        check(self._L.gbwt_hip_fm_info(self._fm, C.byref(info)))
+        return _as_dict(info, skip_reserved=True)
+
+    def count(self, patterns):
+        """The SA range of every pattern: uint64[m, 2] of (lo, hi); hi - lo is the number of occurrences."""
+        offsets, data = _patterns_csr(patterns)
+        m = offsets.size - 1
+        ranges = np.zeros((m, 2), dtype=np.uint64)
+        check(self._L.gbwt_hip_fm_count(self._fm, _ptr(offsets), _ptr(data), m, _ptr(ranges)))
+        return ranges
+
+    def _rows(self, call, offsets, data):
+        m = offsets.size - 1
+        out = np.zeros(m + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        check(call(_ptr(offsets), _ptr(data), m, _ptr(out), None, 0, C.byref(total)))
+        values = np.zeros(max(1, total.value), dtype=np.uint64)
+        check(call(_ptr(offsets), _ptr(data), m, _ptr(out), _ptr(values), values.size, C.byref(total)))
+        return out, values[: total.value]
+
+    def locate_csr(self, patterns):
+        """(offsets[m + 1], positions): row k holds the text positions SA[lo_k .. hi_k) of pattern k in SA order."""
+        offsets, data = _patterns_csr(patterns)
+        return self._rows(lambda o, b, m, *rest: self._L.gbwt_hip_fm_locate(self._fm, o, b, m, *rest), offsets, data)
+
+    def locate(self, pattern):
+        """The text positions of one pattern, in SA order."""
+        return self.locate_csr([pattern])[1].copy()
+
+    @staticmethod
+    def _device_patterns(d_offsets, d_bytes, m, nbytes):
+        if m < 0 or nbytes < 0:
+            raise ValueError("m and the number of pattern bytes must not be negative")
+        return C.c_void_p(int(d_offsets)), C.c_void_p(int(d_bytes)) if d_bytes else None, int(m), int(nbytes)
+
+    def count_device(self, d_offsets, d_bytes, m, nbytes):
+        """gbwt_hip_fm_count_device: the CSR of m patterns (u64 offsets, `nbytes` bytes) behind device pointers (int); a _lib.FmLocated whose
+        d_ranges[2 m] stays in HBM until the next request."""
+        out = _lib.FmLocated()
+        check(self._L.gbwt_hip_fm_count_device(self._fm, *self._device_patterns(d_offsets, d_bytes, m, nbytes), C.byref(out)))
+        return out
+
+    def locate_device(self, d_offsets, d_bytes, m, nbytes):
+        """gbwt_hip_fm_locate_device: d_offsets[m + 1], d_values[total] (positions) and d_ranges[2 m] in HBM until the next request."""
+        out = _lib.FmLocated()
+        check(self._L.gbwt_hip_fm_locate_device(self._fm, *self._device_patterns(d_offsets, d_bytes, m, nbytes), C.byref(out)))
+        return out
+
+
+class PathFMIndex(FMIndex):
+    """The FM-index of the text of paths of a GBZ (GBZ.fm_index): FMIndex, and the graph positions of the occurrences."""
+
+    def graph_positions_csr(self, patterns, unique=False):
+        """(offsets[m + 1], tags): row k holds the tags -- ((node << 11) | (orientation << 10)) + offset, 0 on an endmarker -- of the first
+        bases of pattern k's occurrences in SA order, or with unique=True the distinct tags ascending."""
+        offsets, data = _patterns_csr(patterns)
+        g = self._owner
+        return self._rows(lambda o, b, m, *rest: self._L.gbwt_hip_fm_graph_positions(self._fm, g._h, g._ws, o, b, m, int(bool(unique)), *rest), offsets, data)
+
+    def graph_positions(self, pattern, unique=True):
+        return self.graph_positions_csr([pattern], unique)[1].copy()
+
+    def graph_positions_device(self, d_offsets, d_bytes, m, nbytes, unique=False):
+        """gbwt_hip_fm_graph_positions_device: as locate_device, with tags in d_values."""
+        out = _lib.FmLocated()
+        g = self._owner
+        check(self._L.gbwt_hip_fm_graph_positions_device(self._fm, g._h, g._ws, *self._device_patterns(d_offsets, d_bytes, m, nbytes), int(bool(unique)), C.byref(out)))
+        return out
 
 
 class GBWT:
@@ -1059,6 +1200,16 @@ class GBZ(GBWT):
         runs = C.c_uint64(0)
         check(self._L.gbwt_hip_write_suffix_array(self._h, self._ws, os.fsencode(base), C.byref(runs)))
         return runs.value
+
+    def fm_index(self, path_ids, endmarker=0, count_only=False):
+        """The FM-index of the text path_sequences(path_ids, FORWARD, endmarker) returns (gbwt_hip_path_fm_index): a PathFMIndex, built on the
+        device from the text and suffix array of suffix_array_device(path_ids, endmarker).  endmarker: a byte value, not None."""
+        ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
+        if endmarker is None:
+            raise ValueError("an FM-index of paths needs an endmarker: the tags of the text count one behind every path")
+        handle = C.c_void_p()
+        check(self._L.gbwt_hip_path_fm_index(self._h, self._ws, _ptr(ids), ids.size, self._endmarker(endmarker), _lib.FM_COUNT_ONLY if count_only else 0, C.byref(handle)))
+        return PathFMIndex(handle, self._device, owner=self)
 
     def last_suffix_array_info(self):
         """The last suffix array built on this workspace (gbwt_hip_last_suffix_array_info): a dict -- n, rounds, active (the active set behind

@@ -444,6 +444,84 @@ typedef struct {
 } gbwt_hip_suffix_array_info;
 gbwt_hip_status gbwt_hip_last_suffix_array_info(const gbwt_hip_workspace *ws, gbwt_hip_suffix_array_info *out);
 
+/* ---- FM-index over a text: count and locate patterns ------------------------------------------------------------------------------------
+ * What the chain `sequences` -> suffix array -> tags is built for: "where in the graph does this string occur" is a backward search of the
+ * pattern over the BWT of the haplotype texts, and the tags of the resulting SA range.  The reference has no FM-index; the contract is that
+ * of the suffix array above: T[0, n) of arbitrary bytes, suffixes compared straight through endmarkers, a proper prefix first.  A pattern P
+ * occurs at i when T[i, i + |P|) == P; its occurrences are the SA range [lo, hi), hi - lo of them.  A pattern that does not occur -- one
+ * that holds a byte T lacks among them -- has the range (0, 0); the empty pattern has (0, n).
+ *
+ * The index is built on the device from T and SA: a code table for the sigma distinct bytes of T, C[c] = text bytes smaller
+ * than c, and the BWT of n + 1 rows -- row 0 is the empty suffix, whose BWT byte is T[n - 1]; row j + 1 is SA row j -- in blocks with the
+ * occurrences of every symbol in front of each block.  The row with SA[j] == 0 (`primary`) shows the call's sentinel in a BWT file; the
+ * sentinel may equal a byte of T and never counts as one.  sigma <= 8 (endmarker, A, C, G, T, N): a block is one 128-byte line of eight
+ * u32 counts and 96 BWT symbols, and one rank reads one line; larger alphabets: 256 symbols per block and the counts beside them.  Unless
+ * built with GBWT_HIP_FM_COUNT_ONLY the index holds SA as u32 (n <= 2^32 - 2, else GBWT_HIP_UNSUPPORTED before any work).  Scratch beyond
+ * the free device memory is GBWT_HIP_CAPACITY with the bytes needed; all scratch is freed before a build returns.
+ *
+ * An object serves ONE HOST THREAD AT A TIME: its requests run on a stream of its own, and their results stay in it until its next request. */
+typedef struct gbwt_hip_fm_index gbwt_hip_fm_index;    /* opaque */
+#define GBWT_HIP_FM_COUNT_ONLY 1u                       /* flags: no suffix array in the index; locate is GBWT_HIP_UNSUPPORTED */
+
+/* Any n bytes in host memory.  sentinel: a byte value 0 .. 255 (the BWT byte in front of suffix 0; it changes no answer). */
+gbwt_hip_status gbwt_hip_fm_build_text(int device, const void *text, uint64_t n, int sentinel, uint32_t flags, gbwt_hip_fm_index **out);
+/* The same over the caller's device buffers, only read: d_text[n], and d_sa[n], the suffix array of gbwt_hip_suffix_array_text_device --
+ * or NULL: the call makes it (its scratch: 8 n bytes and that call's).  A d_sa with a value outside the text or without an entry 0 is
+ * GBWT_HIP_INVALID_DATA.  The build is ordered on `stream` (a hipStream_t; NULL: the default stream) and done when the call returns. */
+gbwt_hip_status gbwt_hip_fm_build_text_device(int device, const void *d_text, uint64_t n, int sentinel, const uint64_t *d_sa, uint32_t flags, void *stream, gbwt_hip_fm_index **out);
+/* The index of the text of paths: text and suffix array are those of gbwt_hip_path_suffix_array_device(path_ids, n, endmarker) on `ws`
+ * (endmarker 0 .. 255: the tags count one behind every path).  The object remembers the handle, the path ids and the endmarker for
+ * gbwt_hip_fm_graph_positions; it must be closed before the handle. */
+gbwt_hip_status gbwt_hip_path_fm_index(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int endmarker, uint32_t flags,
+                                       gbwt_hip_fm_index **out);
+void gbwt_hip_fm_close(gbwt_hip_fm_index *fm);
+
+/* block_rows: BWT symbols per block (96 packed, 256 plain); primary: the SA row with SA[i] == 0; index_bytes: what the object keeps for
+ * the index (planned_index_bytes: what the plan promised), sa_bytes of it the suffix array (0 when count-only); peak_scratch_bytes /
+ * planned_scratch_bytes: the build's own scratch (the ranking of a suffix array made by the build comes on top: see above).  Phase times
+ * of the build by HIP events: suffix_array_ms (0 where the caller brought it), histogram_ms, codes_ms (the BWT symbols into the blocks),
+ * counts_ms (per block, and their sums across blocks), fill_ms, narrow_ms (SA to u32).  queries: the requests computed so far -- a call that
+ * repeats the request whose rows the object holds computes nothing and does not count; last_*: the patterns, backward steps (one per
+ * pattern byte consumed), values in the rows, and the kernel times of the last computed request (count: the search; fill: scan and rows). */
+typedef struct {
+    uint64_t n, sigma, block_rows, blocks, primary, index_bytes, planned_index_bytes, sa_bytes, peak_scratch_bytes, planned_scratch_bytes;
+    uint64_t queries, last_patterns, last_steps, last_total;
+    uint32_t packed, count_only, path_level, reserved;
+    float suffix_array_ms, histogram_ms, codes_ms, counts_ms, fill_ms, narrow_ms, last_count_ms, last_fill_ms;
+} gbwt_hip_fm_index_info;
+gbwt_hip_status gbwt_hip_fm_info(const gbwt_hip_fm_index *fm, gbwt_hip_fm_index_info *out);
+
+/* Queries.  Patterns are a CSR: pattern k is bytes[offsets[k], offsets[k + 1]), offsets[m + 1] ascending (GBWT_HIP_BAD_ARGUMENT otherwise, before
+ * any device work in the host forms).  One lane per pattern reads it backward and leaves once its range is empty.
+ *
+ * gbwt_hip_fm_count: ranges[2 k], ranges[2 k + 1] = (lo, hi) of pattern k.
+ * gbwt_hip_fm_locate: row k = SA[lo_k .. hi_k) in SA order: out_offsets[m + 1] and *total always; positions == NULL is the size query, and the
+ * call that repeats its request with a buffer (capacity: entries it holds; too few: GBWT_HIP_CAPACITY with *total) only copies -- nothing is
+ * searched twice.  GBWT_HIP_UNSUPPORTED on a count-only index.
+ * gbwt_hip_fm_graph_positions (an object of gbwt_hip_path_fm_index, with the handle it was made from and a workspace of it; anything else
+ * is GBWT_HIP_BAD_ARGUMENT): the located positions go to gbwt_hip_tags_device on `ws` without leaving the device: row k = the tags of the
+ * occurrences' first bases in SA order -- ((node << 11) | (orientation << 10)) + offset, 0 where an occurrence starts on an endmarker --,
+ * or with unique == 1 the distinct tags ascending (sorted on the device; at most 2^31 - 1 positions in such a request).  Same protocol. */
+gbwt_hip_status gbwt_hip_fm_count(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, uint64_t *ranges);
+gbwt_hip_status gbwt_hip_fm_locate(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, uint64_t *out_offsets, uint64_t *positions, uint64_t capacity,
+                                   uint64_t *total);
+gbwt_hip_status gbwt_hip_fm_graph_positions(gbwt_hip_fm_index *fm, const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *offsets, const void *bytes, uint64_t m,
+                                            int unique, uint64_t *out_offsets, uint64_t *tags, uint64_t capacity, uint64_t *total);
+/* The device forms: d_offsets[m + 1] and d_bytes[bytes] are in HBM and complete when the call is made (offsets that descend or exceed
+ * `bytes` are GBWT_HIP_BAD_ARGUMENT, found by the kernel; nothing outside d_bytes[0, bytes) is read).  The results stay in HBM, owned by
+ * the object, until its next request: d_ranges[2 m] for all three; d_offsets[m + 1] and d_values[total] -- positions, or tags -- for
+ * locate and graph positions (NULL, total 0 for count). */
+typedef struct {
+    const uint64_t *d_offsets;   /* [m + 1] */
+    const uint64_t *d_values;    /* [total] */
+    const uint64_t *d_ranges;    /* [2 m] */
+    uint64_t total, m;
+} gbwt_hip_fm_located;
+gbwt_hip_status gbwt_hip_fm_count_device(gbwt_hip_fm_index *fm, const uint64_t *d_offsets, const void *d_bytes, uint64_t m, uint64_t bytes, gbwt_hip_fm_located *out);
+gbwt_hip_status gbwt_hip_fm_locate_device(gbwt_hip_fm_index *fm, const uint64_t *d_offsets, const void *d_bytes, uint64_t m, uint64_t bytes, gbwt_hip_fm_located *out);
+gbwt_hip_status gbwt_hip_fm_graph_positions_device(gbwt_hip_fm_index *fm, const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *d_offsets, const void *d_bytes,
+                                                   uint64_t m, uint64_t bytes, int unique, gbwt_hip_fm_located *out);
+
 /* ---- graph topology: weakly connected components, contig path selection -------------------------------------------------------------
  * GBZ::weakly_connected_components (src/gbz.rs:570-598; known answer src/gbz/tests.rs:503-518): the node ids of the graph that the GBWT
  * records describe, partitioned by "joined through an edge, whatever the orientations" (the successors and predecessors of both
