@@ -17,6 +17,7 @@
 #include "build.hpp"
 #include "build_codec.hpp"
 #include "capi_internal.hpp"
+#include "device_common.hpp"
 #include "hip_raii.hpp"
 
 namespace gbwt_hip {
@@ -25,22 +26,10 @@ namespace {
 
 constexpr uint32_t THREADS = 256;
 
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + THREADS - 1) / THREADS); }   // n <= 2^32: at most 2^24 blocks
 __device__ __forceinline__ uint64_t global_thread() { return static_cast<uint64_t>(blockIdx.x) * THREADS + threadIdx.x; }
 
-// first k < n with a[k] >= x (n: none)
-template <class T>
-__device__ __forceinline__ uint64_t lower_bound(const T *a, uint64_t n, T x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-using Scratch = BuildScratch;
-using Buf = BuildBuf;
+using Scratch = CountedScratch;
+using Buf = CountedBuf;
 
 // ---- 1. expand ---------------------------------------------------------------------------------------------------------------------
 // Slot t: the path that owns it by bisection over first(p) = (off[p] + p) << bidir (a path owns one start and its visits, twice with
@@ -131,9 +120,9 @@ __global__ __launch_bounds__(THREADS) void k_build_record_bounds(const uint64_t 
         return;
     }
     const uint64_t v = r == 0 ? 0 : r + alphabet_offset;       // < 2^32
-    edge_first[r] = static_cast<uint32_t>(lower_bound<uint64_t>(edge, edges, v << 32));
-    run_first[r] = static_cast<uint32_t>(lower_bound<uint64_t>(run_key, runs, v << 32));   // (the runs are in record order; inside a record no key is below v << 32)
-    visit_first[r] = static_cast<uint32_t>(lower_bound<uint32_t>(rec, slots, static_cast<uint32_t>(v)));
+    edge_first[r] = static_cast<uint32_t>(lower_bound<uint64_t>(edge, 0, edges, v << 32));
+    run_first[r] = static_cast<uint32_t>(lower_bound<uint64_t>(run_key, 0, runs, v << 32));   // (the runs are in record order; inside a record no key is below v << 32)
+    visit_first[r] = static_cast<uint32_t>(lower_bound<uint32_t>(rec, 0, slots, static_cast<uint32_t>(v)));
 }
 
 // The visits of node w that came from v are one block of w's record; the offset of edge v -> w is where the block starts.  Lanes at the
@@ -147,7 +136,7 @@ __global__ __launch_bounds__(THREADS) void k_build_edge_offsets(const uint32_t *
     if (v == 0) return;
     if (i > sequences && rec[i - 1] == w && pred[i - 1] == v) return;
     const uint64_t rv = v - alphabet_offset, lo = edge_first[rv], hi = edge_first[rv + 1];
-    const uint64_t e = lo + lower_bound<uint64_t>(edge + lo, hi - lo, (static_cast<uint64_t>(v) << 32) | w);
+    const uint64_t e = lo + lower_bound<uint64_t>(edge + lo, 0, hi - lo, (static_cast<uint64_t>(v) << 32) | w);
     if (e < hi) edge_offset[e] = static_cast<uint32_t>(i - visit_first[w - alphabet_offset]);
 }
 
@@ -176,7 +165,7 @@ __global__ __launch_bounds__(THREADS) void k_build_run_sizes(const uint64_t *__r
     if (j > runs) return;
     if (j == runs) { sizes[j] = 0; return; }
     const uint64_t key = run_key[j], r = record_of(key, alphabet_offset), lo = edge_first[r], sigma = edge_first[r + 1] - lo;
-    const uint64_t rank = lower_bound<uint64_t>(edge + lo, sigma, key);
+    const uint64_t rank = lower_bound<uint64_t>(edge + lo, 0, sigma, key);
     const uint64_t len = (j + 1 < runs ? static_cast<uint64_t>(head[j + 1]) : slots) - head[j];
     run_rank[j] = static_cast<uint32_t>(rank);
     sizes[j] = build_codec::run_size(sigma, rank, len);
@@ -226,27 +215,6 @@ __global__ __launch_bounds__(THREADS) void k_build_fill_runs(const uint64_t *__r
     build_codec::write_run(data + hdr_at[r + 1] + edge_at[hi] + run_at[j], sigma, run_rank[j], len);
 }
 
-int bits_for(uint64_t values) {                      // bits that hold 0 .. values - 1 (at least one)
-    int b = 1;
-    while (b < 63 && (uint64_t(1) << b) < values) b++;
-    return b;
-}
-
-// exclusive sum of n u64 (temp grows as needed)
-void exclusive_sum(const uint64_t *in, uint64_t *out, uint64_t n, Scratch &sc, Buf &temp, hipStream_t s) {
-    size_t bytes = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n, s));
-    if (bytes > temp.bytes) temp.alloc(sc, bytes);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp.ptr, bytes, in, out, n, s));
-}
-
-template <class T> T read_value(const T *d, hipStream_t s) {
-    T v{};
-    HIP_CHECK(hipMemcpyAsync(&v, d, sizeof(T), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return v;
-}
-
 }  // namespace
 
 void build_node_range(const uint32_t *d_nodes, uint64_t n, uint32_t &min_node, uint32_t &max_node, hipStream_t s) {
@@ -267,7 +235,7 @@ void build_node_range(const uint32_t *d_nodes, uint64_t n, uint32_t &min_node, u
 // From the sorted slots as record bodies -- rec[i] the node of position i's record (0: the endmarker's), succ[i] its successor -- to the
 // record stream on the host: run heads, edge lists, offsets (the caller's: BodyOffsets), sizes, scans, bytes.  The construction and the
 // merge (merge.hip) both enter here.  rec and succ are given back on the way, temp (any size) is the scratch of the library calls; `begin` is an event the caller has recorded on s.
-void encode_sorted_bodies(BuildBuf &rec, BuildBuf &succ, uint64_t slots, uint64_t records, uint64_t alphabet_offset, const BodyOffsets &offsets, BuildScratch &sc, BuildBuf &temp,
+void encode_sorted_bodies(CountedBuf &rec, CountedBuf &succ, uint64_t slots, uint64_t records, uint64_t alphabet_offset, const BodyOffsets &offsets, CountedScratch &sc, CountedBuf &temp,
                           BuildOutput &out, hipEvent_t begin, hipStream_t s) {
     EventSet<5> ev;
     Buf head(sc, slots * sizeof(uint32_t)), count(sc, sizeof(uint64_t));
@@ -371,7 +339,7 @@ void build_records_on_device(const BuildInput &in, BuildOutput &out, hipStream_t
         HIP_CHECK(hipEventRecord(ev.e[1], s));
 
         // 2. ranks by reverse prefix: the first sort by the symbol of the slot, then doubling rounds until every rank is its own
-        const int bits = bits_for(slots);
+        const int bits = bits_for(slots, 63);
         size_t sort_bytes = 0, scan_bytes = 0;
         for (int end_bit : {33, 2 * bits}) {             // (the two sorts below)
             size_t need = 0;

@@ -10,6 +10,7 @@
 
 #include "../../include/gbwt_hip.h"
 #include "capi_internal.hpp"
+#include "counted_buffer.hpp"
 #include "host_index.hpp"
 
 namespace gbwt_hip {
@@ -36,35 +37,6 @@ struct BuildOutput {
     float expand_ms = 0, rank_ms = 0, edges_ms = 0, encode_ms = 0;
 };
 
-// HBM of a construction or a merge, counted: what it holds now and the most it ever held
-struct BuildScratch {
-    size_t now = 0, peak = 0;
-};
-struct BuildBuf {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    BuildScratch *owner = nullptr;
-    BuildBuf() = default;
-    BuildBuf(BuildScratch &sc, size_t need) { alloc(sc, need); }
-    BuildBuf(const BuildBuf &) = delete;
-    BuildBuf &operator=(const BuildBuf &) = delete;
-    ~BuildBuf() { release(); }
-    void alloc(BuildScratch &sc, size_t need) {
-        release();
-        const size_t want = std::max<size_t>(need, 256);
-        if (hipError_t e = hipMalloc(&ptr, want); e != hipSuccess) { ptr = nullptr; throw HipError{e, "hipMalloc(&ptr, want)"}; }
-        bytes = want; owner = &sc;
-        sc.now += want; sc.peak = std::max(sc.peak, sc.now);
-    }
-    void release() noexcept {
-        if (!ptr) return;
-        (void)hipFree(ptr);
-        owner->now -= bytes;
-        ptr = nullptr; bytes = 0;
-    }
-    template <class T> T *as() const { return static_cast<T *>(ptr); }
-};
-
 // The sorted slots as record bodies, on their way to bytes (build.hip: encode_sorted_bodies).  The edge lists are in hand when the
 // offsets are asked for: edge[e] = (node of the record << 32) | successor, sorted; record r owns [edge_first[r], edge_first[r + 1]) and the
 // positions from visit_first[r] on; edge_offset is zeroed.  `launch` starts the kernel that fills edge_offset on the stream; `release`
@@ -88,7 +60,7 @@ void build_records_on_device(const BuildInput &in, BuildOutput &out, hipStream_t
 // build.hip: from the sorted bodies to the record stream in out.data / out.starts (and out.edges_ms, counted from `begin`, an event
 // the caller has recorded on s, and out.encode_ms).  rec[i]: the node of position i's record (0: the endmarker's), succ[i]: its
 // successor; both are given back on the way.  temp: scratch of the library calls, any size, grown as needed.
-void encode_sorted_bodies(BuildBuf &rec, BuildBuf &succ, uint64_t slots, uint64_t records, uint64_t alphabet_offset, const BodyOffsets &offsets, BuildScratch &sc, BuildBuf &temp,
+void encode_sorted_bodies(CountedBuf &rec, CountedBuf &succ, uint64_t slots, uint64_t records, uint64_t alphabet_offset, const BodyOffsets &offsets, CountedScratch &sc, CountedBuf &temp,
                           BuildOutput &out, hipEvent_t begin, hipStream_t s);
 
 // min and max of n > 0 nodes in HBM (the caller of a device-resident input checks and sizes with them)

@@ -18,6 +18,7 @@
 
 #include "capi_internal.hpp"
 #include "extract_plan.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -95,7 +96,7 @@ gbwt_hip_status direct_rows(const Request &r) {
         HIP_CHECK(hipMemsetAsync(e.counters.ptr, 0, 4 * sizeof(uint32_t), s));
         if (rows.parted) launch_part_lengths(strided, e.seq_ids.as<uint64_t>(), n, e.lengths.as<uint64_t>(), e.counters.as<uint32_t>(), s);
         else launch_gather_lengths(ix->dev.seq_len, ix->dev.n_sequences, e.seq_ids.as<uint64_t>(), n, e.lengths.as<uint64_t>(), e.counters.as<uint32_t>(), s);
-        launch_scan(e.lengths.as<uint64_t>(), e.offsets.as<uint64_t>(), n, r.ws->scratch.scan_temp.ptr, r.temp_bytes, s);
+        launch_scan(e.lengths.as<uint64_t>(), e.offsets.as<uint64_t>(), n, r.ws->scratch.scan_temp.ptr, r.temp_bytes, s, knobs.scan_piece);
     }
     uint64_t total = rows.total;
     uint32_t max_len = rows.max_len;
@@ -120,14 +121,14 @@ gbwt_hip_status direct_rows(const Request &r) {
     uint64_t walkers = p.walkers;
     if (p.same_segments) a.walkers = walkers;
     if (p.needs_order) {
-        const size_t ob = walker_order_temp_bytes(n), sb = scan_temp_bytes(a.segments);
+        const size_t ob = walker_order_temp_bytes(n), sb = scan_temp_bytes(a.segments, knobs.scan_piece);
         e.order_keys.reserve(2 * n * sizeof(uint32_t)); e.order_rows.reserve(2 * n * sizeof(uint32_t));
         e.order_counts.reserve(a.segments * sizeof(uint64_t)); e.order_level.reserve((a.segments + 1ull) * sizeof(uint64_t));
-        e.order_temp.reserve(std::max<size_t>(std::max(ob, sb), 16));
+        e.order_temp.reserve(std::max(ob, sb));
         const uint32_t *sorted_rows = nullptr;
         launch_walker_order(strided, e.seq_ids.as<uint64_t>(), n, a.segments, e.order_keys.as<uint32_t>(), e.order_rows.as<uint32_t>(),
                             e.order_counts.as<uint64_t>(), e.order_level.as<uint64_t>(), e.order_temp.ptr, ob, &sorted_rows, s);
-        launch_scan(e.order_counts.as<uint64_t>(), e.order_level.as<uint64_t>(), a.segments, e.order_temp.ptr, sb, s);
+        launch_scan(e.order_counts.as<uint64_t>(), e.order_level.as<uint64_t>(), a.segments, e.order_temp.ptr, sb, s, knobs.scan_piece);
         HIP_CHECK(hipMemcpyAsync(&walkers, e.order_level.as<uint64_t>() + a.segments, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         a.sorted_rows = sorted_rows; a.level = e.order_level.as<uint64_t>(); a.walkers = walkers;
@@ -198,7 +199,7 @@ gbwt_hip_status pool_rows(const Request &r) {
         launch_walk(dev, a, s);
         HIP_CHECK(hipEventRecord(e.ev[1], s));
         HIP_CHECK(hipMemcpyAsync(&flags, a.flags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        launch_scan(a.lengths, e.offsets.as<uint64_t>(), n, r.ws->scratch.scan_temp.ptr, r.temp_bytes, s);
+        launch_scan(a.lengths, e.offsets.as<uint64_t>(), n, r.ws->scratch.scan_temp.ptr, r.temp_bytes, s, knobs.scan_piece);
         HIP_CHECK(hipStreamSynchronize(s));
         HIP_CHECK(hipGetLastError());
         if (!(flags & FLAG_POOL_OVERFLOW)) break;
@@ -278,8 +279,8 @@ gbwt_hip_status gbwt_hip_extract_part_device(const gbwt_hip_index *ix, gbwt_hip_
         e.lengths.reserve(std::max<uint64_t>(n, 1) * sizeof(uint64_t));
         e.offsets.reserve((n + 1) * sizeof(uint64_t));
         e.head.reserve(std::max<uint64_t>(n, 1) * sizeof(uint32_t));
-        const Request r{ix, ws, seq_ids, n, part, parts, n ? scan_temp_bytes(n) : 0, out};
-        ws->scratch.scan_temp.reserve(std::max<size_t>(r.temp_bytes, 16));
+        const Request r{ix, ws, seq_ids, n, part, parts, scan_temp_bytes(n, ws->knobs.scan_piece), out};
+        ws->scratch.scan_temp.reserve(r.temp_bytes);
         HIP_CHECK(hipEventRecord(e.ev[3], s));   // everything the extraction puts on the stream lies between ev[3] and ev[2]
         if (n) HIP_CHECK(hipMemcpyAsync(e.seq_ids.ptr, seq_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         // 4. one of three bodies, 5. each of which ends in finish()

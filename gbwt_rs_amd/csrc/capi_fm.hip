@@ -9,10 +9,12 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "device_common.hpp"
 #include "extract_files.hpp"
 #include "fm_index.hpp"
 #include "fm_plan.hpp"
 #include "kernels.hpp"
+#include "scan.hpp"
 #include "suffix_array.hpp"
 
 using namespace gbwt_hip;
@@ -219,12 +221,6 @@ gbwt_hip_status check_object(const gbwt_hip_fm_index *fm, Kind kind, const gbwt_
     return GBWT_HIP_OK;
 }
 
-int bits_for(uint64_t values) {                      // bits that hold 0 .. values - 1 (at least one)
-    int b = 1;
-    while (b < 32 && (uint64_t(1) << b) < values) b++;
-    return b;
-}
-
 // The rows of a request into the object.  Exactly one of h_offsets / d_offsets; bytes: the pattern bytes behind d_bytes (the host form: offsets[m]).
 gbwt_hip_status fm_compute(gbwt_hip_fm_index *fm, Kind kind, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m, uint64_t bytes,
                            int unique, const gbwt_hip_index *ix, gbwt_hip_workspace *ws) {
@@ -242,7 +238,7 @@ gbwt_hip_status fm_compute(gbwt_hip_fm_index *fm, Kind kind, const uint64_t *h_o
         fm->occ.reserve(slots * sizeof(uint64_t));
         fm->roff.reserve((slots + 1) * sizeof(uint64_t));
         fm->words.reserve(WORDS * sizeof(uint64_t));
-        fm->temp.reserve(std::max<size_t>(scan_temp_bytes(slots), 16));
+        fm->temp.reserve(scan_temp_bytes(m));
         uint64_t *d_words = fm->words.as<uint64_t>();
         HIP_CHECK(hipMemsetAsync(d_words, 0, WORDS * sizeof(uint64_t), s));
         if (h_offsets) {
@@ -292,7 +288,7 @@ gbwt_hip_status fm_compute(gbwt_hip_fm_index *fm, Kind kind, const uint64_t *h_o
                 fm->rank.reserve((total + 1) * sizeof(uint64_t));
                 fm->uoff.reserve((m + 1) * sizeof(uint64_t));
                 fm->temp.reserve(std::max<size_t>(fm_sort_temp_bytes(total), scan_temp_bytes(total)));
-                launch_fm_sort_rows(fm->tags.as<uint64_t>(), fm->rows.as<uint32_t>(), total, bits_for(m), fm->tmp_values.as<uint64_t>(), fm->tmp_rows.as<uint32_t>(),
+                launch_fm_sort_rows(fm->tags.as<uint64_t>(), fm->rows.as<uint32_t>(), total, bits_for(m, 32), fm->tmp_values.as<uint64_t>(), fm->tmp_rows.as<uint32_t>(),
                                     fm->sorted_values.as<uint64_t>(), fm->sorted_rows.as<uint32_t>(), fm->temp.ptr, fm->temp.bytes, s);
                 launch_fm_run_flags(fm->sorted_values.as<uint64_t>(), fm->sorted_rows.as<uint32_t>(), total, fm->flag.as<uint64_t>(), s);
                 launch_scan(fm->flag.as<uint64_t>(), fm->rank.as<uint64_t>(), total, fm->temp.ptr, fm->temp.bytes, s);

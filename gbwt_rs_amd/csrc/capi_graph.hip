@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -87,7 +88,7 @@ void ensure_components(const gbwt_hip_index *ix) {
             ix->components.offsets.reserve((components + 1) * sizeof(uint64_t));
             counts.reserve(std::max<uint64_t>(components, 1) * sizeof(uint64_t));
             DeviceBuffer scan_temp;
-            const size_t tb = std::max<size_t>(scan_temp_bytes(components + 1), 16);
+            const size_t tb = scan_temp_bytes(components);
             scan_temp.reserve(tb);
             launch_component_counts(g, label, components, counts.as<uint64_t>(), b.stream);
             launch_scan(counts.as<uint64_t>(), ix->components.offsets.as<uint64_t>(), components, scan_temp.ptr, tb, b.stream);

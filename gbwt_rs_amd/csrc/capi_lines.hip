@@ -23,6 +23,7 @@
 #include "gfa_host.hpp"
 #include "lines.hpp"
 #include "lines_plan.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -153,12 +154,13 @@ gbwt_hip_status lines_size(LinesRequest &r) {
     const ChunksCap cap = chunks_cap(r.paths.total, n);
     if (cap.refused) return fail(GBWT_HIP_UNSUPPORTED, LINES_TOO_MANY_CHUNKS);
     const LinesLayout at = lines_layout(n, cap.chunks);
-    r.tb = scan_temp_bytes(std::max(n, cap.chunks));
+    const uint64_t piece = ws->knobs.scan_piece;
+    r.tb = scan_temp_bytes(std::max(n, cap.chunks), piece);
     ws->scratch.a.reserve(at.a_bytes);
     ws->lines.b.reserve((n + 1) * sizeof(uint64_t));
     ws->scratch.chunk_first.reserve(at.chunk_first_bytes);
     ws->scratch.chunks.reserve(at.chunks_bytes);
-    ws->scratch.scan_temp.reserve(std::max<size_t>(r.tb, 16));
+    ws->scratch.scan_temp.reserve(r.tb);
     ws->lines.valid.reserve(std::max<uint64_t>(n, 16));
     void *const a = ws->scratch.a.ptr, *const first = ws->scratch.chunk_first.ptr, *const chunks = ws->scratch.chunks.ptr, *const temp = ws->scratch.scan_temp.ptr;
     r.d_line_len = scratch_at<uint64_t>(a, at.line_len); r.d_line_end = scratch_at<uint64_t>(a, at.line_end);
@@ -175,23 +177,23 @@ gbwt_hip_status lines_size(LinesRequest &r) {
     r.sizing = line_sizing(r.translated, ix->lc_state);
     r.rows = ChunkedRows{r.paths.d_offsets, r.paths.d_nodes, n, d_chunk_first, d_chunk_path, cap.chunks};
     hipStream_t s = r.s;
-    launch_chunk_plan(r.paths.d_offsets, n, cap.chunks, d_chunk_counts, d_chunk_first, d_chunk_path, temp, r.tb, s);
+    launch_chunk_plan(r.paths.d_offsets, n, cap.chunks, d_chunk_counts, d_chunk_first, d_chunk_path, temp, r.tb, s, piece);
     if (r.sizing == LineSizing::Cached) {
         launch_line_sizes_cached(r.paths.d_offsets, r.d_seq_ids, n, r.cache, r.hdr, r.p_lines, r.d_line_len, r.d_line_end, s);
     } else {
         if (r.sizing == LineSizing::Translated) {
             launch_chunk_stats_segments(r.rows, segment_tables(ix), r.p_lines, d_chunk_text, d_chunk_seq, d_chunk_bad, s);
-            launch_scan(d_chunk_bad, d_bad_before, cap.chunks, temp, r.tb, s);
+            launch_scan(d_chunk_bad, d_bad_before, cap.chunks, temp, r.tb, s, piece);
         } else {
             launch_chunk_stats(r.rows, ix->label_len.as<uint32_t>(), static_cast<uint64_t>(h.sequences_labels.size()), static_cast<uint32_t>(h.alphabet_offset + 1), r.p_lines,
                                d_chunk_text, d_chunk_seq, s);
         }
-        launch_scan(d_chunk_text, r.d_text_before, cap.chunks, temp, r.tb, s);
-        launch_scan(d_chunk_seq, d_seq_before, cap.chunks, temp, r.tb, s);
+        launch_scan(d_chunk_text, r.d_text_before, cap.chunks, temp, r.tb, s, piece);
+        launch_scan(d_chunk_seq, d_seq_before, cap.chunks, temp, r.tb, s, piece);
         launch_line_sizes(r.d_seq_ids, d_chunk_first, n, r.d_text_before, d_seq_before, r.translated ? d_bad_before : nullptr, r.hdr, r.p_lines, r.d_line_len, r.d_line_end,
                           r.d_valid, s);
     }
-    launch_scan(r.d_line_len, r.d_line_start, n, temp, r.tb, s);
+    launch_scan(r.d_line_len, r.d_line_start, n, temp, r.tb, s, piece);
     return GBWT_HIP_OK;
 }
 
@@ -307,11 +309,12 @@ gbwt_hip_status path_lines_impl(const gbwt_hip_index *ix, gbwt_hip_workspace *ws
 // Sizing of a segment tokens request: tokens and flag of every chunk, their scans, tokens and validity of every row.  Returns the rows
 // and their chunks for the fill; `at` says where the arrays lie.
 ChunkedRows segment_tokens_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const gbwt_hip_paths &paths, uint64_t n, uint64_t cap, const TokensLayout &at, hipStream_t s) {
-    const size_t tb = scan_temp_bytes(std::max(n, cap));
+    const uint64_t piece = ws->knobs.scan_piece;
+    const size_t tb = scan_temp_bytes(std::max(n, cap), piece);
     ws->scratch.a.reserve(at.a_bytes);
     ws->scratch.chunk_first.reserve(at.chunk_first_bytes);
     ws->scratch.chunks.reserve(at.chunks_bytes);
-    ws->scratch.scan_temp.reserve(std::max<size_t>(tb, 16));
+    ws->scratch.scan_temp.reserve(tb);
     ws->lines.valid.reserve(std::max<uint64_t>(n, 16));
     void *const first = ws->scratch.chunk_first.ptr, *const chunks = ws->scratch.chunks.ptr, *const temp = ws->scratch.scan_temp.ptr;
     uint64_t *const d_chunk_first = scratch_at<uint64_t>(first, at.chunk_first), *const d_chunk_counts = scratch_at<uint64_t>(first, at.chunk_counts);
@@ -319,10 +322,10 @@ ChunkedRows segment_tokens_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws
     uint64_t *const d_tokens_before = scratch_at<uint64_t>(chunks, at.tokens_before), *const d_bad_before = scratch_at<uint64_t>(chunks, at.bad_before);
     uint32_t *const d_chunk_path = scratch_at<uint32_t>(chunks, at.chunk_path);
     const ChunkedRows rows{paths.d_offsets, paths.d_nodes, n, d_chunk_first, d_chunk_path, cap};
-    launch_chunk_plan(paths.d_offsets, n, cap, d_chunk_counts, d_chunk_first, d_chunk_path, temp, tb, s);
+    launch_chunk_plan(paths.d_offsets, n, cap, d_chunk_counts, d_chunk_first, d_chunk_path, temp, tb, s, piece);
     launch_segment_chunk_tokens(rows, segment_tables(ix), d_chunk_tokens, d_chunk_bad, s);
-    launch_scan(d_chunk_tokens, d_tokens_before, cap, temp, tb, s);
-    launch_scan(d_chunk_bad, d_bad_before, cap, temp, tb, s);
+    launch_scan(d_chunk_tokens, d_tokens_before, cap, temp, tb, s, piece);
+    launch_scan(d_chunk_bad, d_bad_before, cap, temp, tb, s, piece);
     launch_segment_row_tokens(d_chunk_first, n, d_tokens_before, d_bad_before, scratch_at<uint64_t>(ws->scratch.a.ptr, at.row_tokens), ws->lines.valid.as<uint8_t>(), s);
     return rows;
 }

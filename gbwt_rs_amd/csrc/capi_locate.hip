@@ -3,7 +3,9 @@
 #include <string>
 #include <vector>
 
-#include "refpos.hpp"
+#include "capi_internal.hpp"
+#include "device_common.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -35,7 +37,7 @@ void build_locate(const gbwt_hip_index *ix, hipStream_t s) {
     // 1. the sampled records and where their positions go
     lens.reserve(std::max<uint64_t>(records, 1) * sizeof(uint64_t));
     ix->locate.base.reserve((records + 1) * sizeof(uint64_t));
-    const size_t scan_bytes = std::max<size_t>(scan_temp_bytes(std::max<uint64_t>(records, 1)), 16);
+    const size_t scan_bytes = scan_temp_bytes(records);
     temp.reserve(std::max(scan_bytes, locate_sort_temp_bytes(sequences)));
     launch_locate_lengths(d, locate_threshold(ix->knobs.locate_interval), lens.as<uint64_t>(), d_flags, s);
     if (records) { launch_scan(lens.as<uint64_t>(), ix->locate.base.as<uint64_t>(), records, temp.ptr, scan_bytes, s); launches += 2; }
@@ -106,19 +108,6 @@ void ensure_locate(const gbwt_hip_index *ix, gbwt_hip_workspace *ws) {
     });
 }
 
-uint64_t read_word(const uint64_t *d_word, hipStream_t s) {
-    uint64_t v = 0;
-    HIP_CHECK(hipMemcpyAsync(&v, d_word, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return v;
-}
-
-int bits_for(uint64_t values) {                      // bits that hold 0 .. values - 1 (at least one)
-    int b = 1;
-    while (b < 32 && (uint64_t(1) << b) < values) b++;
-    return b;
-}
-
 gbwt_hip_status check_request(const gbwt_hip_index *ix, const gbwt_hip_workspace *ws, const void *items, uint64_t n, int unique) {
     if (unique != 0 && unique != 1) return fail(GBWT_HIP_BAD_ARGUMENT, "unique must be 0 or 1");
     if (!ix || !ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
@@ -127,7 +116,7 @@ gbwt_hip_status check_request(const gbwt_hip_index *ix, const gbwt_hip_workspace
     return GBWT_HIP_OK;
 }
 
-// words of locate.words: [0] flags (low half), [1] scan carry, [2] LF steps of a counting launch
+// words of locate.words: [0] flags (low half), [2] LF steps of a counting launch
 constexpr uint64_t WORDS = 4;
 
 // The rows of a request, computed into the workspace (locate.off or uoff, ids, valid, total).  Exactly one of h_states / d_states.
@@ -149,7 +138,7 @@ gbwt_hip_status locate_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws,
         ws->locate.off.reserve((rows + 1) * sizeof(uint64_t));
         ws->locate.valid.reserve(rows);
         ws->locate.words.reserve(WORDS * sizeof(uint64_t));
-        const size_t scan_bytes = std::max<size_t>(scan_temp_bytes(std::min<uint64_t>(rows, REFPOS_SCAN_PIECE)), 16);
+        const size_t scan_bytes = scan_temp_bytes(n, ws->knobs.scan_piece);
         ws->scratch.scan_temp.reserve(scan_bytes);
         uint64_t *d_words = ws->locate.words.as<uint64_t>();
         uint32_t *d_flags = reinterpret_cast<uint32_t *>(d_words);
@@ -162,9 +151,9 @@ gbwt_hip_status locate_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws,
         }
         // 1. which states are ranges of a record, and the rows' offsets
         launch_locate_valid(d, d_states, d_given, n, ws->locate.counts.as<uint64_t>(), ws->locate.valid.as<uint8_t>(), s);
-        launch_refpos_scan(ws->locate.counts.as<uint64_t>(), ws->locate.off.as<uint64_t>(), n, d_words + 1, ws->scratch.scan_temp.ptr, scan_bytes, s);
+        launch_scan(ws->locate.counts.as<uint64_t>(), ws->locate.off.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, scan_bytes, s, ws->knobs.scan_piece);
         HIP_CHECK(hipGetLastError());
-        const uint64_t total = read_word(ws->locate.off.as<uint64_t>() + n, s);     // the one wait in front of the rows: the total sizes them
+        const uint64_t total = read_value(ws->locate.off.as<uint64_t>() + n, s);     // the one wait in front of the rows: the total sizes them
         if (total > (~uint64_t(0)) / 64) return fail(GBWT_HIP_CAPACITY, "too many ids for device memory");
         const uint64_t items = std::max<uint64_t>(total, 1);
         const bool keyed = unique != 0 && total != 0 && !count_steps;
@@ -198,12 +187,12 @@ gbwt_hip_status locate_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws,
             ws->locate.rank.reserve((items + 1) * sizeof(uint64_t));
             ws->locate.uoff.reserve((rows + 1) * sizeof(uint64_t));
             ws->locate.temp.reserve(locate_sort_temp_bytes(std::min(total, piece)));
-            ws->scratch.scan_temp.reserve(std::max<size_t>(scan_temp_bytes(std::min<uint64_t>(items, REFPOS_SCAN_PIECE)), 16));
-            const int bits = 32 + bits_for(n);
+            ws->scratch.scan_temp.reserve(scan_temp_bytes(total, ws->knobs.scan_piece));
+            const int bits = 32 + bits_for(n, 32);
             for (size_t c = 0; c + 1 < cuts.size(); c++)
                 launch_locate_sort_keys(ws->locate.keys.as<uint64_t>() + cuts[c], ws->locate.sorted.as<uint64_t>() + cuts[c], cuts[c + 1] - cuts[c], bits, ws->locate.temp.ptr, ws->locate.temp.bytes, s);
             launch_locate_run_flags(ws->locate.sorted.as<uint64_t>(), total, ws->locate.flag.as<uint64_t>(), s);
-            launch_refpos_scan(ws->locate.flag.as<uint64_t>(), ws->locate.rank.as<uint64_t>(), total, d_words + 1, ws->scratch.scan_temp.ptr, ws->scratch.scan_temp.bytes, s);
+            launch_scan(ws->locate.flag.as<uint64_t>(), ws->locate.rank.as<uint64_t>(), total, ws->scratch.scan_temp.ptr, ws->scratch.scan_temp.bytes, s, ws->knobs.scan_piece);
             launch_locate_compact(ws->locate.sorted.as<uint64_t>(), ws->locate.rank.as<uint64_t>(), total, ws->locate.off.as<uint64_t>(), n, ws->locate.ids.as<uint64_t>(), ws->locate.uoff.as<uint64_t>(), s);
             HIP_CHECK(hipMemcpyAsync(&kept, ws->locate.rank.as<uint64_t>() + total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         }

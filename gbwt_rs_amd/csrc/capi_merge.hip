@@ -37,8 +37,8 @@ gbwt_hip_status rebuild(const gbwt_hip_index *a, const gbwt_hip_index *b, uint64
     st = extract_all(b, wb, rb);
     if (st != GBWT_HIP_OK) return st;
     const uint64_t n = ra.n + rb.n, total = ra.total + rb.total;
-    BuildScratch sc;
-    BuildBuf offsets(sc, (n + 1) * sizeof(uint64_t)), nodes(sc, total * sizeof(uint32_t));
+    CountedScratch sc;
+    CountedBuf offsets(sc, (n + 1) * sizeof(uint64_t)), nodes(sc, total * sizeof(uint32_t));
     merge_concat_rows(ra.d_offsets, ra.d_nodes, ra.n, ra.total, rb.d_offsets, rb.d_nodes, rb.n, rb.total, offsets.as<uint64_t>(), nodes.as<uint32_t>(), s);
     HIP_CHECK(hipStreamSynchronize(s));
     build_records_on_device(BuildInput{offsets.as<uint64_t>(), nodes.as<uint32_t>(), n, total, false, min_node, max_node}, o, s);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -128,7 +129,7 @@ bool checkpoint_samples(gbwt_hip_index &ix, uint32_t interval, uint32_t *d_flags
         static size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
         void *take(size_t bytes) { void *p = static_cast<char *>(arena.ptr) + at; at += padded(bytes); return p; }
     } small, large;
-    const size_t tb = scan_temp_bytes(nr), sb = scan_temp_bytes(S), scan_bytes = std::max<size_t>(std::max(tb, sb), 16);
+    const size_t tb = scan_temp_bytes(nr), sb = scan_temp_bytes(S), scan_bytes = std::max(tb, sb);
     small.arena.reserve(Carver::padded(nr * sizeof(uint64_t)) + Carver::padded((nr + 1) * sizeof(uint64_t)) + Carver::padded(scan_bytes) + Carver::padded(2 * sizeof(uint64_t)) +
                         Carver::padded(S * sizeof(uint64_t)));
     uint64_t *counts = static_cast<uint64_t *>(small.take(nr * sizeof(uint64_t))), *cp_first = static_cast<uint64_t *>(small.take((nr + 1) * sizeof(uint64_t)));
@@ -223,16 +224,15 @@ void decode_starts_on_device(gbwt_hip_index &ix) {
     DeviceBuffer words, ranks, scan_tmp, flags;
     words.reserve(std::max<uint64_t>(v.high_words + v.low_words, 1) * sizeof(uint64_t));
     ranks.reserve(2 * (v.high_words + 1) * sizeof(uint64_t));
-    const size_t tb = scan_temp_bytes(std::max<uint64_t>(v.high_words, 1));
-    scan_tmp.reserve(std::max<size_t>(tb, 16));
+    const size_t tb = scan_temp_bytes(v.high_words);
+    scan_tmp.reserve(tb);
     flags.reserve(sizeof(uint32_t));
     HIP_CHECK(hipMemsetAsync(flags.ptr, 0, sizeof(uint32_t), nullptr));
     uint64_t *d_high = words.as<uint64_t>(), *d_low = d_high + v.high_words, *d_counts = ranks.as<uint64_t>(), *d_rank = d_counts + (v.high_words + 1);
     if (v.high_words) HIP_CHECK(hipMemcpy(d_high, v.high, v.high_words * sizeof(uint64_t), hipMemcpyHostToDevice));
     if (v.low_words) HIP_CHECK(hipMemcpy(d_low, v.low, v.low_words * sizeof(uint64_t), hipMemcpyHostToDevice));
     launch_ef_counts(d_high, v.high_words, d_counts, nullptr);
-    if (v.high_words) launch_scan(d_counts, d_rank, v.high_words, scan_tmp.ptr, tb, nullptr);
-    else HIP_CHECK(hipMemsetAsync(d_rank, 0, sizeof(uint64_t), nullptr));
+    launch_scan(d_counts, d_rank, v.high_words, scan_tmp.ptr, tb, nullptr);
     // the declared number of ones must be the number of set bits BEFORE it sizes the table (a corrupt count could ask for 32 times the file
     // size of device memory and surface as a device error instead of InvalidData: the host decode checks in the same order)
     uint64_t total = 0;
@@ -383,7 +383,7 @@ void build_tables(gbwt_hip_index &ix, uint64_t generic_records, DeviceBuffer &sc
     table_base.reserve((n_records + 1) * sizeof(uint64_t)); edge_base.reserve((n_records + 1) * sizeof(uint64_t));
     launch_table_counts(d, positions.as<uint64_t>(), sigmas.as<uint64_t>(), nullptr);
     const size_t tb = scan_temp_bytes(n_records);
-    scan_tmp.reserve(std::max<size_t>(tb, 16));
+    scan_tmp.reserve(tb);
     launch_scan(positions.as<uint64_t>(), table_base.as<uint64_t>(), n_records, scan_tmp.ptr, tb, nullptr);
     launch_scan(sigmas.as<uint64_t>(), edge_base.as<uint64_t>(), n_records, scan_tmp.ptr, tb, nullptr);
     uint64_t total_positions = 0, total_edges = 0;
@@ -513,7 +513,7 @@ void samples_after_walk(gbwt_hip_index &ix, Sampling how, uint32_t interval, con
     ix.sample_base.reserve((h.sequences + 1) * sizeof(uint64_t));
     launch_sample_counts(ix.seq_len.as<uint32_t>(), h.sequences, interval, counts.as<uint64_t>(), nullptr);
     const size_t tb = scan_temp_bytes(h.sequences);
-    scan_tmp.reserve(std::max<size_t>(tb, 16));
+    scan_tmp.reserve(tb);
     launch_scan(counts.as<uint64_t>(), ix.sample_base.as<uint64_t>(), h.sequences, scan_tmp.ptr, tb, nullptr);
     uint64_t total_samples = 0;
     HIP_CHECK(hipMemcpy(&total_samples, ix.sample_base.as<uint64_t>() + h.sequences, sizeof(uint64_t), hipMemcpyDeviceToHost));

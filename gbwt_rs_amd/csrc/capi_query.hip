@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -202,11 +203,11 @@ gbwt_hip_status gbwt_hip_follow(const gbwt_hip_index *ix, gbwt_hip_workspace *ws
             ws->query.in_b.reserve(n * sizeof(uint64_t));
             ws->query.out_valid.reserve(n);
             ws->query.follow_off.reserve((n + 1) * sizeof(uint64_t));
-            const size_t temp_bytes = scan_temp_bytes(n);
-            ws->scratch.scan_temp.reserve(std::max<size_t>(temp_bytes, 16));
+            const size_t temp_bytes = scan_temp_bytes(n, ws->knobs.scan_piece);
+            ws->scratch.scan_temp.reserve(temp_bytes);
             HIP_CHECK(hipMemcpyAsync(ws->query.in_a.ptr, states, key_bytes, hipMemcpyHostToDevice, s));
             launch_follow_count(ix->dev, ws->query.in_a.as<gbwt_hip_bd_state>(), n, backward != 0, ws->query.in_b.as<uint64_t>(), ws->query.out_valid.as<uint8_t>(), s);
-            launch_scan(ws->query.in_b.as<uint64_t>(), ws->query.follow_off.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, temp_bytes, s);
+            launch_scan(ws->query.in_b.as<uint64_t>(), ws->query.follow_off.as<uint64_t>(), n, ws->scratch.scan_temp.ptr, temp_bytes, s, ws->knobs.scan_piece);
             HIP_CHECK(hipGetLastError());
         }
         HIP_CHECK(hipMemcpyAsync(out_offsets, ws->query.follow_off.ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));

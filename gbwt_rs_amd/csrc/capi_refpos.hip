@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "refpos.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -112,22 +113,22 @@ gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
         if (P > 0xFFFFFFFFull) return fail(GBWT_HIP_UNSUPPORTED, "the requested paths hold " + std::to_string(P) + " nodes: a request for positions is limited to 2^32 - 1");
         const RefposRows rows{paths.d_offsets, paths.d_nodes, n, P};
         const uint64_t words = (P + 1) * sizeof(uint64_t);
-        const size_t tb = std::max<size_t>(scan_temp_bytes(std::min<uint64_t>(std::max<uint64_t>(P, 1), REFPOS_SCAN_PIECE)), 16);
+        const uint64_t piece = ws->knobs.scan_piece;
+        const size_t tb = scan_temp_bytes(P, piece);
         require_fits({{&ws->refpos.off, words}, {&ws->refpos.mark, words}, {&ws->refpos.jump, words}, {&ws->scratch.scan_temp, tb}}, "the offsets, marks and jumps of a request for positions");
         ws->refpos.off.reserve(words); ws->refpos.mark.reserve(words); ws->refpos.jump.reserve(words);
         ws->scratch.scan_temp.reserve(tb);
         ws->refpos.rows.reserve(host_rows.size() * sizeof(uint64_t));
-        ws->refpos.flags.reserve(REFPOS_FLAGS * sizeof(uint32_t) + sizeof(uint64_t));
+        ws->refpos.flags.reserve(REFPOS_FLAGS * sizeof(uint32_t));
         uint64_t *d_off = ws->refpos.off.as<uint64_t>(), *d_mark = ws->refpos.mark.as<uint64_t>(), *d_slot = ws->refpos.jump.as<uint64_t>();
         uint32_t *d_jump = ws->refpos.jump.as<uint32_t>(), *d_next = d_jump + (P + 1), *d_flags = ws->refpos.flags.as<uint32_t>();
-        uint64_t *d_carry = reinterpret_cast<uint64_t *>(d_flags + REFPOS_FLAGS);
         const uint64_t *d_rows = ws->refpos.rows.as<uint64_t>();
         HIP_CHECK(hipMemcpyAsync(ws->refpos.rows.ptr, host_rows.data(), host_rows.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemsetAsync(ws->refpos.flags.ptr, 0, REFPOS_FLAGS * sizeof(uint32_t), s));
         HIP_CHECK(hipEventRecord(ws->refpos.ev[0], s));
         // 2. bases in front of every position
         launch_refpos_lengths(rows, labels_of(ix), d_mark, s);
-        launch_refpos_scan(d_mark, d_off, P, d_carry, ws->scratch.scan_temp.ptr, tb, s);
+        launch_scan(d_mark, d_off, P, ws->scratch.scan_temp.ptr, tb, s, piece);
         // 3. successors, 4. the greedy chain of every row by pointer doubling
         launch_refpos_succ(rows, d_off, interval, d_jump, s);
         HIP_CHECK(hipMemsetAsync(d_mark, 0, words, s));
@@ -135,7 +136,7 @@ gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
         const uint32_t rounds = rounds_for(P);
         for (uint32_t t = 0; t < rounds; t++) { launch_refpos_round(d_mark, d_jump, d_next, P, d_flags, t, s); std::swap(d_jump, d_next); }
         // 5. slots (over the jump arrays, which nobody reads any more)
-        launch_refpos_scan(d_mark, d_slot, P, d_carry, ws->scratch.scan_temp.ptr, tb, s);
+        launch_scan(d_mark, d_slot, P, ws->scratch.scan_temp.ptr, tb, s, piece);
         uint64_t total = 0;
         uint32_t flags[REFPOS_FLAGS] = {};
         HIP_CHECK(hipMemcpyAsync(&total, d_slot + P, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -143,9 +144,8 @@ gbwt_hip_status positions_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
         HIP_CHECK(hipEventRecord(ws->refpos.ev[1], s));
         HIP_CHECK(hipStreamSynchronize(s));          // the one wait in front of the results: the total sizes them
         HIP_CHECK(hipGetLastError());
-        const uint64_t pieces = (P + REFPOS_SCAN_PIECE - 1) / REFPOS_SCAN_PIECE;
-        // lengths, two scans (a piece behind the first has two carry launches around it), successors, first marks, the rounds, paths, walk
-        ws->refpos.launches = static_cast<uint32_t>((P ? 1 : 0) + 2 * (P ? 3 * pieces - 2 : 0) + 2 + rounds + 2);
+        // lengths, two scans (one launch per piece of GBWT_HIP_SCAN_PIECE positions: ceil(P / piece) each), successors, first marks, the rounds, paths, walk
+        ws->refpos.launches = static_cast<uint32_t>((P ? 1 : 0) + 2 * scan_launches(P, piece) + 2 + rounds + 2);
         for (uint32_t t = 0; t < rounds; t++) ws->refpos.rounds += flags[t] != 0 ? 1u : 0u;
         if (total > (~uint64_t(0)) / sizeof(gbwt_hip_reference_position)) return fail(GBWT_HIP_CAPACITY, "too many positions for device memory");
         const uint64_t result_bytes = std::max<uint64_t>(total, 1) * sizeof(gbwt_hip_reference_position);

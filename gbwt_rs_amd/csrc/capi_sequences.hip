@@ -11,6 +11,7 @@
 #include "capi_internal.hpp"
 #include "extract_files.hpp"
 #include "gfa_host.hpp"
+#include "scan.hpp"
 #include "sequences.hpp"
 
 using namespace gbwt_hip;
@@ -63,28 +64,29 @@ gbwt_hip_status sequences_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *
         // 2. sizes.  Chunks of SEQ_CHUNK positions (at least one per row, at most len / SEQ_CHUNK + 1): launches and scans run over that bound.
         const uint64_t chunks_cap = paths.total / SEQ_CHUNK + n;
         if (chunks_cap > 0x7FFFFFFFull) return fail(GBWT_HIP_UNSUPPORTED, "too many chunks in one batch: ask for fewer paths per call");
-        const size_t tb = scan_temp_bytes(std::max(n, chunks_cap) + 1);
+        const uint64_t piece = ws->knobs.scan_piece;
+        const size_t tb = scan_temp_bytes(std::max(n, chunks_cap) + 1, piece);
         ws->scratch.a.reserve(n * sizeof(uint64_t));
         ws->scratch.chunk_first.reserve(2 * (n + 1) * sizeof(uint64_t));
         ws->scratch.chunks.reserve((2 * chunks_cap + 1) * sizeof(uint64_t) + (chunks_cap + 1) * sizeof(uint32_t));
         ws->scratch.plan.reserve(chunks_cap * sizeof(SeqPlan));
-        ws->scratch.scan_temp.reserve(std::max<size_t>(tb, 16));
+        ws->scratch.scan_temp.reserve(tb);
         uint64_t *d_row_len = ws->scratch.a.as<uint64_t>(), *d_row_start = ws->bases.offsets.as<uint64_t>();
         uint64_t *d_chunk_first = ws->scratch.chunk_first.as<uint64_t>(), *d_chunk_counts = d_chunk_first + (n + 1);
         uint64_t *d_chunk_bases = ws->scratch.chunks.as<uint64_t>(), *d_bases_before = d_chunk_bases + chunks_cap;
         uint32_t *d_chunk_path = reinterpret_cast<uint32_t *>(d_bases_before + (chunks_cap + 1));
         const Labels labels = labels_of(ix);
         const ChunkedRows rows{paths.d_offsets, paths.d_nodes, n, d_chunk_first, d_chunk_path, chunks_cap};
-        launch_chunk_plan(paths.d_offsets, n, chunks_cap, d_chunk_counts, d_chunk_first, d_chunk_path, ws->scratch.scan_temp.ptr, tb, s);
+        launch_chunk_plan(paths.d_offsets, n, chunks_cap, d_chunk_counts, d_chunk_first, d_chunk_path, ws->scratch.scan_temp.ptr, tb, s, piece);
         const auto chunk_pass = [&]() {
             launch_chunk_bases(rows, labels, d_chunk_bases, s);
-            launch_scan(d_chunk_bases, d_bases_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s);
+            launch_scan(d_chunk_bases, d_bases_before, chunks_cap, ws->scratch.scan_temp.ptr, tb, s, piece);
         };
         // The host waits once, for the total that sizes the text buffer.  With the line cache the rows are sized without a node read and the
         // total leaves before the pass that places the chunks inside their rows: the host's wait and allocation run under that pass.
         if (!cacheable) chunk_pass();
         launch_row_bytes(d_seq_ids, n, h.sequences, cacheable ? ix->lc_path.as<uint64_t>() : nullptr, d_chunk_first, d_bases_before, endmarker, d_row_len, s);
-        launch_scan(d_row_len, d_row_start, n, ws->scratch.scan_temp.ptr, tb, s);
+        launch_scan(d_row_len, d_row_start, n, ws->scratch.scan_temp.ptr, tb, s, piece);
         HIP_CHECK(hipMemcpyAsync(ws->extract.pinned_words.p, d_row_start + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipEventRecord(ws->bases.ev[1], s));
         if (cacheable) chunk_pass();

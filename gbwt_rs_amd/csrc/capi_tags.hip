@@ -15,6 +15,7 @@
 #include "batch_writer.hpp"
 #include "capi_internal.hpp"
 #include "extract_files.hpp"
+#include "scan.hpp"
 #include "tags.hpp"
 
 using namespace gbwt_hip;
@@ -71,10 +72,7 @@ gbwt_hip_status tags_plan(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, cons
         if (st != GBWT_HIP_OK) return st;
         HIP_CHECK(hipEventElapsedTime(&ws->tags.walk_ms, ws->extract.ev[0], ws->extract.ev[1]));
         const uint64_t positions = paths.total + n;
-        // GBWT_HIP_TAG_SCAN_PIECE (positions per launch of the scan) and GBWT_HIP_TAG_WIDE (64-bit hints whatever the size) let tests reach what
-        // only plans of 2^30 and 2^32 positions reach otherwise; read when a plan is made
-        uint64_t scan_piece = TAG_SCAN_PIECE;
-        if (const char *v = std::getenv("GBWT_HIP_TAG_SCAN_PIECE")) scan_piece = std::min<uint64_t>(TAG_SCAN_PIECE, std::max<uint64_t>(1024, std::strtoull(v, nullptr, 10)));
+        // GBWT_HIP_TAG_WIDE (64-bit hints whatever the size) lets tests reach what only plans of 2^32 positions reach otherwise; read when a plan is made
         const char *force_wide = std::getenv("GBWT_HIP_TAG_WIDE");
         const bool wide = positions > 0xFFFFFFFFull || (force_wide && std::atoi(force_wide) != 0);
         DeviceBuffer lengths;                        // the label lengths in front of the scan: scratch of the plan
@@ -82,14 +80,13 @@ gbwt_hip_status tags_plan(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, cons
         ws->tags.node.reserve(positions * sizeof(uint32_t));
         ws->tags.off.reserve((positions + 1) * sizeof(uint64_t));
         lengths.reserve(positions * sizeof(uint64_t));
-        const size_t tb = scan_temp_bytes(std::min(positions, scan_piece));
-        ws->scratch.scan_temp.reserve(std::max<size_t>(tb, 16));
+        const size_t tb = scan_temp_bytes(positions, ws->knobs.scan_piece);
+        ws->scratch.scan_temp.reserve(tb);
         ws->scratch.a.reserve((n + 1) * sizeof(uint64_t));
         uint64_t *d_len = lengths.as<uint64_t>(), *d_off = ws->tags.off.as<uint64_t>(), *d_rows = ws->scratch.a.as<uint64_t>();
         HIP_CHECK(hipEventRecord(ws->tags.ev[0], s));
         launch_tag_positions(paths.d_offsets, paths.d_nodes, n, positions, labels_of(ix), ws->tags.node.as<uint32_t>(), d_len, s);
-        // (the word of scratch: one nobody reads before the next request clears the state)
-        launch_tag_scan(d_len, d_off, positions, scan_piece, ws->tags.state.as<TagState>()->last, ws->scratch.scan_temp.ptr, tb, s);
+        launch_scan(d_len, d_off, positions, ws->scratch.scan_temp.ptr, tb, s, ws->knobs.scan_piece);
         launch_tag_rows(paths.d_offsets, n, d_off, positions, d_rows, s);
         ws->tags.rows.resize(n + 1);
         HIP_CHECK(hipMemcpyAsync(ws->tags.rows.data(), d_rows, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));

@@ -7,6 +7,7 @@
 
 #include "capi_internal.hpp"
 #include "gfa_host.hpp"
+#include "scan.hpp"
 #include "topology.hpp"
 
 using namespace gbwt_hip;
@@ -28,19 +29,10 @@ GraphTables graph_tables(const gbwt_hip_index *ix, bool with_labels) {
     return t;
 }
 
-// one u64 from the device, behind everything the stream holds
-uint64_t read_word(const uint64_t *d_word, hipStream_t s) {
-    uint64_t v = 0;
-    HIP_CHECK(hipMemcpyAsync(&v, d_word, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return v;
-}
-
 void scan(gbwt_hip_workspace *ws, const uint64_t *d_lengths, uint64_t *d_offsets, uint64_t n, hipStream_t s) {
-    const size_t temp = std::max<size_t>(scan_temp_bytes(std::max<uint64_t>(n, 1)), 16);
+    const size_t temp = scan_temp_bytes(n, ws->knobs.scan_piece);
     ws->scratch.scan_temp.reserve(temp);
-    if (n) launch_scan(d_lengths, d_offsets, n, ws->scratch.scan_temp.ptr, temp, s);
-    else HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), s));
+    launch_scan(d_lengths, d_offsets, n, ws->scratch.scan_temp.ptr, temp, s, ws->knobs.scan_piece);
 }
 
 const char *const NEEDS_GFA = "segments, links and graph lines need a GBZ opened with GBWT_HIP_OPEN_GFA";
@@ -87,7 +79,7 @@ gbwt_hip_status rows_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, c
         launch_edge_count(ix->dev, ws->edges.ids.as<uint64_t>(), ws->edges.orient.as<uint8_t>(), n, predecessors != 0, ws->edges.counts.as<uint64_t>(), ws->edges.valid.as<uint8_t>(), s);
         scan(ws, ws->edges.counts.as<uint64_t>(), ws->edges.off.as<uint64_t>(), n, s);
         HIP_CHECK(hipGetLastError());
-        uint64_t total = read_word(ws->edges.off.as<uint64_t>() + n, s);
+        uint64_t total = read_value(ws->edges.off.as<uint64_t>() + n, s);
         ws->edges.edges.reserve(std::max<uint64_t>(total, 1) * sizeof(uint64_t));
         if (links) ws->edges.rows.reserve(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
         launch_edge_fill(ix->dev, ws->edges.ids.as<uint64_t>(), ws->edges.orient.as<uint8_t>(), n, predecessors != 0, ws->edges.off.as<uint64_t>(), ws->edges.edges.as<uint64_t>(),
@@ -98,7 +90,7 @@ gbwt_hip_status rows_compute(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, c
             launch_link_cut(tables, ws->edges.off.as<uint64_t>(), ws->edges.edges.as<uint64_t>(), ws->edges.rows.as<uint32_t>(), n, total, ws->edges.cut.as<uint64_t>(), s);
             scan(ws, ws->edges.cut.as<uint64_t>(), ws->edges.loff.as<uint64_t>(), n, s);
             HIP_CHECK(hipGetLastError());
-            const uint64_t kept = read_word(ws->edges.loff.as<uint64_t>() + n, s);
+            const uint64_t kept = read_value(ws->edges.loff.as<uint64_t>() + n, s);
             ws->edges.links.reserve(std::max<uint64_t>(kept, 1) * sizeof(uint64_t));
             launch_link_write(tables, ws->edges.off.as<uint64_t>(), ws->edges.edges.as<uint64_t>(), ws->edges.rows.as<uint32_t>(), total, ws->edges.cut.as<uint64_t>(),
                               ws->edges.loff.as<uint64_t>(), ws->edges.links.as<uint64_t>(), s);
@@ -170,7 +162,7 @@ void graph_lines_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const Gr
     else launch_node_flags(ix->dev, g, flags.as<uint64_t>(), s);
     scan(ws, flags.as<uint64_t>(), rank.as<uint64_t>(), domain, s);
     HIP_CHECK(hipGetLastError());
-    const uint64_t items = read_word(rank.as<uint64_t>() + domain, s);
+    const uint64_t items = read_value(rank.as<uint64_t>() + domain, s);
     ws->graph_text.items.reserve(std::max<uint64_t>(items, 1) * sizeof(uint64_t));
     ws->graph_text.soff.reserve((items + 1) * sizeof(uint64_t));
     sizes.reserve(std::max<uint64_t>(items, 1) * sizeof(uint64_t));
@@ -189,8 +181,8 @@ void graph_lines_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const Gr
     launch_edge_count(ix->dev, ids.as<uint64_t>(), orient.as<uint8_t>(), queries, false, counts.as<uint64_t>(), valid.as<uint8_t>(), s);
     scan(ws, counts.as<uint64_t>(), off.as<uint64_t>(), queries, s);
     HIP_CHECK(hipGetLastError());
-    const uint64_t sbytes = read_word(ws->graph_text.soff.as<uint64_t>() + items, s);
-    const uint64_t edges = read_word(off.as<uint64_t>() + queries, s);
+    const uint64_t sbytes = read_value(ws->graph_text.soff.as<uint64_t>() + items, s);
+    const uint64_t edges = read_value(off.as<uint64_t>() + queries, s);
     ws->graph_text.edges.reserve(std::max<uint64_t>(edges, 1) * sizeof(uint64_t));
     ws->graph_text.rows.reserve(std::max<uint64_t>(edges, 1) * sizeof(uint32_t));
     ws->graph_text.loff.reserve((edges + 1) * sizeof(uint64_t));
@@ -208,8 +200,8 @@ void graph_lines_size(const gbwt_hip_index *ix, gbwt_hip_workspace *ws, const Gr
                            sizes.as<uint64_t>(), lines.as<uint64_t>(), s);
     scan(ws, sizes.as<uint64_t>(), ws->graph_text.loff.as<uint64_t>(), edges, s);
     HIP_CHECK(hipGetLastError());
-    ws->graph_text.lbytes = read_word(ws->graph_text.loff.as<uint64_t>() + edges, s);
-    ws->graph_text.links = read_word(lines.as<uint64_t>(), s);
+    ws->graph_text.lbytes = read_value(ws->graph_text.loff.as<uint64_t>() + edges, s);
+    ws->graph_text.links = read_value(lines.as<uint64_t>(), s);
     ws->graph_text.item_count = items; ws->graph_text.edge_count = edges; ws->graph_text.sbytes = sbytes; ws->graph_text.translated = translated;
     ws->graph_text.sized = true;                                   // (the scratch buffers go here: hipFree waits for the stream)
 }
@@ -272,14 +264,14 @@ gbwt_hip_status gbwt_hip_node_ids(const gbwt_hip_index *ix, uint64_t *out, uint6
         const ComponentGeometry g = graph_geometry(ix->dev);
         if (g.slots == 0) return GBWT_HIP_OK;
         DeviceBuffer flags, rank, temp, ids;
-        const size_t temp_bytes = std::max<size_t>(scan_temp_bytes(g.slots), 16);
+        const size_t temp_bytes = scan_temp_bytes(g.slots);
         flags.reserve(g.slots * sizeof(uint64_t));
         rank.reserve((g.slots + 1) * sizeof(uint64_t));
         temp.reserve(temp_bytes);
         launch_node_flags(ix->dev, g, flags.as<uint64_t>(), nullptr);
         launch_scan(flags.as<uint64_t>(), rank.as<uint64_t>(), g.slots, temp.ptr, temp_bytes, nullptr);
         HIP_CHECK(hipGetLastError());
-        *total = read_word(rank.as<uint64_t>() + g.slots, nullptr);
+        *total = read_value(rank.as<uint64_t>() + g.slots, nullptr);
         if (!out) return GBWT_HIP_OK;
         if (capacity < *total) return fail(GBWT_HIP_CAPACITY, "output capacity too small for the node ids");
         if (*total == 0) return GBWT_HIP_OK;

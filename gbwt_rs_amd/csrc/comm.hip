@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "scan.hpp"
 
 using namespace gbwt_hip;
 
@@ -272,8 +273,8 @@ gbwt_hip_status gather(gbwt_hip_comm *c, const uint64_t *d_lengths, uint64_t n, 
             if (units) HIP_CHECK(hipMemcpyAsync(part_at(rank), d_payload, units * unit, hipMemcpyDeviceToDevice, s));
         }
         // 3. path order
-        const size_t tb = scan_temp_bytes(std::max<uint64_t>(total_rows, 1));
-        c->scan_temp.reserve(std::max<size_t>(tb, 16));
+        const size_t tb = scan_temp_bytes(total_rows);
+        c->scan_temp.reserve(tb);
         std::vector<uint64_t> start_first(world + 1, 0);              // (interleaved) part r's scan of its lengths has rows + 1 entries
         if (in_place) {
             launch_scan(d_part_len, c->offsets.as<uint64_t>(), total_rows, c->scan_temp.ptr, tb, s);

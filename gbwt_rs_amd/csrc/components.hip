@@ -23,6 +23,7 @@
 
 #include <algorithm>
 
+#include "device_common.hpp"
 #include "kernels.hpp"
 #include "lf_device.hpp"
 
@@ -30,7 +31,6 @@ namespace gbwt_hip {
 
 namespace {
 
-inline unsigned blocks_for(uint64_t n) { return static_cast<unsigned>((n + 255) / 256); }
 
 // slot of a GBWT node inside the alphabet, or COMPONENT_NONE outside it
 __device__ __forceinline__ uint32_t slot_of(const DeviceIndex &ix, const ComponentGeometry &g, uint64_t node) {

@@ -20,6 +20,7 @@ struct ExtractKnobs {
     uint32_t debug = 0;                                       // GBWT_HIP_DEBUG_DRY_ROWS (measurement switches, WalkArgs::debug)
     unsigned copy_threads = 8;                                // GBWT_HIP_COPY_THREADS
     uint64_t locate_sort_piece = 0x7FFFFFFFull;               // GBWT_HIP_LOCATE_SORT_PIECE: items of one radix sort of a unique locate request (hipcub counts in int; tests lower it)
+    uint64_t scan_piece = uint64_t(1) << 30;                  // GBWT_HIP_SCAN_PIECE: items of one launch of a prefix sum (scan.hpp: SCAN_PIECE; 1024 .. 2^30, tests lower it)
     // GBWT_HIP_WALK_MODE (0-3) / _PATHS_PER_WAVE (0-64; 0 = automatic) / _SMALL_RECORD: what gbwt_hip_workspace_tune sets, and overwrites
     uint32_t walk_mode = 0, paths_per_wave = 0, small_record = 16;
     static ExtractKnobs from_env() {
@@ -41,6 +42,7 @@ struct ExtractKnobs {
         k.debug = static_cast<uint32_t>(num("GBWT_HIP_DEBUG_DRY_ROWS", 0));
         k.copy_threads = static_cast<unsigned>(std::min(64, std::max(1, num("GBWT_HIP_COPY_THREADS", 8))));
         k.locate_sort_piece = static_cast<uint64_t>(std::max(1, num("GBWT_HIP_LOCATE_SORT_PIECE", 0x7FFFFFFF)));
+        if (const char *v = std::getenv("GBWT_HIP_SCAN_PIECE")) k.scan_piece = std::min<uint64_t>(uint64_t(1) << 30, std::max<uint64_t>(1024, std::strtoull(v, nullptr, 10)));
         if (const int m = num("GBWT_HIP_WALK_MODE", -1); m >= 0 && m <= 3) k.walk_mode = static_cast<uint32_t>(m);
         if (const int p = num("GBWT_HIP_PATHS_PER_WAVE", -1); p >= 0 && p <= 64) k.paths_per_wave = static_cast<uint32_t>(p);
         if (const char *v = std::getenv("GBWT_HIP_SMALL_RECORD")) { const long r = std::atol(v); if (r >= 0) k.small_record = static_cast<uint32_t>(r); }

@@ -16,6 +16,7 @@
 
 #include "device_common.hpp"
 #include "fm_index.hpp"
+#include "scan.hpp"
 
 namespace gbwt_hip {
 
@@ -24,7 +25,6 @@ namespace {
 constexpr unsigned THREADS = 256;
 constexpr unsigned WAVE = 64;
 
-dim3 blocks_for(uint64_t items) { return dim3(grid_for(items, THREADS)); }
 
 __global__ void __launch_bounds__(THREADS) k_fm_histogram(const uint8_t *__restrict__ text, uint64_t n, uint64_t *__restrict__ hist) {
     __shared__ uint32_t bins[256];
@@ -119,12 +119,6 @@ __global__ void __launch_bounds__(THREADS) k_fm_count(FmLayout L, FmTables t, co
     if (threadIdx.x == 0 && block_steps) atomicAdd(reinterpret_cast<unsigned long long *>(words + 1), block_steps);
 }
 
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int lane) {
-    const uint32_t lo = static_cast<uint32_t>(__shfl(static_cast<int>(static_cast<uint32_t>(v)), lane, WAVE));
-    const uint32_t hi = static_cast<uint32_t>(__shfl(static_cast<int>(static_cast<uint32_t>(v >> 32)), lane, WAVE));
-    return (uint64_t(hi) << 32) | lo;
-}
-
 // A wave takes 64 rows: a lane copies its own row where it is short, and the wave copies the long ones together, 64 positions at a time
 __global__ void __launch_bounds__(THREADS) k_fm_locate_fill(const uint32_t *__restrict__ sa32, const uint64_t *__restrict__ ranges, const uint64_t *__restrict__ row_offsets, uint64_t m,
                                                             uint64_t *__restrict__ positions, uint32_t *__restrict__ rows) {
@@ -183,7 +177,6 @@ void launch_fm_block_counts(const uint8_t *d_lines, uint64_t rows, uint64_t bloc
 }
 
 namespace {
-constexpr uint64_t SCAN_PIECE = uint64_t(1) << 30;       // items of one scan (an int counts them)
 uint64_t codes_per_piece(uint64_t blocks) { return std::max<uint64_t>(1, SCAN_PIECE / blocks); }
 }  // namespace
 

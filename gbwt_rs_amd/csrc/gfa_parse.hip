@@ -31,6 +31,7 @@
 
 #include "build.hpp"
 #include "capi_internal.hpp"
+#include "device_common.hpp"
 #include "gfa_names.hpp"
 #include "gfa_parse.hpp"
 
@@ -74,27 +75,6 @@ __device__ __forceinline__ uint32_t wave_exclusive(uint32_t v, uint32_t &total) 
     }
     total = __shfl(x, 63, 64);
     return x - v;
-}
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int lane) {
-    const uint32_t lo = __shfl(static_cast<uint32_t>(v), lane, 64), hi = __shfl(static_cast<uint32_t>(v >> 32), lane, 64);
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-// first index with a[i] >= x
-__device__ __forceinline__ uint64_t lower_bound(const uint64_t *a, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-// first index with a[i] > x
-__device__ __forceinline__ uint64_t upper_bound(const uint64_t *a, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 __device__ __forceinline__ uint4 load_tile(const uint8_t *text, uint64_t tile) {
@@ -597,42 +577,19 @@ __global__ __launch_bounds__(THREADS) void k_gfa_copy_labels(const uint8_t *__re
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 
-struct Tally { size_t now = 0, peak = 0; };
-struct Buf {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    Tally *owner = nullptr;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-    void alloc(Tally &t, size_t need, bool counted = true) {
-        release();
-        const size_t want = std::max<size_t>(need, 256);
-        HIP_CHECK(hipMalloc(&ptr, want));
-        bytes = want;
-        if (counted) { owner = &t; t.now += want; t.peak = std::max(t.peak, t.now); }
-    }
-    void release() noexcept {
-        if (!ptr) return;
-        (void)hipFree(ptr);
-        if (owner) owner->now -= bytes;
-        ptr = nullptr; bytes = 0; owner = nullptr;
-    }
-    template <class T> T *as() const { return static_cast<T *>(ptr); }
-};
+using Tally = CountedScratch;
+using Buf = CountedBuf;
 
 using Event = EventSet<1>;
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return static_cast<unsigned>(std::max<uint64_t>(1, (items + per_block - 1) / per_block)); }
+// (at least one block: a launch over no items is a launch of idle lanes, not an error)
+inline unsigned blocks_or_one(uint64_t items, uint64_t per_block) { return static_cast<unsigned>(std::max<uint64_t>(1, (items + per_block - 1) / per_block)); }
 
+// exclusive_sum in place, with a temp of its own that is gone when it returns
 template <class T>
 void exclusive_sum(Tally &tally, T *data, uint64_t n, hipStream_t s) {
-    size_t bytes = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, data, data, static_cast<int>(n), s));
     Buf temp;
-    temp.alloc(tally, bytes);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp.ptr, bytes, data, data, static_cast<int>(n), s));
+    exclusive_sum(data, data, n, tally, temp, s);
     HIP_CHECK(hipStreamSynchronize(s));       // (temp goes)
 }
 
@@ -641,9 +598,9 @@ void exclusive_sum(Tally &tally, T *data, uint64_t n, hipStream_t s) {
 struct GfaDeviceParse::Impl {
     hipStream_t s = nullptr;
     uint64_t len = 0, tiles = 0, lines = 0, tabs = 0, max_id = 0;
-    Tally tally;
+    Tally tally, rows_tally;      // rows_tally: the rows, which nobody reports
     Buf text, tile_nl, tile_tab, nl_pos, tab_pos, kind, first_tab, lo, hi, id, rank_h, rank_s, rank_p, rank_w, words, seg_id, seg_line, present, visited, tile_p, tile_w;
-    Buf offsets, nodes;                       // the rows: the caller's, not counted
+    Buf offsets, nodes;                       // the rows: the caller's, counted apart (rows_tally)
     // a translated parse
     GfaParseOptions options;
     Buf name_lo, name_len, hash, rank, bucket, seg_start;
@@ -689,13 +646,13 @@ void GfaDeviceParse::rows() {
     m.words.alloc(m.tally, (CNT_WORDS + 1) * sizeof(u64));
     HIP_CHECK(hipMemsetAsync(m.words.ptr, 0, CNT_WORDS * sizeof(u64), s));
     HIP_CHECK(hipMemsetAsync(m.err(), 0xFF, sizeof(u64), s));
-    m.offsets.alloc(m.tally, sizeof(uint64_t), false);
+    m.offsets.alloc(m.rows_tally, sizeof(uint64_t));
     HIP_CHECK(hipMemsetAsync(m.offsets.ptr, 0, sizeof(uint64_t), s));
     HIP_CHECK(hipEventRecord(e0[0], s));
     if (m.tiles == 0) { HIP_CHECK(hipStreamSynchronize(s)); peak_bytes = m.tally.peak; return; }
 
     // -- structure
-    const unsigned tile_blocks = blocks_for(m.tiles, WAVES);
+    const unsigned tile_blocks = blocks_or_one(m.tiles, WAVES);
     m.tile_nl.alloc(m.tally, (m.tiles + 1) * sizeof(uint64_t));
     m.tile_tab.alloc(m.tally, (m.tiles + 1) * sizeof(uint64_t));
     HIP_CHECK(hipMemsetAsync(m.tile_nl.as<uint64_t>() + m.tiles, 0, sizeof(uint64_t), s));
@@ -721,7 +678,7 @@ void GfaDeviceParse::rows() {
     for (Buf *r : {&m.rank_h, &m.rank_s, &m.rank_p, &m.rank_w}) r->alloc(m.tally, L * sizeof(uint32_t));
     m.tables = LineTables{m.kind.as<uint8_t>(), m.first_tab.as<uint64_t>(), m.lo.as<uint64_t>(), m.hi.as<uint64_t>(), m.id.as<uint32_t>(),
                           m.rank_h.as<uint32_t>(), m.rank_s.as<uint32_t>(), m.rank_p.as<uint32_t>(), m.rank_w.as<uint32_t>()};
-    const unsigned line_blocks = blocks_for(L, THREADS);
+    const unsigned line_blocks = blocks_or_one(L, THREADS);
     hipLaunchKernelGGL(k_gfa_lines, dim3(line_blocks), dim3(THREADS), 0, s, text, m.nl_pos.as<uint64_t>(), L, m.tab_pos.as<uint64_t>(), m.tabs, m.tables, by_name ? 1u : 0u, m.counters(), m.err());
     HIP_CHECK(hipGetLastError());
     for (Buf *r : {&m.rank_h, &m.rank_s, &m.rank_p, &m.rank_w}) exclusive_sum(m.tally, r->as<uint32_t>(), L, s);
@@ -771,8 +728,8 @@ void GfaDeviceParse::rows() {
     if (translated) {
         m.translated_rows(steps_p, e_names0, e_names1, e_expand0, e_expand1, *this);
     } else {
-        m.offsets.alloc(m.tally, (n_paths + 1) * sizeof(uint64_t), false);
-        m.nodes.alloc(m.tally, counts.steps * sizeof(uint32_t), false);
+        m.offsets.alloc(m.rows_tally, (n_paths + 1) * sizeof(uint64_t));
+        m.nodes.alloc(m.rows_tally, counts.steps * sizeof(uint32_t));
         HIP_CHECK(hipMemcpyAsync(m.offsets.as<uint64_t>() + n_paths, &counts.steps, sizeof(uint64_t), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_gfa_fill_steps, dim3(tile_blocks), dim3(THREADS), 0, s, text, m.tiles, m.tile_nl.as<uint64_t>(), L, m.tables, m.tile_p.as<uint64_t>(), m.tile_w.as<uint64_t>(),
                            counts.p_lines, steps_p, m.present.as<uint32_t>(), m.max_id, m.visited.as<uint32_t>(), m.offsets.as<uint64_t>(), m.nodes.as<uint32_t>(), m.err());
@@ -790,7 +747,7 @@ void GfaDeviceParse::rows() {
             HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, m.seg_id.as<uint32_t>(), keys.as<uint32_t>(), vals_in.as<uint32_t>(), vals.as<uint32_t>(), static_cast<int>(S), 0, 31, s));
             temp.alloc(m.tally, bytes);
             HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp.ptr, bytes, m.seg_id.as<uint32_t>(), keys.as<uint32_t>(), vals_in.as<uint32_t>(), vals.as<uint32_t>(), static_cast<int>(S), 0, 31, s));
-            hipLaunchKernelGGL(k_gfa_duplicates, dim3(blocks_for(S, THREADS)), dim3(THREADS), 0, s, keys.as<uint32_t>(), vals.as<uint32_t>(), m.seg_line.as<uint32_t>(), S, m.err());
+            hipLaunchKernelGGL(k_gfa_duplicates, dim3(blocks_or_one(S, THREADS)), dim3(THREADS), 0, s, keys.as<uint32_t>(), vals.as<uint32_t>(), m.seg_line.as<uint32_t>(), S, m.err());
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipStreamSynchronize(s));
         }
@@ -821,7 +778,7 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
     Impl &m = *this;
     const uint8_t *txt = m.text.as<uint8_t>();
     const uint64_t S = out.counts.segments, T = out.counts.steps, n_paths = out.n_paths, L = m.lines;
-    const unsigned tile_blocks = blocks_for(m.tiles, WAVES);
+    const unsigned tile_blocks = blocks_or_one(m.tiles, WAVES);
     if (T + 1 > GFA_MAX_LINES) throw Unsupported("more than 2^31 - 2 steps are not supported");
 
     // -- names: the plan of the segments and the table of their names
@@ -835,7 +792,7 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
     m.bucket.alloc(m.tally, buckets * sizeof(uint32_t));
     m.seg_start.alloc(m.tally, (S + 1) * sizeof(uint64_t));
     HIP_CHECK(hipMemsetAsync(m.seg_start.as<uint64_t>() + S, 0, sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_gfa_segment_plan, dim3(blocks_for(S, THREADS)), dim3(THREADS), 0, s, txt, m.tab_pos.as<uint64_t>(), m.tables, m.seg_line.as<uint32_t>(), S, m.options.max_node_length,
+    hipLaunchKernelGGL(k_gfa_segment_plan, dim3(blocks_or_one(S, THREADS)), dim3(THREADS), 0, s, txt, m.tab_pos.as<uint64_t>(), m.tables, m.seg_line.as<uint32_t>(), S, m.options.max_node_length,
                        m.name_lo.as<uint64_t>(), m.name_len.as<uint32_t>(), hash_in.as<uint64_t>(), rank_in.as<uint32_t>(), m.seg_start.as<uint64_t>(), m.counters());
     HIP_CHECK(hipGetLastError());
     exclusive_sum(m.tally, m.seg_start.as<uint64_t>(), S + 1, s);
@@ -850,9 +807,9 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
     }
     hash_in.release(); rank_in.release();
     m.names = GfaNameTable{txt, m.name_lo.as<uint64_t>(), m.name_len.as<uint32_t>(), m.hash.as<uint64_t>(), m.rank.as<uint32_t>(), m.bucket.as<uint32_t>(), bits, static_cast<uint32_t>(S)};
-    hipLaunchKernelGGL(k_gfa_name_duplicates, dim3(blocks_for(S, THREADS)), dim3(THREADS), 0, s, m.names, m.seg_line.as<uint32_t>(), m.err());
+    hipLaunchKernelGGL(k_gfa_name_duplicates, dim3(blocks_or_one(S, THREADS)), dim3(THREADS), 0, s, m.names, m.seg_line.as<uint32_t>(), m.err());
     HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_gfa_name_buckets, dim3(blocks_for(buckets, THREADS)), dim3(THREADS), 0, s, m.hash.as<uint64_t>(), S, bits, m.bucket.as<uint32_t>());
+    hipLaunchKernelGGL(k_gfa_name_buckets, dim3(blocks_or_one(buckets, THREADS)), dim3(THREADS), 0, s, m.hash.as<uint64_t>(), S, bits, m.bucket.as<uint32_t>());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(e_names1[0], s));
     out.table_bytes = S * (2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) + buckets * sizeof(uint32_t);
@@ -877,17 +834,17 @@ void GfaDeviceParse::Impl::translated_rows(uint64_t steps_p, Event &e_names0, Ev
     // -- expand: every step becomes the nodes of its segment
     HIP_CHECK(hipEventRecord(e_expand0[0], s));
     out.row_nodes = 0;
-    m.offsets.alloc(m.tally, (n_paths + 1) * sizeof(uint64_t), false);
+    m.offsets.alloc(m.rows_tally, (n_paths + 1) * sizeof(uint64_t));
     if (word == ~u64(0)) {
         if (out.total_nodes > 0x7FFFFFFFull) throw Unsupported(std::to_string(out.total_nodes) + " nodes after chopping: more than 2^31 - 1 are not supported");
         exclusive_sum(m.tally, node_off.as<uint64_t>(), T + 1, s);
         HIP_CHECK(hipMemcpy(&out.row_nodes, node_off.as<uint64_t>() + T, sizeof(uint64_t), hipMemcpyDeviceToHost));
         if (out.row_nodes > BUILD_MAX_SLOTS) throw Unsupported(std::to_string(out.row_nodes) + " visits: more than 2^32 - 1 are not supported (u32 positions on device)");
-        m.nodes.alloc(m.tally, out.row_nodes * sizeof(uint32_t), false);
-        hipLaunchKernelGGL(k_gfa_path_offsets, dim3(blocks_for(n_paths + 1, THREADS)), dim3(THREADS), 0, s, step_off.as<uint64_t>(), node_off.as<uint64_t>(), n_paths, m.offsets.as<uint64_t>());
+        m.nodes.alloc(m.rows_tally, out.row_nodes * sizeof(uint32_t));
+        hipLaunchKernelGGL(k_gfa_path_offsets, dim3(blocks_or_one(n_paths + 1, THREADS)), dim3(THREADS), 0, s, step_off.as<uint64_t>(), node_off.as<uint64_t>(), n_paths, m.offsets.as<uint64_t>());
         HIP_CHECK(hipGetLastError());
         if (out.row_nodes) {
-            hipLaunchKernelGGL(k_gfa_expand_steps, dim3(blocks_for(out.row_nodes, THREADS)), dim3(THREADS), 0, s, node_off.as<uint64_t>(), step_seg.as<uint32_t>(), T, m.seg_start.as<uint64_t>(),
+            hipLaunchKernelGGL(k_gfa_expand_steps, dim3(blocks_or_one(out.row_nodes, THREADS)), dim3(THREADS), 0, s, node_off.as<uint64_t>(), step_seg.as<uint32_t>(), T, m.seg_start.as<uint64_t>(),
                                out.row_nodes, m.nodes.as<uint32_t>());
             HIP_CHECK(hipGetLastError());
         }
@@ -911,10 +868,10 @@ void GfaDeviceParse::labels(Strings &out, uint64_t &graph_nodes) {
     HIP_CHECK(hipMemsetAsync(slot_off.ptr, 0, (slots + 1) * sizeof(uint64_t), s));
     HIP_CHECK(hipMemsetAsync(slot_src.ptr, 0, slots * sizeof(uint64_t), s));
     if (translated)
-        hipLaunchKernelGGL(k_gfa_node_slots, dim3(blocks_for(slots, THREADS)), dim3(THREADS), 0, s, m.seg_start.as<uint64_t>(), m.seg_line.as<uint32_t>(), S, m.visited.as<uint32_t>(), m.tables,
+        hipLaunchKernelGGL(k_gfa_node_slots, dim3(blocks_or_one(slots, THREADS)), dim3(THREADS), 0, s, m.seg_start.as<uint64_t>(), m.seg_line.as<uint32_t>(), S, m.visited.as<uint32_t>(), m.tables,
                            m.options.max_node_length, slots, slot_off.as<uint64_t>(), slot_src.as<uint64_t>(), m.counters());
     else
-        hipLaunchKernelGGL(k_gfa_label_slots, dim3(blocks_for(S, THREADS)), dim3(THREADS), 0, s, m.seg_id.as<uint32_t>(), m.seg_line.as<uint32_t>(), S, m.visited.as<uint32_t>(), m.tables,
+        hipLaunchKernelGGL(k_gfa_label_slots, dim3(blocks_or_one(S, THREADS)), dim3(THREADS), 0, s, m.seg_id.as<uint32_t>(), m.seg_line.as<uint32_t>(), S, m.visited.as<uint32_t>(), m.tables,
                            min_id, slots, slot_off.as<uint64_t>(), slot_src.as<uint64_t>(), m.counters());
     HIP_CHECK(hipGetLastError());
     exclusive_sum(m.tally, slot_off.as<uint64_t>(), slots + 1, s);
@@ -923,7 +880,7 @@ void GfaDeviceParse::labels(Strings &out, uint64_t &graph_nodes) {
     const size_t padded = (static_cast<size_t>(total) + 15) / 16 * 16;
     bytes.alloc(m.tally, padded);
     if (total) {
-        hipLaunchKernelGGL(k_gfa_copy_labels, dim3(blocks_for(padded / 16, THREADS)), dim3(THREADS), 0, s, m.text.as<uint8_t>(), slot_off.as<uint64_t>(), slot_src.as<uint64_t>(), slots, total,
+        hipLaunchKernelGGL(k_gfa_copy_labels, dim3(blocks_or_one(padded / 16, THREADS)), dim3(THREADS), 0, s, m.text.as<uint8_t>(), slot_off.as<uint64_t>(), slot_src.as<uint64_t>(), slots, total,
                            bytes.as<uint8_t>());
         HIP_CHECK(hipGetLastError());
     }
@@ -949,7 +906,7 @@ void GfaDeviceParse::translation(GfaTranslation &out) {
     Buf slot_off, slot_src, bytes;
     slot_off.alloc(m.tally, (S + 1) * sizeof(uint64_t)); slot_src.alloc(m.tally, S * sizeof(uint64_t));
     HIP_CHECK(hipMemsetAsync(slot_off.as<uint64_t>() + S, 0, sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_gfa_name_slots, dim3(blocks_for(S, THREADS)), dim3(THREADS), 0, s, m.name_lo.as<uint64_t>(), m.name_len.as<uint32_t>(), S, m.visited.as<uint32_t>(),
+    hipLaunchKernelGGL(k_gfa_name_slots, dim3(blocks_or_one(S, THREADS)), dim3(THREADS), 0, s, m.name_lo.as<uint64_t>(), m.name_len.as<uint32_t>(), S, m.visited.as<uint32_t>(),
                        slot_off.as<uint64_t>(), slot_src.as<uint64_t>());
     HIP_CHECK(hipGetLastError());
     exclusive_sum(m.tally, slot_off.as<uint64_t>(), S + 1, s);
@@ -958,7 +915,7 @@ void GfaDeviceParse::translation(GfaTranslation &out) {
     const size_t padded = (static_cast<size_t>(total) + 15) / 16 * 16;
     bytes.alloc(m.tally, padded);
     if (total) {
-        hipLaunchKernelGGL(k_gfa_copy_labels, dim3(blocks_for(padded / 16, THREADS)), dim3(THREADS), 0, s, m.text.as<uint8_t>(), slot_off.as<uint64_t>(), slot_src.as<uint64_t>(), S, total,
+        hipLaunchKernelGGL(k_gfa_copy_labels, dim3(blocks_or_one(padded / 16, THREADS)), dim3(THREADS), 0, s, m.text.as<uint8_t>(), slot_off.as<uint64_t>(), slot_src.as<uint64_t>(), S, total,
                            bytes.as<uint8_t>());
         HIP_CHECK(hipGetLastError());
     }

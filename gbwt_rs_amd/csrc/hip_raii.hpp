@@ -49,6 +49,14 @@ struct PinnedWords {
     PinnedWords &operator=(const PinnedWords &) = delete;
 };
 
+// one value from the device, behind everything the stream holds
+template <class T> T read_value(const T *d, hipStream_t s) {
+    T v{};
+    HIP_CHECK(hipMemcpyAsync(&v, d, sizeof(T), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return v;
+}
+
 struct Workspace {
     gbwt_hip_workspace *ws = nullptr;
     Workspace() = default;

@@ -18,12 +18,10 @@ constexpr uint32_t FLAG_POOL_OVERFLOW = 1u;
 // ---- load-time passes -------------------------------------------------------------------------
 // per-record descriptors + rank blocks (device_index.hpp): d_desc has 4 * n_records entries; build_desc also
 // writes the number of rank blocks of every record and the statistics of the index (d_stats, zeroed by the caller: [0] = max
-// Record::len, [1] = max outdegree, [2] = number of malformed records, [3] = all BWT positions); block_scan + finish_block_base turn
+// Record::len, [1] = max outdegree, [2] = number of malformed records, [3] = all BWT positions); block_scan (scan.hpp) + finish_block_base turn
 // the counts into first-block indices (BLOCK_NONE where there are none; block 0 is the shared zero block), fill_blocks decodes
 // the outdegree-2 records into their blocks, link_desc stores the successors' block bases into the descriptors.
 void launch_build_desc(const DeviceIndex &ix, uint4 *d_desc, uint32_t *d_block_counts, uint64_t *d_stats, hipStream_t stream);
-size_t block_scan_temp_bytes(uint64_t n);
-void launch_block_scan(const uint32_t *d_counts, uint32_t *d_block_base, uint64_t n, void *d_temp, size_t temp_bytes, hipStream_t stream);
 void launch_finish_block_base(const uint32_t *d_counts, uint32_t *d_block_base, uint64_t n, uint4 *d_desc_raw /* class 2 records also get their block base in C.z */, hipStream_t stream);
 void launch_link_desc(const DeviceIndex &ix, uint4 *d_desc, hipStream_t stream);
 void launch_link_lookahead(const DeviceIndex &ix, uint4 *d_desc, const uint32_t *d_block_counts, uint32_t hops, hipStream_t stream);
@@ -219,10 +217,6 @@ void launch_component_counts(const ComponentGeometry &g, const uint32_t *d_compo
 void launch_component_csr(const ComponentGeometry &g, const ComponentShape &w, uint64_t components, uint32_t *d_nodes, hipStream_t s);
 // d_out[p] = component of the first node of path p (sequence p * stride; COMPONENT_NONE for an empty path)
 void launch_path_components(const DeviceIndex &ix, const ComponentGeometry &g, const uint32_t *d_component, uint64_t paths, uint32_t stride, uint32_t *d_out, hipStream_t s);
-
-// inclusive scan of lengths[n] into offsets[1..n], offsets[0] = 0 (hipcub); temp storage managed by caller
-size_t scan_temp_bytes(uint64_t n);
-void launch_scan(const uint64_t *d_lengths, uint64_t *d_offsets, uint64_t n, void *d_temp, size_t temp_bytes, hipStream_t s);
 
 // ---- locate (locate.hip) ------------------------------------------------------------------------
 // The locate index of a handle as the kernels see it.  rec_base[r] = slot of offset 0 of record r in `table` when r is SAMPLED, LOCATE_NONE

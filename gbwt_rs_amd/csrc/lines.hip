@@ -11,6 +11,7 @@
 // path of a GBZ built from a GFA -- is recognised and formatted here (a position is a token iff it is the first node of its segment in the
 // orientation of travel, and every other position must continue its predecessor).  A path that is not is flagged and left to the host.
 #include "lines.hpp"
+#include "scan.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -405,9 +406,9 @@ __global__ void __launch_bounds__(FORMAT_THREADS) k_segment_fill_tokens(const ui
 }  // namespace
 
 void launch_chunk_plan(const uint64_t *d_offsets, uint64_t n, uint64_t chunks_cap, uint64_t *d_chunk_counts, uint64_t *d_chunk_first, uint32_t *d_chunk_path, void *d_temp,
-                       size_t temp_bytes, hipStream_t s) {
+                       size_t temp_bytes, hipStream_t s, uint64_t scan_piece) {
     hipLaunchKernelGGL(k_chunk_counts, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, d_offsets, n, d_chunk_counts);
-    launch_scan(d_chunk_counts, d_chunk_first, n, d_temp, temp_bytes, s);
+    launch_scan(d_chunk_counts, d_chunk_first, n, d_temp, temp_bytes, s, scan_piece);
     hipLaunchKernelGGL(k_chunk_paths, dim3(static_cast<unsigned>((chunks_cap + 255) / 256)), dim3(256), 0, s, d_chunk_first, n, chunks_cap, d_chunk_path);
 }
 

@@ -66,7 +66,7 @@ struct ChunkedRows {
 // The chunk plan of a batch of rows, for the lines and for other passes over rows (the bases of sequences.hip): first chunk of every row
 // (d_chunk_first[n + 1], d_chunk_counts[n] scratch) and the row of every chunk (d_chunk_path[chunks_cap]).
 void launch_chunk_plan(const uint64_t *d_offsets, uint64_t n, uint64_t chunks_cap, uint64_t *d_chunk_counts, uint64_t *d_chunk_first, uint32_t *d_chunk_path, void *d_temp,
-                       size_t temp_bytes, hipStream_t s);
+                       size_t temp_bytes, hipStream_t s, uint64_t scan_piece);
 
 // sizing, a wave per chunk: text bytes of the chunk's tokens and its summed label (segment) lengths; with a translation also whether a
 // position of the chunk fits no segment

@@ -2,7 +2,7 @@
 // (hand-written HIP for gfx950, no MFMA: integer pointer-chasing over a byte stream).  Launch wrappers are declared in kernels.hpp.
 #include "kernels.hpp"
 
-#include <hipcub/hipcub.hpp>
+#include <algorithm>
 
 #include "device_common.hpp"
 #include "lf_device.hpp"
@@ -757,17 +757,6 @@ __global__ void __launch_bounds__(256) k_finish_block_base(const uint32_t *count
     if (bb != BLOCK_NONE && desc_raw != nullptr) reinterpret_cast<uint32_t *>(desc_raw + 4 * rec + 2)[2] = bb;
 }
 
-size_t block_scan_temp_bytes(uint64_t n) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, static_cast<const uint32_t *>(nullptr), static_cast<uint32_t *>(nullptr), static_cast<int>(n));
-    return bytes;
-}
-
-void launch_block_scan(const uint32_t *d_counts, uint32_t *d_block_base, uint64_t n, void *d_temp, size_t temp_bytes, hipStream_t stream) {
-    if (n == 0) return;
-    (void)hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_counts, d_block_base, static_cast<int>(n), stream);
-}
-
 void launch_finish_block_base(const uint32_t *d_counts, uint32_t *d_block_base, uint64_t n, uint4 *d_desc_raw, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(k_finish_block_base, dim3(grid_for(n, 256)), dim3(256), 0, stream, d_counts, d_block_base, n, d_desc_raw);
 }
@@ -829,19 +818,6 @@ void launch_ef_values(const uint64_t *d_high, uint64_t high_words, const uint64_
 
 void launch_starts_check(const uint32_t *d_starts32, const uint64_t *d_starts64, uint64_t ones, uint32_t *d_flags, hipStream_t s) {
     if (ones) hipLaunchKernelGGL(k_starts_check, dim3(grid_for(ones, 256)), dim3(256), 0, s, d_starts32, d_starts64, ones, d_flags);
-}
-
-size_t scan_temp_bytes(uint64_t n) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, bytes, static_cast<const uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
-                                     static_cast<int>(n));
-    return bytes;
-}
-
-void launch_scan(const uint64_t *d_lengths, uint64_t *d_offsets, uint64_t n, void *d_temp, size_t temp_bytes, hipStream_t s) {
-    (void)hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), s);
-    if (n == 0) return;
-    (void)hipcub::DeviceScan::InclusiveSum(d_temp, temp_bytes, d_lengths, d_offsets + 1, static_cast<int>(n), s);
 }
 
 }  // namespace gbwt_hip

@@ -82,20 +82,14 @@ __global__ void __launch_bounds__(256) k_locate_bases(const uint64_t *__restrict
     if (wave != 0 && (threadIdx.x & (WAVE - 1)) == 0) atomicAdd(reinterpret_cast<unsigned long long *>(sampled), static_cast<unsigned long long>(__popcll(wave)));
 }
 
-// the sequence of lane t < seg_first[n]: the last one that starts at or before t (sequences without lanes start where the next one does)
-__device__ __forceinline__ uint64_t locate_row_of(const uint64_t *offsets, uint64_t n, uint64_t t) {
-    uint64_t lo = 0, hi = n - 1;
-    while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if (offsets[mid] <= t) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 struct LocateBuild { const uint64_t *seg_first; uint64_t walkers, step_limit; uint64_t *counts; uint32_t *flags; uint32_t segmented; };
 
 template <bool FAST>
 __global__ void __launch_bounds__(256) k_locate_build(DeviceIndex ix, LocateIndex L, LocateBuild b) {
     const uint64_t t = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     if (t >= b.walkers) return;
-    const uint64_t id = b.segmented ? locate_row_of(b.seg_first, ix.n_sequences, t) : t, j = b.segmented ? t - b.seg_first[id] : 0u;
+    // the sequence of lane t < seg_first[n]: the last one that starts at or before t (sequences without lanes start where the next one does)
+    const uint64_t id = b.segmented ? last_at_or_before(b.seg_first, ix.n_sequences, t) : t, j = b.segmented ? t - b.seg_first[id] : 0u;
     if (id >= ix.n_sequences || id >= ix.n_endmarker) { atomicOr(b.flags, LOCATE_FLAG_WALK); return; }
     // Nodes [from, to) of the sequence are this lane's (device_index.hpp: row_segments); the LAST lane of a sequence runs to its end, wherever
     // that is.  Pos of node `from`: the endmarker entry (segment 0), or one step from sample j, which is the position of node from - 1.
@@ -192,7 +186,7 @@ template <bool FAST>
 __global__ void __launch_bounds__(256) k_locate(DeviceIndex ix, LocateIndex L, LocateQuery q) {
     const uint64_t t = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     if (t >= q.total) return;
-    const uint64_t row = locate_row_of(q.offsets, q.n, t);
+    const uint64_t row = last_at_or_before(q.offsets, q.n, t);
     const uint64_t node = q.states[row].node, offset = q.states[row].start + (t - q.offsets[row]);
     uint32_t id = 0;
     uint64_t steps = 0;
@@ -230,7 +224,6 @@ __global__ void __launch_bounds__(256) k_locate_compact(const uint64_t *__restri
     if (i <= n) new_offsets[i] = rank[offsets[i]];
 }
 
-dim3 blocks_for(uint64_t items) { return dim3(grid_for(items, 256)); }
 
 }  // namespace
 

@@ -17,6 +17,7 @@
 
 #include "build.hpp"
 #include "capi_internal.hpp"
+#include "device_common.hpp"
 #include "hip_raii.hpp"
 #include "lf_device.hpp"
 #include "merge.hpp"
@@ -29,10 +30,9 @@ using namespace record_access;
 
 constexpr uint32_t THREADS = 256;
 
-using Scratch = BuildScratch;
-using Buf = BuildBuf;
+using Scratch = CountedScratch;
+using Buf = CountedBuf;
 
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + THREADS - 1) / THREADS); }
 __device__ __forceinline__ uint64_t global_thread() { return static_cast<uint64_t>(blockIdx.x) * THREADS + threadIdx.x; }
 
 // An input with the first position of every record (first[records] = sequences + visits)
@@ -303,23 +303,16 @@ __global__ __launch_bounds__(THREADS) void k_merge_concat(const uint64_t *__rest
     else if (t == na + nb) offsets[t] = ta + tb;
 }
 
-void exclusive_sum32(const uint32_t *in, uint32_t *out, uint64_t n, Scratch &sc, Buf &temp, hipStream_t s) {
-    size_t bytes = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n, s));
-    if (bytes > temp.bytes) temp.alloc(sc, bytes);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp.ptr, bytes, in, out, n, s));
-}
-
 }  // namespace
 
-void merge_decode_bodies(const MergeInput &in, MergeDecoded &d, BuildScratch &sc, BuildBuf &temp, hipStream_t s) {
+void merge_decode_bodies(const MergeInput &in, MergeDecoded &d, CountedScratch &sc, CountedBuf &temp, hipStream_t s) {
     const uint64_t records = in.ix.n_records;
     d.positions = in.sequences + in.visits;
     d.first.alloc(sc, (records + 1) * sizeof(uint32_t));
     d.body.alloc(sc, d.positions * sizeof(uint32_t));
     Buf len(sc, (records + 1) * sizeof(uint32_t)), is_long(sc, records + 1), long_records(sc, (records + 1) * sizeof(uint32_t)), count(sc, sizeof(uint64_t));
     k_merge_count<<<blocks_for(records + 1), THREADS, 0, s>>>(in.ix, in.sequences, len.as<uint32_t>(), is_long.as<uint8_t>());
-    exclusive_sum32(len.as<uint32_t>(), d.first.as<uint32_t>(), records + 1, sc, temp, s);
+    exclusive_sum(len.as<uint32_t>(), d.first.as<uint32_t>(), records + 1, sc, temp, s);
     hipcub::CountingInputIterator<uint32_t> ids(0);
     size_t bytes = 0;
     HIP_CHECK(hipcub::DeviceSelect::Flagged(nullptr, bytes, ids, is_long.as<uint8_t>(), long_records.as<uint32_t>(), count.as<uint64_t>(), static_cast<int64_t>(records), s));
@@ -371,7 +364,7 @@ void merge_records_on_device(const MergeInput &a, const MergeInput &b, BuildOutp
     {
         Buf len(sc, (records + 1) * sizeof(uint32_t));
         k_merge_lengths<<<blocks_for(records + 1), THREADS, 0, s>>>(A, B, records, alphabet_offset, len.as<uint32_t>());
-        exclusive_sum32(len.as<uint32_t>(), first.as<uint32_t>(), records + 1, sc, temp, s);
+        exclusive_sum(len.as<uint32_t>(), first.as<uint32_t>(), records + 1, sc, temp, s);
         HIP_CHECK(hipMemsetAsync(rec.ptr, 0, rec.bytes, s));
         HIP_CHECK(hipMemsetAsync(succ.ptr, 0, succ.bytes, s));
         k_merge_interleave<<<blocks_for(slots), THREADS, 0, s>>>(W, R, dw.body.as<uint32_t>(), dr.body.as<uint32_t>(), cross.as<uint32_t>(), dw.positions, dr.positions,

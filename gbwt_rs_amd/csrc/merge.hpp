@@ -84,13 +84,13 @@ struct MergeInput {
 
 // first[] (records + 1 entries: the first position of every record, the endmarker's first) and the successor of every position
 struct MergeDecoded {
-    BuildBuf first, body;
+    CountedBuf first, body;
     uint64_t positions = 0;
 };
 
 // Lengths, scan and bodies of one input (k_merge_count, k_merge_decode*): also the first phase of a removal (remove.hip).  temp: scratch
 // of the library calls, any size, grown as needed.  Throws InvalidData where the records do not hold what the header says.
-void merge_decode_bodies(const MergeInput &in, MergeDecoded &d, BuildScratch &sc, BuildBuf &temp, hipStream_t s);
+void merge_decode_bodies(const MergeInput &in, MergeDecoded &d, CountedScratch &sc, CountedBuf &temp, hipStream_t s);
 
 struct MergeWalk {
     uint32_t walked_input = 0;             // 0 = a, 1 = b

@@ -41,25 +41,12 @@ __global__ void __launch_bounds__(256) k_refpos_lengths(const uint32_t *__restri
     len[i] = b - a;
 }
 
-// A piece of the scan starts from the sum in front of it: added to its first item, and put back where launch_scan has cleared it
-__global__ void k_refpos_carry(uint64_t *in, uint64_t *out, uint64_t at, uint64_t *saved, int restore) {
-    if (restore) { out[at] = *saved; return; }
-    *saved = out[at];
-    in[at] += *saved;
-}
-
-// the row of position i < offsets[n]: the last one that starts at or before i (rows without nodes in front of it start where it does)
-__device__ __forceinline__ uint64_t refpos_row_of(const uint64_t *offsets, uint64_t n, uint64_t i) {
-    uint64_t lo = 0, hi = n - 1;
-    while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if (offsets[mid] <= i) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 __global__ void __launch_bounds__(256) k_refpos_succ(RefposRows rows, const uint64_t *__restrict__ off, uint64_t interval, uint32_t *__restrict__ jump) {
     const uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x, P = rows.positions;
     if (i > P) return;
     if (i == P) { jump[P] = static_cast<uint32_t>(P); return; }
-    const uint64_t r = refpos_row_of(rows.offsets, rows.n, i), end = rows.offsets[r + 1], base = off[rows.offsets[r]];
+    // the row of position i: the last one that starts at or before i (rows without nodes in front of it start where it does)
+    const uint64_t r = last_at_or_before(rows.offsets, rows.n, i), end = rows.offsets[r + 1], base = off[rows.offsets[r]];
     const uint64_t here = off[i] - base;
     const uint64_t target = here + interval < here ? ~uint64_t(0) : here + interval;
     uint64_t lo = i + 1, hi = end;                   // the first k in [i + 1, end) with off_k >= target, or end
@@ -96,7 +83,7 @@ template <bool FAST>
 __global__ void __launch_bounds__(256) k_refpos_walk(DeviceIndex ix, RefposRows rows, RefposWalk w) {
     const uint64_t t = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     if (t >= w.walkers) return;
-    const uint64_t r = refpos_row_of(w.seg_first, rows.n, t), j = t - w.seg_first[r], id = w.seq_ids[r];
+    const uint64_t r = last_at_or_before(w.seg_first, rows.n, t), j = t - w.seg_first[r], id = w.seq_ids[r];
     const uint64_t a = rows.offsets[r], len = rows.offsets[r + 1] - a;
     if (len == 0) return;
     // nodes [from, to) of the row are this lane's; Pos of node `from` = the endmarker entry (segment 0), or one step from the sample's state,
@@ -136,22 +123,11 @@ __global__ void __launch_bounds__(256) k_refpos_walk(DeviceIndex ix, RefposRows 
     if (!ok) atomicOr(w.flags + REFPOS_FLAG_MISMATCH, 1u);
 }
 
-dim3 blocks_for(uint64_t items) { return dim3(grid_for(items, 256)); }
 
 }  // namespace
 
 void launch_refpos_lengths(const RefposRows &rows, const Labels &L, uint64_t *d_len, hipStream_t s) {
     if (rows.positions) hipLaunchKernelGGL(k_refpos_lengths, blocks_for(rows.positions), dim3(256), 0, s, rows.nodes, rows.positions, L, d_len);
-}
-
-void launch_refpos_scan(uint64_t *d_in, uint64_t *d_out, uint64_t n, uint64_t *d_carry, void *d_temp, size_t temp_bytes, hipStream_t s) {
-    if (n == 0) { launch_scan(d_in, d_out, 0, d_temp, temp_bytes, s); return; }
-    for (uint64_t at = 0; at < n; at += REFPOS_SCAN_PIECE) {
-        const uint64_t piece = std::min(REFPOS_SCAN_PIECE, n - at);
-        if (at != 0) hipLaunchKernelGGL(k_refpos_carry, dim3(1), dim3(1), 0, s, d_in, d_out, at, d_carry, 0);
-        launch_scan(d_in + at, d_out + at, piece, d_temp, temp_bytes, s);
-        if (at != 0) hipLaunchKernelGGL(k_refpos_carry, dim3(1), dim3(1), 0, s, d_in, d_out, at, d_carry, 1);
-    }
 }
 
 void launch_refpos_succ(const RefposRows &rows, const uint64_t *d_off, uint64_t interval, uint32_t *d_jump, hipStream_t s) {

@@ -1,4 +1,5 @@
-// refpos.hpp -- launch wrappers of the reference-position kernels (refpos.hip; the entry points are in capi_refpos.hip).
+// refpos.hpp -- launch wrappers of the reference-position kernels (refpos.hip; the entry points are in capi_refpos.hip, the two scans of a
+// request are scan.hpp's).
 #pragma once
 
 #include "capi_internal.hpp"
@@ -13,10 +14,6 @@ struct RefposRows { const uint64_t *offsets; const uint32_t *nodes; uint64_t n, 
 
 // len[i] = label length of the node of position i
 void launch_refpos_lengths(const RefposRows &rows, const Labels &L, uint64_t *d_len, hipStream_t s);
-// launch_scan over any number of items (it counts in int): d_out[0] = 0, d_out[i + 1] = d_in[0] + .. + d_in[i].  d_in is scratch afterwards;
-// d_carry is one word of scratch.  temp_bytes >= scan_temp_bytes(min(n, REFPOS_SCAN_PIECE))
-constexpr uint64_t REFPOS_SCAN_PIECE = uint64_t(1) << 30;
-void launch_refpos_scan(uint64_t *d_in, uint64_t *d_out, uint64_t n, uint64_t *d_carry, void *d_temp, size_t temp_bytes, hipStream_t s);
 // jump[i] = the first k > i of the row of i with off_k >= off_i + interval (saturating, offsets inside the row), or `positions`; jump[positions] = positions
 void launch_refpos_succ(const RefposRows &rows, const uint64_t *d_off, uint64_t interval, uint32_t *d_jump, hipStream_t s);
 // mark[first position of every row with nodes] = 1 (d_mark zeroed by the caller)

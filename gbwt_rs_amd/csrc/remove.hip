@@ -19,6 +19,7 @@
 
 #include "build.hpp"
 #include "capi_internal.hpp"
+#include "device_common.hpp"
 #include "hip_raii.hpp"
 #include "lf_device.hpp"
 #include "merge.hpp"
@@ -32,10 +33,9 @@ using namespace record_access;
 
 constexpr uint32_t THREADS = 256;
 
-using Scratch = BuildScratch;
-using Buf = BuildBuf;
+using Scratch = CountedScratch;
+using Buf = CountedBuf;
 
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + THREADS - 1) / THREADS); }
 __device__ __forceinline__ uint64_t global_thread() { return static_cast<uint64_t>(blockIdx.x) * THREADS + threadIdx.x; }
 
 // ---- marks -----------------------------------------------------------------------------------------------------------------------------

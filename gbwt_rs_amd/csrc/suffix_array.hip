@@ -213,10 +213,10 @@ gbwt_hip_status build_suffix_array(const uint8_t *d_text, uint64_t n, uint8_t se
     const uint64_t tiles = (n + SA_TILE - 1) / SA_TILE;
     const dim3 tile_blocks(static_cast<unsigned>(std::min<uint64_t>(tiles, 8ull * static_cast<unsigned>(std::max(cus, 1)))));
 
-    BuildScratch sc;
-    BuildBuf rank(sc, plan.rank_bytes), sa(sc, plan.sa_bytes), key_a(sc, plan.key_bytes), key_b(sc, plan.key_bytes), pos_a(sc, plan.pos_bytes), pos_b(sc, plan.pos_bytes);
-    BuildBuf slot_a(sc, plan.slot_bytes), slot_b(sc, plan.slot_bytes), dense(sc, plan.dense_bytes), picked(sc, plan.picked_bytes), flag(sc, plan.flag_bytes);
-    BuildBuf temp(sc, plan.temp_bytes), words(sc, plan.words_bytes);     // words[0]: the size of the active set, words[1]: the runs
+    CountedScratch sc;
+    CountedBuf rank(sc, plan.rank_bytes), sa(sc, plan.sa_bytes), key_a(sc, plan.key_bytes), key_b(sc, plan.key_bytes), pos_a(sc, plan.pos_bytes), pos_b(sc, plan.pos_bytes);
+    CountedBuf slot_a(sc, plan.slot_bytes), slot_b(sc, plan.slot_bytes), dense(sc, plan.dense_bytes), picked(sc, plan.picked_bytes), flag(sc, plan.flag_bytes);
+    CountedBuf temp(sc, plan.temp_bytes), words(sc, plan.words_bytes);     // words[0]: the size of the active set, words[1]: the runs
     uint64_t *const d_words = words.as<uint64_t>();
     HIP_CHECK(hipMemsetAsync(d_words, 0, 2 * sizeof(uint64_t), s));
     HIP_CHECK(hipEventRecord(ctx.ev[1], s));

@@ -28,7 +28,7 @@
 #include <algorithm>
 
 #include "capi_status.hpp"
-#include "kernels.hpp"
+#include "device_common.hpp"
 #include "tags.hpp"
 
 using namespace gbwt_hip;
@@ -57,14 +57,6 @@ __global__ void __launch_bounds__(256) k_tag_positions(const uint64_t *offsets, 
     pos_len[q] = b - a;
 }
 
-// launch_scan in pieces (it counts in int, and clears the word in front of what it writes): a piece starts from the sum in front of it, which is
-// added to its first length and put back where the scan of the piece has cleared it
-__global__ void k_tag_carry(uint64_t *pos_len, uint64_t *pos_off, uint64_t at, uint64_t *saved, int restore) {
-    if (restore) { pos_off[at] = *saved; return; }
-    *saved = pos_off[at];
-    pos_len[at] += *saved;
-}
-
 // Text offset of every row, and the text length behind the last
 __global__ void __launch_bounds__(256) k_tag_rows(const uint64_t *offsets, uint64_t n, const uint64_t *pos_off, uint64_t positions, uint64_t *rows) {
     const uint64_t k = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
@@ -79,17 +71,13 @@ __global__ void __launch_bounds__(256) k_tag_top(const uint64_t *pos_off, uint64
     const uint64_t h = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     if (h >= hints) return;
     if (h + 1 == hints) { top[h] = static_cast<H>(positions - 1); return; }
-    const uint64_t t = h << TAG_SHIFT;
-    uint64_t lo = 0, hi = positions - 1;
-    while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if (pos_off[mid] <= t) lo = mid; else hi = mid - 1; }
-    top[h] = static_cast<H>(lo);
+    top[h] = static_cast<H>(last_at_or_before(pos_off, positions, h << TAG_SHIFT));
 }
 
 // The tag of one text offset t < text_len (the lookup of the gather kernel, alone: the tag in front of a workgroup's first tile)
 template <class H>
 __device__ __forceinline__ uint64_t tag_of(const TagMap<H> &m, uint64_t t) {
-    uint64_t lo = m.top[t >> TAG_SHIFT], hi = m.top[(t >> TAG_SHIFT) + 1];
-    while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if (m.off[mid] <= t) lo = mid; else hi = mid - 1; }
+    const uint64_t lo = last_at_or_before(m.off, m.top[t >> TAG_SHIFT], m.top[(t >> TAG_SHIFT) + 1], t);
     return (static_cast<uint64_t>(m.node[lo]) << 10) + (t - m.off[lo]);
 }
 
@@ -175,7 +163,6 @@ __global__ void __launch_bounds__(TAG_THREADS) k_tags(const uint64_t *__restrict
     }
 }
 
-dim3 blocks_of(uint64_t items) { return dim3(static_cast<unsigned>((items + 255) / 256)); }
 
 }  // namespace
 
@@ -183,24 +170,16 @@ namespace gbwt_hip {
 
 void launch_tag_positions(const uint64_t *d_offsets, const uint32_t *d_nodes, uint64_t n, uint64_t positions, const Labels &L, uint32_t *d_pos_node, uint64_t *d_pos_len,
                           hipStream_t s) {
-    hipLaunchKernelGGL(k_tag_positions, blocks_of(positions), dim3(256), 0, s, d_offsets, d_nodes, n, positions, L, d_pos_node, d_pos_len);
-}
-
-void launch_tag_scan(uint64_t *d_pos_len, uint64_t *d_pos_off, uint64_t positions, uint64_t piece, uint64_t *d_saved, void *d_temp, size_t temp_bytes, hipStream_t s) {
-    for (uint64_t at = 0; at < positions; at += piece) {
-        if (at != 0) hipLaunchKernelGGL(k_tag_carry, dim3(1), dim3(1), 0, s, d_pos_len, d_pos_off, at, d_saved, 0);
-        launch_scan(d_pos_len + at, d_pos_off + at, std::min(piece, positions - at), d_temp, temp_bytes, s);
-        if (at != 0) hipLaunchKernelGGL(k_tag_carry, dim3(1), dim3(1), 0, s, d_pos_len, d_pos_off, at, d_saved, 1);
-    }
+    hipLaunchKernelGGL(k_tag_positions, blocks_for(positions), dim3(256), 0, s, d_offsets, d_nodes, n, positions, L, d_pos_node, d_pos_len);
 }
 
 void launch_tag_rows(const uint64_t *d_offsets, uint64_t n, const uint64_t *d_pos_off, uint64_t positions, uint64_t *d_rows, hipStream_t s) {
-    hipLaunchKernelGGL(k_tag_rows, blocks_of(n + 1), dim3(256), 0, s, d_offsets, n, d_pos_off, positions, d_rows);
+    hipLaunchKernelGGL(k_tag_rows, blocks_for(n + 1), dim3(256), 0, s, d_offsets, n, d_pos_off, positions, d_rows);
 }
 
 void launch_tag_top(const uint64_t *d_pos_off, uint64_t positions, uint64_t hints, void *d_top, bool wide, hipStream_t s) {
-    if (wide) hipLaunchKernelGGL(k_tag_top<uint64_t>, blocks_of(hints), dim3(256), 0, s, d_pos_off, positions, hints, static_cast<uint64_t *>(d_top));
-    else hipLaunchKernelGGL(k_tag_top<uint32_t>, blocks_of(hints), dim3(256), 0, s, d_pos_off, positions, hints, static_cast<uint32_t *>(d_top));
+    if (wide) hipLaunchKernelGGL(k_tag_top<uint64_t>, blocks_for(hints), dim3(256), 0, s, d_pos_off, positions, hints, static_cast<uint64_t *>(d_top));
+    else hipLaunchKernelGGL(k_tag_top<uint32_t>, blocks_for(hints), dim3(256), 0, s, d_pos_off, positions, hints, static_cast<uint32_t *>(d_top));
 }
 
 void launch_tags(int device, const TagTables &t, const uint64_t *d_sa, uint64_t count, uint64_t *d_tags, TagState *d_state, bool has_prev, uint32_t parity, hipStream_t s) {

@@ -1,5 +1,5 @@
-// tags.hpp -- launch wrappers of tags.hip: the position map of a tag plan (node and label length of every position, the scan of the lengths
-// in pieces, the text offset of every row, the sampled top level) and the gather of one batch of suffix array values.
+// tags.hpp -- launch wrappers of tags.hip: the position map of a tag plan (node and label length of every position, the text offset of every
+// row, the sampled top level; the scan of the lengths in between is scan.hpp's) and the gather of one batch of suffix array values.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,7 +11,6 @@
 namespace gbwt_hip {
 
 constexpr uint32_t TAG_SHIFT = 5;                                   // one hint per 32 text offsets
-constexpr uint64_t TAG_SCAN_PIECE = uint64_t(1) << 30;              // (launch_scan counts in int)
 
 // What a request leaves behind: the runs counted so far, the last tag of the batches (two slots in turn: a batch reads the one its
 // predecessor wrote while its own last workgroup writes the other), and whether a value was out of range.
@@ -25,9 +24,6 @@ struct TagTables { const void *top; bool wide; const uint64_t *off; const uint32
 // node and label length of every position of the rows (CSR: d_offsets[n + 1], d_nodes) with one endmarker position behind each row
 void launch_tag_positions(const uint64_t *d_offsets, const uint32_t *d_nodes, uint64_t n, uint64_t positions, const Labels &L, uint32_t *d_pos_node, uint64_t *d_pos_len,
                           hipStream_t s);
-// d_pos_off[positions + 1] = the exclusive scan of d_pos_len, `piece` positions per launch of the scan; d_saved: a word of scratch for the
-// sum in front of a piece (d_pos_len is changed where a piece starts)
-void launch_tag_scan(uint64_t *d_pos_len, uint64_t *d_pos_off, uint64_t positions, uint64_t piece, uint64_t *d_saved, void *d_temp, size_t temp_bytes, hipStream_t s);
 // d_rows[n + 1]: the text offset of every row, and the text length behind the last
 void launch_tag_rows(const uint64_t *d_offsets, uint64_t n, const uint64_t *d_pos_off, uint64_t positions, uint64_t *d_rows, hipStream_t s);
 void launch_tag_top(const uint64_t *d_pos_off, uint64_t positions, uint64_t hints, void *d_top, bool wide, hipStream_t s);

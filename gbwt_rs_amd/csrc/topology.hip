@@ -17,6 +17,7 @@
 // edge of the kept rows writes its line (two names and ten bytes).
 #include <hip/hip_runtime.h>
 
+#include "device_common.hpp"
 #include "lf_device.hpp"
 #include "topology.hpp"
 
@@ -24,7 +25,6 @@ namespace gbwt_hip {
 
 namespace {
 
-inline unsigned blocks_for(uint64_t n) { return static_cast<unsigned>((n + 255) / 256); }
 
 constexpr uint32_t BIG_STAGE = 1024;          // nodes staged in LDS per round of k_edge_fill_big (8 KiB)
 constexpr uint32_t NO_SEGMENT = 0xFFFFFFFFu;

@@ -160,7 +160,7 @@ struct GraphTextState {
 
 // Locate (locate.hip, capi_locate.hip).  The rows of the last request -- off / ids / valid, for a unique request uoff and the compacted
 // ids -- live in buffers of their own: an edges / links request leaves them alone.  states: the states of a request given on the host;
-// counts, keys, sorted, flag, rank, temp: scratch; words: the flag word, a scan carry and the step counter; pos / pos_ids / pos_valid: a
+// counts, keys, sorted, flag, rank, temp: scratch; words: the flag word and the step counter; pos / pos_ids / pos_valid: a
 // positions request.  ev[0] .. ev[1]: the locate kernel, ev[1] .. ev[2]: sort and compaction of a unique request.  memo: states, unique, n.
 struct LocateState {
     DeviceBuffer states, counts, off, ids, valid, keys, sorted, flag, rank, uoff, temp, words, pos, pos_ids, pos_valid;

@@ -662,7 +662,8 @@ gbwt_hip_status gbwt_hip_reference_positions(const gbwt_hip_index *index, gbwt_h
  * lengths, scans, successors and the pointer-doubling rounds up to the host's wait for the total, *offsets_ms = the LF walk that carries the
  * in-record offsets and writes the positions. */
 gbwt_hip_status gbwt_hip_last_positions_ms(const gbwt_hip_workspace *ws, float *walk_ms, float *select_ms, float *offsets_ms);
-/* Of the same request: the pointer-doubling rounds that marked something, and the kernels and scans it launched behind its extraction. */
+/* Of the same request: the pointer-doubling rounds that marked something, and the kernels and scans it launched behind its extraction (a scan
+ * counts one launch per piece of GBWT_HIP_SCAN_PIECE positions: one, short of 2^30 positions). */
 gbwt_hip_status gbwt_hip_last_positions_rounds(const gbwt_hip_workspace *ws, uint32_t *rounds, uint32_t *launches);
 
 /* ---- locate: the sequences behind a search state (any handle) ---------------------------------------------------------------------------

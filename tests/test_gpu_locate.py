@@ -182,6 +182,22 @@ def test_wide_rows_revisits_and_sort_pieces(monkeypatch):
     assert_rows(pieces.locate_csr(batch, unique=False), plain)
 
 
+def test_rows_and_ids_scanned_in_pieces(monkeypatch):
+    """The scans of a request -- the rows' offsets over the states, the ranks of a unique request over the ids -- in pieces of 4 096 items, on a
+    workspace of its own (GBWT_HIP_SCAN_PIECE is read when a workspace is made): what only requests of more than 2^30 states or ids get otherwise."""
+    dev, oracle = synth_pair(wide_paths())
+    own = LX.owners(oracle)
+    hub = TG.fwd(10)
+    n = own.lengths.of(hub)
+    states = [(hub, i % n, i % n + 1) for i in range(4200)] + [(hub, 7, 3), (hub, 0, n + 1)] + [oracle.find(hub)] * 130 + [(hub, 5, 60)]
+    assert len(states) > 4096                             # more than one piece of rows; more than eight of ids (below)
+    monkeypatch.setenv("GBWT_HIP_SCAN_PIECE", "4096")
+    pieces = dev.another_workspace()
+    plain, unique = check_states(pieces, own, states)
+    assert sum(len(r) for r in plain if r is not None) > 8 * 4096 and any(r is None for r in plain)
+    assert sum(len(r) for r in unique if r is not None) < sum(len(r) for r in plain if r is not None)
+
+
 # ---- the three ways a lane can end --------------------------------------------------------------------------------------------------------
 
 def test_interval_one_default_and_none_agree(monkeypatch):

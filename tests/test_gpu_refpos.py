@@ -155,6 +155,25 @@ def test_genome_path_positions_any_ids(genome):
     assert np.array_equal(paths["first"], np.concatenate([[0], np.cumsum(paths["count"])[:-1]]).astype(np.uint64))
 
 
+def test_genome_positions_scanned_in_pieces(genome, monkeypatch):
+    """The two scans of a request -- bases in front of every position, slots of the kept ones -- in pieces of 4 096 positions, on a workspace of
+    its own (GBWT_HIP_SCAN_PIECE is read when a workspace is made): what only requests of more than 2^30 positions get otherwise.  Every piece
+    is a launch, which the launch count shows."""
+    dev = G.GBZ.load(genome.gbz)
+    every = list(range(genome.paths))
+    positions = sum(genome.nodes)
+    assert positions > 8 * 4096
+    monkeypatch.setenv("GBWT_HIP_SCAN_PIECE", "4096")
+    pieces = dev.another_workspace()
+    monkeypatch.delenv("GBWT_HIP_SCAN_PIECE")
+    for interval in (0, 5000):
+        want = expect(genome.starts, every, interval)
+        assert R.same(dev.path_positions(every, interval), want), interval
+        assert R.same(pieces.path_positions(every, interval), want), interval
+        whole, cut = dev.last_positions_rounds()[1], pieces.last_positions_rounds()[1]
+        assert cut > whole and cut - whole == 2 * (-(-positions // 4096) - 1), (interval, whole, cut)   # a launch more per further piece of either scan
+
+
 class Tangle:
     def __init__(self, directory):
         self.gbz = os.path.join(directory, "tangle.gbz")

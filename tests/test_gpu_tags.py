@@ -128,7 +128,7 @@ def test_synthetic_genome_host_device_and_file_forms(tmp_path, monkeypatch):
     walk_ms, plan_ms, gather_ms = dev.last_tags_ms()
     assert walk_ms > 0 and plan_ms > 0 and gather_ms > 0
     # the same plan scanned in pieces and with 64-bit hints (what plans of 2^30 and 2^32 positions get)
-    monkeypatch.setenv("GBWT_HIP_TAG_SCAN_PIECE", "4096")
+    monkeypatch.setenv("GBWT_HIP_SCAN_PIECE", "4096")
     monkeypatch.setenv("GBWT_HIP_TAG_WIDE", "1")
     other = dev.another_workspace()
     assert positions > 8 * 4096

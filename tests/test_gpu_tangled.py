@@ -176,7 +176,7 @@ def test_tangle_tag_files_batches_and_wide_plan(tangle, tmp_path, monkeypatch):
     assert dev.write_tag_array(base) == T.runs(want)
     assert np.array_equal(np.fromfile(base + ".tags", dtype="<u8"), want)
     # the plan scanned in pieces and with 64-bit hints, on a workspace of its own
-    monkeypatch.setenv("GBWT_HIP_TAG_SCAN_PIECE", "4096")
+    monkeypatch.setenv("GBWT_HIP_SCAN_PIECE", "4096")
     monkeypatch.setenv("GBWT_HIP_TAG_WIDE", "1")
     other = dev.another_workspace()
     assert sum(TG.TANGLE_PATH_LENGTHS) > 8 * 4096
