@@ -112,6 +112,29 @@ class FmLocated(C.Structure):
     _fields_ = [("d_offsets", C.c_void_p), ("d_values", C.c_void_p), ("d_ranges", C.c_void_p), ("total", C.c_uint64), ("m", C.c_uint64)]
 
 
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 1, 2, 3     # gbwt_hip_fm_seed_options.strands, gbwt_hip_fm_seed.strand
+
+
+class FmSeedOptions(C.Structure):
+    _fields_ = [("min_length", C.c_uint32), ("strands", C.c_uint32), ("max_occurrences", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FmSeed(C.Structure):
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_uint64), ("start", C.c_uint32), ("end", C.c_uint32), ("strand", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FmSeedInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("requests", "reads", "read_bytes", "anchors", "refined_ends", "steps", "seeds", "hits", "over_max", "planned_scratch_bytes",
+                                                "peak_scratch_bytes")] + \
+               [(name, C.c_uint32) for name in ("stride", "strands")] + \
+               [(name, C.c_float) for name in ("idle_share", "anchor_ms", "refine_ms", "emit_ms", "hits_ms", "reserved")]
+
+
+class FmSeedRows(C.Structure):
+    _fields_ = [("d_read_offsets", C.c_void_p), ("d_seeds", C.c_void_p), ("d_hit_offsets", C.c_void_p), ("d_hits", C.c_void_p), ("total_seeds", C.c_uint64), ("total_hits", C.c_uint64),
+                ("m", C.c_uint64)]
+
+
 class ReferencePath(C.Structure):
     _fields_ = [("path_id", C.c_uint64), ("len", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64)]
 
@@ -251,6 +274,11 @@ SIGNATURES = {
     "gbwt_hip_fm_count_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmLocated)]),
     "gbwt_hip_fm_locate_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmLocated)]),
     "gbwt_hip_fm_graph_positions_device": (_int, [_p, _p, _p, _p, _p, _u64, _u64, _int, C.POINTER(FmLocated)]),
+    "gbwt_hip_fm_last_seed_info": (_int, [_p, C.POINTER(FmSeedInfo)]),
+    "gbwt_hip_fm_seeds": (_int, [_p, _p, _p, _u64, C.POINTER(FmSeedOptions), _p, _p, _u64, C.POINTER(_u64), _p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_fm_seed_graph_positions": (_int, [_p, _p, _p, _p, _p, _u64, C.POINTER(FmSeedOptions), _p, _p, _u64, C.POINTER(_u64), _p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_fm_seeds_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmSeedRows)]),
+    "gbwt_hip_fm_seed_graph_positions_device": (_int, [_p, _p, _p, _p, _p, _u64, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmSeedRows)]),
     "gbwt_hip_components_device": (_int, [_p, C.POINTER(Components)]),
     "gbwt_hip_weakly_connected_components": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_path_components": (_int, [_p, _p, _u64, _p]),

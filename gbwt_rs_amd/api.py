@@ -47,6 +47,20 @@ STATE_DTYPE = np.dtype([("node", "<u8"), ("start", "<u8"), ("end", "<u8")])
 BD_DTYPE = np.dtype([("forward", STATE_DTYPE), ("reverse", STATE_DTYPE)])
 REFPATH_DTYPE = np.dtype([("path_id", "<u8"), ("len", "<u8"), ("first", "<u8"), ("count", "<u8")])      # gbwt_hip_reference_path
 REFPOS_DTYPE = np.dtype([("offset", "<u8"), ("node", "<u8"), ("pos_offset", "<u8")])                    # gbwt_hip_reference_position
+SEED_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8"), ("start", "<u4"), ("end", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])   # gbwt_hip_fm_seed
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = _lib.STRAND_FORWARD, _lib.STRAND_REVERSE, _lib.STRAND_BOTH
+
+_COMPLEMENT = np.full(256, ord("N"), dtype=np.uint8)
+for _a, _b in zip(b"ACGTacgt", b"TGCATGCA"):
+    _COMPLEMENT[_a] = _b
+
+
+def reverse_complement(data):
+    """support::reverse_complement (src/support.rs:87-110) on the host: A/C/G/T in either case to the upper-case complement, every other byte
+    to N, in reverse order; bytes in, bytes out.  FMIndex.seeds computes it on the device: this one is for callers and tests."""
+    if isinstance(data, str):
+        data = data.encode()
+    return _COMPLEMENT[np.frombuffer(bytes(data), dtype=np.uint8)[::-1]].tobytes()
 
 
 def encode_node(node_id, orientation):  # support::encode_node, src/support.rs:155-157
@@ -247,6 +261,51 @@ class FMIndex:
         check(self._L.gbwt_hip_fm_locate_device(self._fm, *self._device_patterns(d_offsets, d_bytes, m, nbytes), C.byref(out)))
         return out
 
+    @staticmethod
+    def _seed_options(min_length, strands, max_occurrences):
+        if strands not in (STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH):
+            raise ValueError("strands must be STRAND_FORWARD, STRAND_REVERSE or STRAND_BOTH")
+        if int(min_length) < 0 or int(max_occurrences) < 0:
+            raise ValueError("min_length and max_occurrences must not be negative")
+        return _lib.FmSeedOptions(int(min_length), int(strands), int(max_occurrences), 0, 0)
+
+    def _seed_rows(self, call, offsets, data, opts):  # the size query, then the fill, which only copies
+        m = offsets.size - 1
+        read_offsets = np.zeros(m + 1, dtype=np.uint64)
+        n_seeds, n_hits = C.c_uint64(0), C.c_uint64(0)
+        reads = (_ptr(offsets), _ptr(data), m, C.byref(opts), _ptr(read_offsets))
+        check(call(*reads, None, 0, C.byref(n_seeds), None, None, 0, C.byref(n_hits)))
+        with_hits = opts.max_occurrences != 0
+        seeds = np.zeros(max(1, n_seeds.value), dtype=SEED_DTYPE)
+        hit_offsets = np.zeros(n_seeds.value + 1, dtype=np.uint64) if with_hits else None
+        hits = np.zeros(max(1, n_hits.value), dtype=np.uint64) if with_hits else None
+        check(call(*reads, seeds.ctypes.data, seeds.size, C.byref(n_seeds), _ptr(hit_offsets), _ptr(hits), hits.size if with_hits else 0, C.byref(n_hits)))
+        return read_offsets, seeds[: n_seeds.value], hit_offsets, hits[: n_hits.value] if with_hits else None
+
+    def seeds(self, reads, min_length=1, strands=STRAND_BOTH, max_occurrences=0):
+        """The maximal exact matches of every read (gbwt_hip_fm_seeds): (read_offsets[m + 1], seeds, hit_offsets, hits).  `reads` as the
+        patterns of count; `seeds` is a structured array of SEED_DTYPE -- start, end, strand and the SA range (lo, hi) of read[start:end] on
+        that strand --, row k of it the seeds of read k, forward strand first, starts and ends ascending; the reverse strand is
+        reverse_complement(read), computed on the device, and its seeds are in its coordinates.  max_occurrences > 0: row i of (hit_offsets,
+        hits) holds the text positions SA[lo:hi] of seed i, empty where it occurs more often; else both are None."""
+        offsets, data = _patterns_csr(reads)
+        opts = self._seed_options(min_length, strands, max_occurrences)
+        return self._seed_rows(lambda *a: self._L.gbwt_hip_fm_seeds(self._fm, *a), offsets, data, opts)
+
+    def seeds_device(self, d_offsets, d_bytes, m, nbytes, min_length=1, strands=STRAND_BOTH, max_occurrences=0):
+        """gbwt_hip_fm_seeds_device: a _lib.FmSeedRows whose d_read_offsets[m + 1], d_seeds[total_seeds] and -- with hits -- d_hit_offsets[total_seeds + 1],
+        d_hits[total_hits] stay in HBM until the next seeds request."""
+        out = _lib.FmSeedRows()
+        opts = self._seed_options(min_length, strands, max_occurrences)
+        check(self._L.gbwt_hip_fm_seeds_device(self._fm, *self._device_patterns(d_offsets, d_bytes, m, nbytes), C.byref(opts), C.byref(out)))
+        return out
+
+    def last_seed_info(self):
+        """gbwt_hip_fm_last_seed_info as a dict: stride, reads, anchors, refined_ends, steps, idle_share, seeds, hits, over_max, scratch bytes, phase times."""
+        info = _lib.FmSeedInfo()
+        check(self._L.gbwt_hip_fm_last_seed_info(self._fm, C.byref(info)))
+        return _as_dict(info, skip_reserved=True)
+
 
 class PathFMIndex(FMIndex):
     """The FM-index of the text of paths of a GBZ (GBZ.fm_index): FMIndex, and the graph positions of the occurrences."""
@@ -266,6 +325,26 @@ class PathFMIndex(FMIndex):
         out = _lib.FmLocated()
         g = self._owner
         check(self._L.gbwt_hip_fm_graph_positions_device(self._fm, g._h, g._ws, *self._device_patterns(d_offsets, d_bytes, m, nbytes), int(bool(unique)), C.byref(out)))
+        return out
+
+    def seeds(self, reads, min_length=1, strands=STRAND_BOTH, max_occurrences=0, graph=False):
+        """FMIndex.seeds; graph=True (with max_occurrences > 0): the hits are the tags of the occurrences' first bases, as graph_positions_csr
+        gives them with unique=False (gbwt_hip_fm_seed_graph_positions)."""
+        if not graph:
+            return super().seeds(reads, min_length, strands, max_occurrences)
+        offsets, data = _patterns_csr(reads)
+        opts = self._seed_options(min_length, strands, max_occurrences)
+        g = self._owner
+        return self._seed_rows(lambda *a: self._L.gbwt_hip_fm_seed_graph_positions(self._fm, g._h, g._ws, *a), offsets, data, opts)
+
+    def seeds_device(self, d_offsets, d_bytes, m, nbytes, min_length=1, strands=STRAND_BOTH, max_occurrences=0, graph=False):
+        """FMIndex.seeds_device; graph=True: tags in d_hits (gbwt_hip_fm_seed_graph_positions_device)."""
+        if not graph:
+            return super().seeds_device(d_offsets, d_bytes, m, nbytes, min_length, strands, max_occurrences)
+        out = _lib.FmSeedRows()
+        opts = self._seed_options(min_length, strands, max_occurrences)
+        g = self._owner
+        check(self._L.gbwt_hip_fm_seed_graph_positions_device(self._fm, g._h, g._ws, *self._device_patterns(d_offsets, d_bytes, m, nbytes), C.byref(opts), C.byref(out)))
         return out
 
 

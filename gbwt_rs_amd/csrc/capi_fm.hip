@@ -12,6 +12,7 @@
 #include "device_common.hpp"
 #include "extract_files.hpp"
 #include "fm_index.hpp"
+#include "fm_object.hpp"
 #include "fm_plan.hpp"
 #include "kernels.hpp"
 #include "scan.hpp"
@@ -19,35 +20,11 @@
 
 using namespace gbwt_hip;
 
-// One FM-index: what fm_layout.hpp describes in HBM, the rows of its last request, and -- for an index of paths -- what the graph-position
-// call needs to turn text positions into tags.  One host thread at a time.
-struct gbwt_hip_fm_index {
-    int device = 0;
-    // the index
-    DeviceBuffer lines, counts, tables, sa;
-    uint64_t index_bytes() const { return bytes_of({&lines, &counts, &tables, &sa}); }
-    FmLayout layout;
-    uint64_t n = 0;
-    bool count_only = false;
-    // the paths behind a path-level index
-    const gbwt_hip_index *index = nullptr;
-    std::vector<uint64_t> path_ids;
-    int endmarker = 0;
-    // the last request: patterns given on the host, ranges and occurrence counts, row offsets, positions, the row of every position, tags;
-    // sorted_* / flag / rank / uoff / kept: a unique request; words: [0] flags, [1] backward steps
-    DeviceBuffer q_offsets, q_bytes, ranges, occ, roff, positions, rows, tags, tmp_values, tmp_rows, sorted_values, sorted_rows, flag, rank, uoff, kept, temp, words;
-    EventSet<3> ev{OnFirstUse{}};
-    RequestKey memo;
-    bool unique_rows = false;         // uoff / kept answer the last request
-    uint64_t last_m = 0, last_total = 0;
-    gbwt_hip_fm_index_info info{};
-    Stream stream{OnFirstUse{}};      // the last member: it goes first, before the buffers its work used
-};
-
 namespace {
 
 constexpr uint64_t WORDS = 4;
-enum Kind { COUNT = 0, LOCATE = 1, GRAPH = 2 };
+using Kind = FmKind;
+constexpr Kind COUNT = FM_COUNT, LOCATE = FM_LOCATE, GRAPH = FM_GRAPH;
 
 gbwt_hip_status check_build(int sentinel, uint32_t flags, gbwt_hip_fm_index **out) {
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
@@ -196,29 +173,6 @@ gbwt_hip_status make_index(int device, gbwt_hip_fm_index **out, Build build) {
         delete fm;
         throw;
     }
-}
-
-// The checks of a query that answer before any device work: first the outputs and the patterns, then the object
-gbwt_hip_status check_patterns(const uint64_t *offsets, const void *bytes, uint64_t m, bool on_host) {
-    if (!offsets) return fail(GBWT_HIP_BAD_ARGUMENT, "null pattern offsets (m + 1 of them, also for m == 0)");
-    if (m >= 0x7FFFFFFFull) return fail(GBWT_HIP_BAD_ARGUMENT, "too many patterns in one request (at most 2^31 - 2)");
-    if (!on_host) return GBWT_HIP_OK;
-    for (uint64_t k = 0; k < m; k++)
-        if (offsets[k + 1] < offsets[k]) return fail(GBWT_HIP_BAD_ARGUMENT, "pattern offsets do not ascend at pattern " + std::to_string(k));
-    if (offsets[m] != 0 && !bytes) return fail(GBWT_HIP_BAD_ARGUMENT, "null pattern bytes");
-    return GBWT_HIP_OK;
-}
-
-gbwt_hip_status check_object(const gbwt_hip_fm_index *fm, Kind kind, const gbwt_hip_index *ix, const gbwt_hip_workspace *ws, int unique) {
-    if (!fm) return fail(GBWT_HIP_BAD_ARGUMENT, "null FM-index");
-    if (unique != 0 && unique != 1) return fail(GBWT_HIP_BAD_ARGUMENT, "unique must be 0 or 1");
-    if (kind != COUNT && fm->count_only) return fail(GBWT_HIP_UNSUPPORTED, "a count-only FM-index holds no suffix array: nothing to locate with");
-    if (kind == GRAPH) {
-        if (!fm->index) return fail(GBWT_HIP_BAD_ARGUMENT, "graph positions need an FM-index made by gbwt_hip_path_fm_index, not one of a plain text");
-        if (!ix || ix != fm->index) return fail(GBWT_HIP_BAD_ARGUMENT, "the FM-index was made from another index handle");
-        if (!ws || ws->index != ix) return fail(GBWT_HIP_BAD_ARGUMENT, "null or mismatched index / workspace");
-    }
-    return GBWT_HIP_OK;
 }
 
 // The rows of a request into the object.  Exactly one of h_offsets / d_offsets; bytes: the pattern bytes behind d_bytes (the host form: offsets[m]).
@@ -419,8 +373,8 @@ gbwt_hip_status gbwt_hip_fm_info(const gbwt_hip_fm_index *fm, gbwt_hip_fm_index_
 gbwt_hip_status gbwt_hip_fm_count(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, uint64_t *ranges) {
     GBWT_HIP_GUARD_BEGIN
     if (m && !ranges) return fail(GBWT_HIP_BAD_ARGUMENT, "null ranges");
-    gbwt_hip_status st = check_patterns(offsets, bytes, m, true);
-    if (st == GBWT_HIP_OK) st = check_object(fm, COUNT, nullptr, nullptr, 0);
+    gbwt_hip_status st = fm_check_patterns(offsets, bytes, m, true);
+    if (st == GBWT_HIP_OK) st = fm_check_object(fm, COUNT, nullptr, nullptr, 0);
     if (st == GBWT_HIP_OK) st = fm_compute(fm, COUNT, offsets, bytes, nullptr, nullptr, m, 0, 0, nullptr, nullptr);
     if (st != GBWT_HIP_OK || m == 0) return st;
     try {
@@ -436,8 +390,8 @@ gbwt_hip_status gbwt_hip_fm_count_device(gbwt_hip_fm_index *fm, const uint64_t *
     GBWT_HIP_GUARD_BEGIN
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     *out = gbwt_hip_fm_located{nullptr, nullptr, nullptr, 0, 0};
-    gbwt_hip_status st = check_patterns(d_offsets, d_bytes, m, false);
-    if (st == GBWT_HIP_OK) st = check_object(fm, COUNT, nullptr, nullptr, 0);
+    gbwt_hip_status st = fm_check_patterns(d_offsets, d_bytes, m, false);
+    if (st == GBWT_HIP_OK) st = fm_check_object(fm, COUNT, nullptr, nullptr, 0);
     if (st == GBWT_HIP_OK) st = fm_compute(fm, COUNT, nullptr, nullptr, d_offsets, static_cast<const uint8_t *>(d_bytes), m, bytes, 0, nullptr, nullptr);
     if (st != GBWT_HIP_OK) return st;
     *out = gbwt_hip_fm_located{nullptr, nullptr, fm->ranges.as<uint64_t>(), 0, m};
@@ -450,8 +404,8 @@ gbwt_hip_status gbwt_hip_fm_locate(gbwt_hip_fm_index *fm, const uint64_t *offset
     GBWT_HIP_GUARD_BEGIN
     if (total) *total = 0;
     if (!total || !out_offsets) return fail(GBWT_HIP_BAD_ARGUMENT, "null total / row offsets");
-    gbwt_hip_status st = check_patterns(offsets, bytes, m, true);
-    if (st == GBWT_HIP_OK) st = check_object(fm, LOCATE, nullptr, nullptr, 0);
+    gbwt_hip_status st = fm_check_patterns(offsets, bytes, m, true);
+    if (st == GBWT_HIP_OK) st = fm_check_object(fm, LOCATE, nullptr, nullptr, 0);
     if (st == GBWT_HIP_OK) st = fm_compute(fm, LOCATE, offsets, bytes, nullptr, nullptr, m, 0, 0, nullptr, nullptr);
     if (st != GBWT_HIP_OK) return st;
     return rows_to_host(fm, LOCATE, m, out_offsets, positions, capacity, total);
@@ -462,8 +416,8 @@ gbwt_hip_status gbwt_hip_fm_locate_device(gbwt_hip_fm_index *fm, const uint64_t 
     GBWT_HIP_GUARD_BEGIN
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     *out = gbwt_hip_fm_located{nullptr, nullptr, nullptr, 0, 0};
-    gbwt_hip_status st = check_patterns(d_offsets, d_bytes, m, false);
-    if (st == GBWT_HIP_OK) st = check_object(fm, LOCATE, nullptr, nullptr, 0);
+    gbwt_hip_status st = fm_check_patterns(d_offsets, d_bytes, m, false);
+    if (st == GBWT_HIP_OK) st = fm_check_object(fm, LOCATE, nullptr, nullptr, 0);
     if (st == GBWT_HIP_OK) st = fm_compute(fm, LOCATE, nullptr, nullptr, d_offsets, static_cast<const uint8_t *>(d_bytes), m, bytes, 0, nullptr, nullptr);
     if (st != GBWT_HIP_OK) return st;
     *out = located_of(fm, LOCATE);
@@ -476,8 +430,8 @@ gbwt_hip_status gbwt_hip_fm_graph_positions(gbwt_hip_fm_index *fm, const gbwt_hi
     GBWT_HIP_GUARD_BEGIN
     if (total) *total = 0;
     if (!total || !out_offsets) return fail(GBWT_HIP_BAD_ARGUMENT, "null total / row offsets");
-    gbwt_hip_status st = check_patterns(offsets, bytes, m, true);
-    if (st == GBWT_HIP_OK) st = check_object(fm, GRAPH, ix, ws, unique);
+    gbwt_hip_status st = fm_check_patterns(offsets, bytes, m, true);
+    if (st == GBWT_HIP_OK) st = fm_check_object(fm, GRAPH, ix, ws, unique);
     if (st == GBWT_HIP_OK) st = fm_compute(fm, GRAPH, offsets, bytes, nullptr, nullptr, m, 0, unique, ix, ws);
     if (st != GBWT_HIP_OK) return st;
     return rows_to_host(fm, GRAPH, m, out_offsets, tags, capacity, total);
@@ -489,8 +443,8 @@ gbwt_hip_status gbwt_hip_fm_graph_positions_device(gbwt_hip_fm_index *fm, const 
     GBWT_HIP_GUARD_BEGIN
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     *out = gbwt_hip_fm_located{nullptr, nullptr, nullptr, 0, 0};
-    gbwt_hip_status st = check_patterns(d_offsets, d_bytes, m, false);
-    if (st == GBWT_HIP_OK) st = check_object(fm, GRAPH, ix, ws, unique);
+    gbwt_hip_status st = fm_check_patterns(d_offsets, d_bytes, m, false);
+    if (st == GBWT_HIP_OK) st = fm_check_object(fm, GRAPH, ix, ws, unique);
     if (st == GBWT_HIP_OK) st = fm_compute(fm, GRAPH, nullptr, nullptr, d_offsets, static_cast<const uint8_t *>(d_bytes), m, bytes, unique, ix, ws);
     if (st != GBWT_HIP_OK) return st;
     *out = located_of(fm, GRAPH);

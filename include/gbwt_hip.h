@@ -522,6 +522,77 @@ gbwt_hip_status gbwt_hip_fm_locate_device(gbwt_hip_fm_index *fm, const uint64_t 
 gbwt_hip_status gbwt_hip_fm_graph_positions_device(gbwt_hip_fm_index *fm, const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *d_offsets, const void *d_bytes,
                                                    uint64_t m, uint64_t bytes, int unique, gbwt_hip_fm_located *out);
 
+/* ---- Seeds of reads: maximal exact matches on the FM-index, on both strands -----------------------------------------------
+ * A read rarely occurs as a whole; what a mapper asks is which pieces of it occur.  For a read P[0, L) of arbitrary bytes and an end e in
+ * 1 .. L, s(e) is the smallest s <= e such that P[s, e) occurs in the text ("occurs" as gbwt_hip_fm_count means it: bytes are bytes; s(e) ==
+ * e where P[e - 1] does not occur).  s never decreases as e grows.  A SEED is [s(e), e) with e - s(e) >= max(min_length, 1) and (e == L or
+ * s(e + 1) > s(e)): exactly the occurring substrings of the read that no longer occurring substring of the read contains.  A seed carries
+ * start, end, strand and the SA range [lo, hi) of P[start, end) in gbwt_hip_fm_count's coordinates; the seeds of a strand are listed with
+ * starts and ends ascending.
+ *
+ * STRANDS: GBWT_HIP_STRAND_FORWARD searches the read as given (no case folding); GBWT_HIP_STRAND_REVERSE searches
+ * support::reverse_complement of it (src/support.rs:87-110: A/C/G/T in either case to the upper-case complement, every other byte to N),
+ * computed on the device, and its seeds are in the coordinates of the reverse-complemented read.  A read's row holds its forward seeds,
+ * then its reverse seeds.
+ *
+ * HITS (max_occurrences > 0): one row per seed, in seed order: SA[lo, hi) in SA order where hi - lo <= max_occurrences, an empty row where
+ * the seed occurs more often (it is still reported, and its range says how often).  gbwt_hip_fm_seed_graph_positions gives the rows as
+ * tags through gbwt_hip_tags_device, as gbwt_hip_fm_graph_positions does, not uniqued.  A count-only index finds seeds and refuses hits
+ * with GBWT_HIP_UNSUPPORTED.
+ *
+ * The search reads every read at the ends L, L - K, L - 2K, .. first (K = stride of the info) and between two of these only where the start
+ * moved.  Its scratch is a function of (reads, read bytes, strands, hits); more than the free device memory is GBWT_HIP_CAPACITY with the
+ * bytes needed, before the first kernel; all of it is freed before the call returns. */
+#define GBWT_HIP_STRAND_FORWARD 1u
+#define GBWT_HIP_STRAND_REVERSE 2u
+#define GBWT_HIP_STRAND_BOTH 3u
+typedef struct {
+    uint32_t min_length;         /* seeds shorter than this are left out (0 counts as 1) */
+    uint32_t strands;            /* 1 forward, 2 reverse, 3 both */
+    uint64_t max_occurrences;    /* 0: no hits */
+    uint32_t flags, reserved;    /* 0 */
+} gbwt_hip_fm_seed_options;      /* NULL = {1, 3, 0, 0, 0} */
+typedef struct {
+    uint64_t lo, hi;
+    uint32_t start, end;
+    uint32_t strand, reserved;
+} gbwt_hip_fm_seed;              /* 32 bytes */
+/* The last computed seeds request of an object.  stride: K; anchors / refined_ends: the ends searched first / in between; steps: backward
+ * steps (as last_steps of gbwt_hip_fm_index_info); idle_share: 1 - steps / (64 x the sum over the waves of the search of their longest lane):
+ * the lane-steps a wave spent waiting for its longest lane; over_max: seeds with more than max_occurrences occurrences (their rows are
+ * empty); planned / peak scratch bytes; HIP-event times of the anchor, refine, emit and hits phases. */
+typedef struct {
+    uint64_t requests, reads, read_bytes, anchors, refined_ends, steps, seeds, hits, over_max, planned_scratch_bytes, peak_scratch_bytes;
+    uint32_t stride, strands;
+    float idle_share, anchor_ms, refine_ms, emit_ms, hits_ms, reserved;
+} gbwt_hip_fm_seed_info;
+gbwt_hip_status gbwt_hip_fm_last_seed_info(const gbwt_hip_fm_index *fm, gbwt_hip_fm_seed_info *out);
+
+/* Reads are a CSR as the patterns of the queries above.  out_read_offsets[m + 1], *total_seeds (and, with max_occurrences > 0,
+ * *total_hits) always; seeds == NULL (and hits == NULL) is the size query, and the call that repeats its request with buffers only copies.
+ * With hits, out_hit_offsets[*total_seeds + 1] is written together with the seeds.  A capacity that is too small is GBWT_HIP_CAPACITY with
+ * the totals set and nothing written.  Checked before any device work, in this order: null outputs; null or descending offsets; strands
+ * outside 1 .. 3; non-zero flags / reserved; then the object. */
+gbwt_hip_status gbwt_hip_fm_seeds(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, const gbwt_hip_fm_seed_options *opts, uint64_t *out_read_offsets,
+                                  gbwt_hip_fm_seed *seeds, uint64_t seed_capacity, uint64_t *total_seeds, uint64_t *out_hit_offsets, uint64_t *hits, uint64_t hit_capacity,
+                                  uint64_t *total_hits);
+gbwt_hip_status gbwt_hip_fm_seed_graph_positions(gbwt_hip_fm_index *fm, const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *offsets, const void *bytes, uint64_t m,
+                                                 const gbwt_hip_fm_seed_options *opts, uint64_t *out_read_offsets, gbwt_hip_fm_seed *seeds, uint64_t seed_capacity,
+                                                 uint64_t *total_seeds, uint64_t *out_hit_offsets, uint64_t *tags, uint64_t hit_capacity, uint64_t *total_hits);
+/* The device forms (d_offsets[m + 1], d_bytes[bytes] as above): the rows stay in HBM, owned by the object, until its next seeds request.
+ * d_hit_offsets / d_hits are NULL without hits. */
+typedef struct {
+    const uint64_t *d_read_offsets;      /* [m + 1] */
+    const gbwt_hip_fm_seed *d_seeds;     /* [total_seeds] */
+    const uint64_t *d_hit_offsets;       /* [total_seeds + 1] */
+    const uint64_t *d_hits;              /* [total_hits]: text positions, or tags */
+    uint64_t total_seeds, total_hits, m;
+} gbwt_hip_fm_seed_rows;
+gbwt_hip_status gbwt_hip_fm_seeds_device(gbwt_hip_fm_index *fm, const uint64_t *d_offsets, const void *d_bytes, uint64_t m, uint64_t bytes, const gbwt_hip_fm_seed_options *opts,
+                                         gbwt_hip_fm_seed_rows *out);
+gbwt_hip_status gbwt_hip_fm_seed_graph_positions_device(gbwt_hip_fm_index *fm, const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *d_offsets, const void *d_bytes,
+                                                        uint64_t m, uint64_t bytes, const gbwt_hip_fm_seed_options *opts, gbwt_hip_fm_seed_rows *out);
+
 /* ---- graph topology: weakly connected components, contig path selection -------------------------------------------------------------
  * GBZ::weakly_connected_components (src/gbz.rs:570-598; known answer src/gbz/tests.rs:503-518): the node ids of the graph that the GBWT
  * records describe, partitioned by "joined through an edge, whatever the orientations" (the successors and predecessors of both
