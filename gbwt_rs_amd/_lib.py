@@ -135,6 +135,31 @@ class FmSeedRows(C.Structure):
                 ("m", C.c_uint64)]
 
 
+class FmChainOptions(C.Structure):
+    _fields_ = [("max_gap", C.c_uint32), ("max_skew", C.c_uint32), ("gap_cost", C.c_uint32), ("min_score", C.c_uint32), ("max_matches", C.c_uint64), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class FmChain(C.Structure):
+    _fields_ = [("text_start", C.c_uint64), ("text_end", C.c_uint64)] + \
+               [(name, C.c_uint32) for name in ("read_start", "read_end", "score", "matches", "strand", "path")]
+
+
+class FmChainMatch(C.Structure):
+    _fields_ = [("y", C.c_uint64), ("x", C.c_uint32), ("w", C.c_uint32)]
+
+
+class FmChainInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("requests", "items", "matches", "skipped_items", "pairs", "chains", "chain_matches", "tile_matches", "planned_scratch_bytes",
+                                                "peak_scratch_bytes", "path_offset_bytes")] + \
+               [(name, C.c_float) for name in ("seeds_ms", "expand_ms", "sort_ms", "dp_ms", "peel_ms", "fill_ms")]
+
+
+class FmChainRows(C.Structure):
+    _fields_ = [("d_read_offsets", C.c_void_p), ("d_chains", C.c_void_p), ("d_match_offsets", C.c_void_p), ("d_matches", C.c_void_p), ("total_chains", C.c_uint64),
+                ("total_matches", C.c_uint64), ("m", C.c_uint64)]
+
+
 class ReferencePath(C.Structure):
     _fields_ = [("path_id", C.c_uint64), ("len", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64)]
 
@@ -279,6 +304,9 @@ SIGNATURES = {
     "gbwt_hip_fm_seed_graph_positions": (_int, [_p, _p, _p, _p, _p, _u64, C.POINTER(FmSeedOptions), _p, _p, _u64, C.POINTER(_u64), _p, _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_fm_seeds_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmSeedRows)]),
     "gbwt_hip_fm_seed_graph_positions_device": (_int, [_p, _p, _p, _p, _p, _u64, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmSeedRows)]),
+    "gbwt_hip_fm_last_chain_info": (_int, [_p, C.POINTER(FmChainInfo)]),
+    "gbwt_hip_fm_chains": (_int, [_p, _p, _p, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmChainOptions), _p, _p, _u64, C.POINTER(_u64), _p, _p, _u64, C.POINTER(_u64)]),
+    "gbwt_hip_fm_chains_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmChainOptions), C.POINTER(FmChainRows)]),
     "gbwt_hip_components_device": (_int, [_p, C.POINTER(Components)]),
     "gbwt_hip_weakly_connected_components": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_path_components": (_int, [_p, _p, _u64, _p]),

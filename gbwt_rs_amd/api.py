@@ -48,6 +48,9 @@ BD_DTYPE = np.dtype([("forward", STATE_DTYPE), ("reverse", STATE_DTYPE)])
 REFPATH_DTYPE = np.dtype([("path_id", "<u8"), ("len", "<u8"), ("first", "<u8"), ("count", "<u8")])      # gbwt_hip_reference_path
 REFPOS_DTYPE = np.dtype([("offset", "<u8"), ("node", "<u8"), ("pos_offset", "<u8")])                    # gbwt_hip_reference_position
 SEED_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8"), ("start", "<u4"), ("end", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])   # gbwt_hip_fm_seed
+CHAIN_DTYPE = np.dtype([("text_start", "<u8"), ("text_end", "<u8"), ("read_start", "<u4"), ("read_end", "<u4"), ("score", "<u4"), ("matches", "<u4"), ("strand", "<u4"),
+                        ("path", "<u4")])                                                                   # gbwt_hip_fm_chain
+CHAIN_MATCH_DTYPE = np.dtype([("y", "<u8"), ("x", "<u4"), ("w", "<u4")])                                    # gbwt_hip_fm_chain_match
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = _lib.STRAND_FORWARD, _lib.STRAND_REVERSE, _lib.STRAND_BOTH
 
 _COMPLEMENT = np.full(256, ord("N"), dtype=np.uint8)
@@ -305,6 +308,49 @@ class FMIndex:
         info = _lib.FmSeedInfo()
         check(self._L.gbwt_hip_fm_last_seed_info(self._fm, C.byref(info)))
         return _as_dict(info, skip_reserved=True)
+
+    @staticmethod
+    def _chain_options(max_gap, max_skew, gap_cost, min_score, max_matches):
+        values = [int(v) for v in (max_gap, max_skew, gap_cost, min_score, max_matches)]
+        if any(v < 0 for v in values) or any(v >= 1 << 32 for v in values[:4]):
+            raise ValueError("max_gap, max_skew, gap_cost and min_score are 32-bit counts, max_matches a count")
+        return _lib.FmChainOptions(*values, 0, 0)
+
+    def chains(self, reads, min_length=1, strands=STRAND_BOTH, max_occurrences=1000, max_gap=0, max_skew=0, gap_cost=1, min_score=1, max_matches=0):
+        """The colinear chains of every read's hits (gbwt_hip_fm_chains): (read_offsets[m + 1], chains, match_offsets, matches).  The seeds are
+        those of seeds(reads, min_length, strands, max_occurrences) with hits; every hit of a seed is a match (y text position, x start in
+        the read, w length).  `chains` is a structured array of CHAIN_DTYPE, row k of it the chains of read k: those of the forward strand,
+        then those of the reverse strand (in the coordinates of reverse_complement(read)), each strand best first; row c of (match_offsets,
+        matches) holds the members of chain c, a CHAIN_MATCH_DTYPE array ascending by (y, x).  max_gap / max_skew 0: 5000 / 500; max_matches:
+        a (read, strand) with more matches yields no chains (0: no limit).  `path` of a chain is 0 on an index of a plain text."""
+        offsets, data = _patterns_csr(reads)
+        seed_opts = self._seed_options(min_length, strands, max_occurrences)
+        chain_opts = self._chain_options(max_gap, max_skew, gap_cost, min_score, max_matches)
+        m = offsets.size - 1
+        read_offsets = np.zeros(m + 1, dtype=np.uint64)
+        n_chains, n_matches = C.c_uint64(0), C.c_uint64(0)
+        request = (self._fm, _ptr(offsets), _ptr(data), m, C.byref(seed_opts), C.byref(chain_opts), _ptr(read_offsets))
+        check(self._L.gbwt_hip_fm_chains(*request, None, 0, C.byref(n_chains), None, None, 0, C.byref(n_matches)))   # the size query computes, the fill only copies
+        chains = np.zeros(max(1, n_chains.value), dtype=CHAIN_DTYPE)
+        match_offsets = np.zeros(n_chains.value + 1, dtype=np.uint64)
+        matches = np.zeros(max(1, n_matches.value), dtype=CHAIN_MATCH_DTYPE)
+        check(self._L.gbwt_hip_fm_chains(*request, chains.ctypes.data, chains.size, C.byref(n_chains), _ptr(match_offsets), matches.ctypes.data, matches.size, C.byref(n_matches)))
+        return read_offsets, chains[: n_chains.value], match_offsets, matches[: n_matches.value]
+
+    def chains_device(self, d_offsets, d_bytes, m, nbytes, min_length=1, strands=STRAND_BOTH, max_occurrences=1000, max_gap=0, max_skew=0, gap_cost=1, min_score=1, max_matches=0):
+        """gbwt_hip_fm_chains_device: a _lib.FmChainRows whose d_read_offsets[m + 1], d_chains[total_chains], d_match_offsets[total_chains + 1] and
+        d_matches[total_matches] stay in HBM until the next chains request."""
+        out = _lib.FmChainRows()
+        seed_opts = self._seed_options(min_length, strands, max_occurrences)
+        chain_opts = self._chain_options(max_gap, max_skew, gap_cost, min_score, max_matches)
+        check(self._L.gbwt_hip_fm_chains_device(self._fm, *self._device_patterns(d_offsets, d_bytes, m, nbytes), C.byref(seed_opts), C.byref(chain_opts), C.byref(out)))
+        return out
+
+    def last_chain_info(self):
+        """gbwt_hip_fm_last_chain_info as a dict: items, matches, skipped_items, pairs, chains, chain_matches, tile_matches, scratch bytes, phase times."""
+        info = _lib.FmChainInfo()
+        check(self._L.gbwt_hip_fm_last_chain_info(self._fm, C.byref(info)))
+        return _as_dict(info)
 
 
 class PathFMIndex(FMIndex):

@@ -350,6 +350,11 @@ gbwt_hip_status gbwt_hip_path_fm_index(const gbwt_hip_index *ix, gbwt_hip_worksp
         fm.index = ix;
         fm.path_ids.assign(path_ids, path_ids + n);
         fm.endmarker = endmarker;
+        // the segments of the chains: the rows of the text, each with its endmarker (sequences.hip counts it into the row)
+        fm.path_offsets.reserve((n + 1) * sizeof(uint64_t));
+        if (n) HIP_CHECK(hipMemcpyAsync(fm.path_offsets.ptr, text.d_line_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, fm.stream));
+        else HIP_CHECK(hipMemsetAsync(fm.path_offsets.ptr, 0, sizeof(uint64_t), fm.stream));
+        HIP_CHECK(hipStreamSynchronize(fm.stream));
         return GBWT_HIP_OK;
     });
     GBWT_HIP_GUARD_END

@@ -27,15 +27,17 @@ gbwt_hip_status check_request(const gbwt_hip_fm_index *fm, const uint64_t *offse
     gbwt_hip_status st = fm_check_patterns(offsets, bytes, m, on_host);
     if (st != GBWT_HIP_OK) return st;
     if (!opts) opts = &DEFAULT_OPTIONS;
-    if (opts->strands < 1 || opts->strands > 3) return fail(GBWT_HIP_BAD_ARGUMENT, "strands: 1 (forward), 2 (reverse) or 3 (both)");
-    if (opts->flags != 0 || opts->reserved != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags and reserved of the seed options must be 0");
+    st = fm_check_seed_options(*opts);
+    if (st != GBWT_HIP_OK) return st;
     if (graph && opts->max_occurrences == 0) return fail(GBWT_HIP_BAD_ARGUMENT, "graph positions of seeds need max_occurrences > 0: the tags are the hits");
     return fm_check_object(fm, graph ? FM_GRAPH : opts->max_occurrences != 0 ? FM_LOCATE : FM_COUNT, ix, ws, 0);
 }
 
-// The rows of a request into the object.  Exactly one of h_offsets / d_offsets; bytes: the read bytes behind d_bytes (the host form: offsets[m]).
-gbwt_hip_status seeds_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m, uint64_t bytes,
-                              const gbwt_hip_fm_seed_options &opts, bool graph, const gbwt_hip_index *ix, gbwt_hip_workspace *ws) {
+}  // namespace
+
+// The rows of a request into the object (fm_object.hpp)
+gbwt_hip_status gbwt_hip::fm_seeds_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m, uint64_t bytes,
+                                           const gbwt_hip_fm_seed_options &opts, bool graph, const gbwt_hip_index *ix, gbwt_hip_workspace *ws) {
     gbwt_hip_fm_seed_state &st = fm->seed;
     const bool hits = opts.max_occurrences != 0;
     if (h_offsets) {
@@ -174,6 +176,8 @@ gbwt_hip_status seeds_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, 
     }
 }
 
+namespace {
+
 gbwt_hip_fm_seed_rows rows_of(const gbwt_hip_fm_index *fm) {
     const gbwt_hip_fm_seed_state &st = fm->seed;
     return gbwt_hip_fm_seed_rows{st.read_offsets.as<uint64_t>(), st.seeds.as<gbwt_hip_fm_seed>(), st.with_hits ? st.hit_offsets.as<uint64_t>() : nullptr,
@@ -210,7 +214,7 @@ gbwt_hip_status host_request(gbwt_hip_fm_index *fm, bool graph, const gbwt_hip_i
     if (wants_hits && !total_hits) return fail(GBWT_HIP_BAD_ARGUMENT, "null total of the hits");
     if (wants_hits && seeds && !out_hit_offsets) return fail(GBWT_HIP_BAD_ARGUMENT, "null hit offsets (one more than the seeds)");
     gbwt_hip_status st = check_request(fm, offsets, bytes, m, true, opts, graph, ix, ws);
-    if (st == GBWT_HIP_OK) st = seeds_compute(fm, offsets, bytes, nullptr, nullptr, m, 0, *opts, graph, ix, ws);
+    if (st == GBWT_HIP_OK) st = fm_seeds_compute(fm, offsets, bytes, nullptr, nullptr, m, 0, *opts, graph, ix, ws);
     if (st != GBWT_HIP_OK) return st;
     return rows_to_host(fm, out_read_offsets, seeds, seed_capacity, total_seeds, out_hit_offsets, hits, hit_capacity, total_hits);
 }
@@ -220,7 +224,7 @@ gbwt_hip_status device_request(gbwt_hip_fm_index *fm, bool graph, const gbwt_hip
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     *out = gbwt_hip_fm_seed_rows{nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
     gbwt_hip_status st = check_request(fm, d_offsets, d_bytes, m, false, opts, graph, ix, ws);
-    if (st == GBWT_HIP_OK) st = seeds_compute(fm, nullptr, nullptr, d_offsets, static_cast<const uint8_t *>(d_bytes), m, bytes, *opts, graph, ix, ws);
+    if (st == GBWT_HIP_OK) st = fm_seeds_compute(fm, nullptr, nullptr, d_offsets, static_cast<const uint8_t *>(d_bytes), m, bytes, *opts, graph, ix, ws);
     if (st != GBWT_HIP_OK) return st;
     *out = rows_of(fm);
     return GBWT_HIP_OK;

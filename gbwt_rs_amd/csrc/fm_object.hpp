@@ -1,5 +1,6 @@
-// fm_object.hpp -- the FM-index object of the C ABI as its two translation units see it (capi_fm.hip: the build and count / locate / graph
-// positions; capi_fm_seeds.hip: the seeds of reads), and the checks of a request that both make before any device work.
+// fm_object.hpp -- the FM-index object of the C ABI as its translation units see it (capi_fm.hip: the build and count / locate / graph
+// positions; capi_fm_seeds.hip: the seeds of reads; capi_fm_chains.hip: their chains), and the checks of a request that they make before
+// any device work.
 #pragma once
 
 #include <string>
@@ -19,6 +20,18 @@ struct gbwt_hip_fm_seed_state {
     gbwt_hip_fm_seed_info info{};
 };
 
+// The rows of the last chains request of an object, and what it was
+struct gbwt_hip_fm_chain_state {
+    gbwt_hip::DeviceBuffer read_offsets, chains, match_offsets, matches;      // (reads given on the host lie in the seeds state)
+    // (the list stands under the buffers.  An FM-index is no part of gbwt_hip_memory_usage, which sums a handle and its
+    // workspaces, so nothing reports this sum yet; gbwt_hip_fm_last_chain_info reports the path offsets, which the object keeps for good)
+    uint64_t device_bytes() const { return gbwt_hip::bytes_of({&read_offsets, &chains, &match_offsets, &matches}); }
+    gbwt_hip::EventSet<6> ev{gbwt_hip::OnFirstUse{}};
+    gbwt_hip::RequestKey memo;
+    uint64_t m = 0, total_chains = 0, total_matches = 0;
+    gbwt_hip_fm_chain_info info{};
+};
+
 // One FM-index: what fm_layout.hpp describes in HBM, the rows of its last request, and -- for an index of paths -- what the graph-position
 // call needs to turn text positions into tags.  One host thread at a time.
 struct gbwt_hip_fm_index {
@@ -33,6 +46,7 @@ struct gbwt_hip_fm_index {
     const gbwt_hip_index *index = nullptr;
     std::vector<uint64_t> path_ids;
     int endmarker = 0;
+    gbwt_hip::DeviceBuffer path_offsets;                  // [path_ids.size() + 1] text offsets of the paths, each with its endmarker: the segments of the chains
     // the last request: patterns given on the host, ranges and occurrence counts, row offsets, positions, the row of every position, tags;
     // sorted_* / flag / rank / uoff / kept: a unique request; words: [0] flags, [1] backward steps
     gbwt_hip::DeviceBuffer q_offsets, q_bytes, ranges, occ, roff, positions, rows, tags, tmp_values, tmp_rows, sorted_values, sorted_rows, flag, rank, uoff, kept, temp, words;
@@ -42,6 +56,7 @@ struct gbwt_hip_fm_index {
     uint64_t last_m = 0, last_total = 0;
     gbwt_hip_fm_index_info info{};
     gbwt_hip_fm_seed_state seed;      // the last seeds request: rows of its own, beside those of the queries above
+    gbwt_hip_fm_chain_state chain;    // the last chains request: rows of its own, beside the seeds rows it was made from
     gbwt_hip::Stream stream{gbwt_hip::OnFirstUse{}};      // the last member: it goes first, before the buffers its work used
 };
 
@@ -71,5 +86,17 @@ inline gbwt_hip_status fm_check_object(const gbwt_hip_fm_index *fm, FmKind kind,
     }
     return GBWT_HIP_OK;
 }
+
+// The seed options as every request that takes them checks them, behind the reads and in front of the object
+inline gbwt_hip_status fm_check_seed_options(const gbwt_hip_fm_seed_options &opts) {
+    if (opts.strands < 1 || opts.strands > 3) return fail(GBWT_HIP_BAD_ARGUMENT, "strands: 1 (forward), 2 (reverse) or 3 (both)");
+    if (opts.flags != 0 || opts.reserved != 0) return fail(GBWT_HIP_BAD_ARGUMENT, "flags and reserved of the seed options must be 0");
+    return GBWT_HIP_OK;
+}
+
+// The rows of a seeds request into the object's seeds state (capi_fm_seeds.hip), for the requests that start with one.  Exactly one of
+// h_offsets / d_offsets; bytes: the read bytes behind d_bytes (the host form: offsets[m]).  The request has passed its checks.
+gbwt_hip_status fm_seeds_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m, uint64_t bytes,
+                                 const gbwt_hip_fm_seed_options &opts, bool graph, const gbwt_hip_index *ix, gbwt_hip_workspace *ws);
 
 }  // namespace gbwt_hip

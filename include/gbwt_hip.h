@@ -593,6 +593,72 @@ gbwt_hip_status gbwt_hip_fm_seeds_device(gbwt_hip_fm_index *fm, const uint64_t *
 gbwt_hip_status gbwt_hip_fm_seed_graph_positions_device(gbwt_hip_fm_index *fm, const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *d_offsets, const void *d_bytes,
                                                         uint64_t m, uint64_t bytes, const gbwt_hip_fm_seed_options *opts, gbwt_hip_fm_seed_rows *out);
 
+/* ---- Chains of seeds: colinear chaining of a read's hits -------------------------------------------------------------------
+ * Which placements of a read do its hits support, and how well?  An ITEM is one (read, strand) pair of a seeds request.  Every hit p of a
+ * seed [start, end) of the item is a MATCH (y = p, x = start, w = end - start): only the hits a seeds request with the same min_length,
+ * strands and max_occurrences reports (a seed with more occurrences contributes none).  The matches of an item are ordered by (y, x), and
+ * the index of a match is its place in that order.  max_matches (0: no limit) caps an item: one with more matches yields no chains and
+ * counts as skipped.  All of it is integer arithmetic: nothing is heuristic.
+ *
+ * SEGMENTS: on an index of a plain text every match has segment 0; on an index of paths the segment of a match is the rank k (in the
+ * path_ids the index was made with) of the path whose bases and endmarker hold y.  A chain never joins matches of different segments; a
+ * seed that runs through an endmarker belongs to the segment of its first byte.
+ * PRECEDENCE: match j may precede match i of the same item when both have one segment, dy = y_i - y_j and dx = x_i - x_j are in
+ * 1 .. max_gap, and d = |dy - dx| <= max_skew.
+ * SCORES: c(j, i) = f(j) + min(w_i, dx, dy) - gap_cost * d, signed.  f(i) = w_i and pred(i) = none unless some admissible j has
+ * c(j, i) > w_i: then f(i) is the largest such c and pred(i) the largest j that attains it.
+ * PEELING: the matches are visited by (f descending, index ascending).  An unused match i starts a chain and walks i, pred(i), .., marking
+ * each used and making it a member, until a match has no predecessor (base = 0) or its predecessor p is used (base = f(p); p is no
+ * member).  The chain's score is f(i) - base; it is reported when score >= max(min_score, 1), and its members stay used either way.
+ * ROWS: a read's row holds the chains of its forward strand, then those of its reverse strand, each in peeling order -- the first chain of
+ * an item is its best --; the members of a chain are listed by ascending index.  Coordinates on the reverse strand are those of the
+ * reverse-complemented read, as for seeds.
+ *
+ * A chains request is a seeds request with hits as text positions, followed by the chaining: afterwards the seeds rows of the object are
+ * those of that request, and gbwt_hip_fm_seeds with the same arguments computes nothing.  The chaining's scratch is a function of (hits,
+ * items); more than the free device memory is GBWT_HIP_CAPACITY with the bytes needed, before its first kernel; all of it is freed before
+ * the call returns.  A request with 2^31 or more hits is GBWT_HIP_UNSUPPORTED. */
+typedef struct {
+    uint32_t max_gap, max_skew;      /* 0: 5000 / 500 -- conventions, not tuned values */
+    uint32_t gap_cost, min_score;    /* gap_cost 0 is allowed (no penalty); min_score 0 counts as 1 */
+    uint64_t max_matches;            /* per (read, strand); 0: no limit */
+    uint32_t flags, reserved;        /* 0 */
+} gbwt_hip_fm_chain_options;         /* NULL = all zero */
+/* text_start / read_start: y / x of the first member; text_end / read_end: y + w / x + w of the last; matches: the members; path: the
+ * segment (0 on an index of a plain text) */
+typedef struct { uint64_t text_start, text_end; uint32_t read_start, read_end, score, matches, strand, path; } gbwt_hip_fm_chain;   /* 40 bytes */
+typedef struct { uint64_t y; uint32_t x, w; } gbwt_hip_fm_chain_match;                                                             /* 16 bytes */
+/* The last computed chains request of an object.  items: reads x strands; matches: those of the items not skipped; pairs: admissible
+ * (j, i) evaluated; chains / chain_matches: reported chains and their members; tile_matches: the most matches of an item that the DP
+ * kernel stages in LDS (larger items run over global memory; a constant of the build, set in every answer); path_offset_bytes: what an
+ * index of paths keeps for the segments (not part of index_bytes); HIP-event times: seeds_ms (0 where the seeds step was answered from
+ * the object's seeds rows), expand_ms, sort_ms, dp_ms, peel_ms, fill_ms. */
+typedef struct {
+    uint64_t requests, items, matches, skipped_items, pairs, chains, chain_matches, tile_matches, planned_scratch_bytes, peak_scratch_bytes, path_offset_bytes;
+    float seeds_ms, expand_ms, sort_ms, dp_ms, peel_ms, fill_ms;
+} gbwt_hip_fm_chain_info;
+gbwt_hip_status gbwt_hip_fm_last_chain_info(const gbwt_hip_fm_index *fm, gbwt_hip_fm_chain_info *out);
+
+/* Reads and seed options as gbwt_hip_fm_seeds takes them (max_occurrences == 0 is GBWT_HIP_BAD_ARGUMENT: chains need hits).
+ * out_read_offsets[m + 1], *total_chains and *total_matches always; chains == NULL (and matches == NULL) is the size query, and the call
+ * that repeats its request with buffers only copies.  out_match_offsets[*total_chains + 1] is written together with the chains.  A
+ * capacity that is too small is GBWT_HIP_CAPACITY with the totals set and nothing written.  Checked before any device work, in this
+ * order: null outputs; the reads; the seed options; the chain options (non-zero flags / reserved; max_gap or max_skew above 2^31 - 1;
+ * gap_cost x max_skew >= 2^31); then the object (a count-only index is GBWT_HIP_UNSUPPORTED). */
+gbwt_hip_status gbwt_hip_fm_chains(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, const gbwt_hip_fm_seed_options *seed_opts,
+                                   const gbwt_hip_fm_chain_options *chain_opts, uint64_t *out_read_offsets, gbwt_hip_fm_chain *chains, uint64_t chain_capacity, uint64_t *total_chains,
+                                   uint64_t *out_match_offsets, gbwt_hip_fm_chain_match *matches, uint64_t match_capacity, uint64_t *total_matches);
+/* The device form: the rows stay in HBM, owned by the object, until its next chains request. */
+typedef struct {
+    const uint64_t *d_read_offsets;              /* [m + 1] */
+    const gbwt_hip_fm_chain *d_chains;           /* [total_chains] */
+    const uint64_t *d_match_offsets;             /* [total_chains + 1] */
+    const gbwt_hip_fm_chain_match *d_matches;    /* [total_matches] */
+    uint64_t total_chains, total_matches, m;
+} gbwt_hip_fm_chain_rows;
+gbwt_hip_status gbwt_hip_fm_chains_device(gbwt_hip_fm_index *fm, const uint64_t *d_offsets, const void *d_bytes, uint64_t m, uint64_t bytes, const gbwt_hip_fm_seed_options *seed_opts,
+                                          const gbwt_hip_fm_chain_options *chain_opts, gbwt_hip_fm_chain_rows *out);
+
 /* ---- graph topology: weakly connected components, contig path selection -------------------------------------------------------------
  * GBZ::weakly_connected_components (src/gbz.rs:570-598; known answer src/gbz/tests.rs:503-518): the node ids of the graph that the GBWT
  * records describe, partitioned by "joined through an edge, whatever the orientations" (the successors and predecessors of both

@@ -18,6 +18,7 @@ than some 16 bases: every interval is refined, as on the other strand of a sampl
 
 The reference has no counterpart: no speed-up is stated."""
 import argparse
+import contextlib
 import json
 import os
 import shutil
@@ -46,16 +47,19 @@ def summary(result):
                                                                                  "idle_share")} for kind in KINDS}}
 
 
-def run(size="small", device=0, repeats=3, reads=READS):
+@contextlib.contextmanager
+def workload(size="small", device=0, reads=READS):
+    """The index and the three batches of reads on the device (tools/chain_bench.py measures the same): a dict with fm, n, ids, contig_ids,
+    generator_seconds, offsets and batches {kind: bytes}, the tensors on the device."""
     import torch
     import c4_bench as C4
     import gbwt_rs_amd as G
     from gbwt_rs_amd import dist as D
     from gbwt_rs_amd import synth as S
-    import bench
     p = dict(C4.SIZES[size])
     dev = torch.device("cuda", device)
     tmpdir = tempfile.mkdtemp(prefix="gbwt_seeds_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    opened = []
     try:
         path = os.path.join(tmpdir, "c4.gbz")
         t0 = time.perf_counter()
@@ -88,6 +92,19 @@ def run(size="small", device=0, repeats=3, reads=READS):
         random = letters[torch.randint(0, 4, (reads * LENGTH,), device=dev, generator=gen)].contiguous()
         offsets = (torch.arange(reads + 1, device=dev, dtype=torch.int64) * LENGTH).contiguous()
         torch.cuda.synchronize(dev)
+        opened.append(fm)
+        yield {"fm": fm, "n": n, "ids": ids, "contig_ids": contig_ids, "generator_seconds": gen_s, "offsets": offsets, "batches": dict(zip(KINDS, (sampled, substituted, random)))}
+    finally:
+        for fm in opened:
+            fm.close()
+        shutil.rmtree(tmpdir, ignore_errors=True)
+
+
+def run(size="small", device=0, repeats=3, reads=READS):
+    import gbwt_rs_amd as G
+    import bench
+    with workload(size, device, reads) as w:
+        fm, n, ids, contig_ids, gen_s, offsets = w["fm"], w["n"], w["ids"], w["contig_ids"], w["generator_seconds"], w["offsets"]
 
         def measured(d_bytes):
             runs = []
@@ -110,9 +127,9 @@ def run(size="small", device=0, repeats=3, reads=READS):
                     **{k: round(statistics.median(r[k] for r in runs), 4) for k in ("anchor_ms", "refine_ms", "emit_ms", "hits_ms")},
                     "scratch_bytes": int(last["peak_scratch_bytes"]), "scratch_bytes_per_read_byte": last["peak_scratch_bytes"] / (reads * LENGTH)}
 
-        batches = {kind: measured(d_bytes) for kind, d_bytes in zip(KINDS, (sampled, substituted, random))}
+        batches = {kind: measured(d_bytes) for kind, d_bytes in w["batches"].items()}
         info = fm.last_seed_info()
-        result = {
+        return {
             "tool": "seed_bench", "size": size,
             "workload": f"Synth.genome[{size} shape, labels 1..1024 bp, seed 42]: the first {len(ids)} of the {len(contig_ids)} paths of contig 'chr1', {n} positions; "
                         f"{reads} reads of {LENGTH} bytes per batch, both strands",
@@ -121,10 +138,6 @@ def run(size="small", device=0, repeats=3, reads=READS):
             "every_sampled_read_has_a_seed": batches["sampled"]["seeds_per_read"] >= 1,
             "source_fingerprint": bench.source_fingerprint(),
         }
-        fm.close()
-        return result
-    finally:
-        shutil.rmtree(tmpdir, ignore_errors=True)
 
 
 def main():
