@@ -471,7 +471,13 @@ gbwt_hip_status gbwt_hip_fm_build_text(int device, const void *text, uint64_t n,
 gbwt_hip_status gbwt_hip_fm_build_text_device(int device, const void *d_text, uint64_t n, int sentinel, const uint64_t *d_sa, uint32_t flags, void *stream, gbwt_hip_fm_index **out);
 /* The index of the text of paths: text and suffix array are those of gbwt_hip_path_suffix_array_device(path_ids, n, endmarker) on `ws`
  * (endmarker 0 .. 255: the tags count one behind every path).  The object remembers the handle, the path ids and the endmarker for
- * gbwt_hip_fm_graph_positions; it must be closed before the handle. */
+ * gbwt_hip_fm_graph_positions; it must be closed before the handle.
+ * path_ids may stand in any order and may name an id more than once: every entry of the list is a row of the text with its own endmarker,
+ * and two entries of one id are two copies of its bases -- a pattern occurs in both, their tags are equal, and the segment of a chain (its
+ * `path`, the rank in the list) and its text offsets alone tell them apart.  The endmarker may be a byte that is also a base (65): the text
+ * is what gbwt_hip_path_sequences writes, so a pattern or a seed can then occur across a path's end; such an occurrence is counted and
+ * located like any other, the tag of an occurrence that starts on an endmarker byte is 0 whatever the byte is, and a chain still never
+ * joins matches of different segments. */
 gbwt_hip_status gbwt_hip_path_fm_index(const gbwt_hip_index *index, gbwt_hip_workspace *ws, const uint64_t *path_ids, uint64_t n, int endmarker, uint32_t flags,
                                        gbwt_hip_fm_index **out);
 void gbwt_hip_fm_close(gbwt_hip_fm_index *fm);
@@ -501,7 +507,9 @@ gbwt_hip_status gbwt_hip_fm_info(const gbwt_hip_fm_index *fm, gbwt_hip_fm_index_
  * gbwt_hip_fm_graph_positions (an object of gbwt_hip_path_fm_index, with the handle it was made from and a workspace of it; anything else
  * is GBWT_HIP_BAD_ARGUMENT): the located positions go to gbwt_hip_tags_device on `ws` without leaving the device: row k = the tags of the
  * occurrences' first bases in SA order -- ((node << 11) | (orientation << 10)) + offset, 0 where an occurrence starts on an endmarker --,
- * or with unique == 1 the distinct tags ascending (sorted on the device; at most 2^31 - 1 positions in such a request).  Same protocol. */
+ * or with unique == 1 the distinct tags ascending (sorted on the device; at most 2^31 - 1 positions in such a request).  Same protocol.
+ * Any workspace of the handle serves, a different one in every call if need be, and requests for tags, bases or suffix arrays of other
+ * paths on that workspace between two calls change no answer: the call asks the tags family for the object's own path ids each time. */
 gbwt_hip_status gbwt_hip_fm_count(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, uint64_t *ranges);
 gbwt_hip_status gbwt_hip_fm_locate(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, uint64_t *out_offsets, uint64_t *positions, uint64_t capacity,
                                    uint64_t *total);
