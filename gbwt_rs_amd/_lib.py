@@ -160,6 +160,29 @@ class FmChainRows(C.Structure):
                 ("total_matches", C.c_uint64), ("m", C.c_uint64)]
 
 
+ALIGN_OK, ALIGN_WIDE, ALIGN_NONE = 0, 1, 2     # gbwt_hip_fm_alignment.status
+
+
+class FmAlignOptions(C.Structure):
+    _fields_ = [("band", C.c_uint32), ("max_width", C.c_uint32), ("max_alignments", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FmAlignment(C.Structure):
+    _fields_ = [("text_start", C.c_uint64), ("text_end", C.c_uint64)] + \
+               [(name, C.c_uint32) for name in ("chain", "edit_distance", "width", "status", "strand", "path")]
+
+
+class FmAlignInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("requests", "items", "chains", "alignments", "wide", "unreachable", "cells", "cigar_ops", "lds_alignments", "global_alignments",
+                                                "tile_bytes", "text_bytes", "planned_scratch_bytes", "peak_scratch_bytes")] + \
+               [(name, C.c_float) for name in ("chains_ms", "select_ms", "dp_ms", "trace_ms", "rows_ms", "reserved")]
+
+
+class FmAlignmentRows(C.Structure):
+    _fields_ = [("d_read_offsets", C.c_void_p), ("d_alignments", C.c_void_p), ("d_cigar_offsets", C.c_void_p), ("d_cigars", C.c_void_p), ("total_alignments", C.c_uint64),
+                ("total_cigars", C.c_uint64), ("m", C.c_uint64)]
+
+
 class ReferencePath(C.Structure):
     _fields_ = [("path_id", C.c_uint64), ("len", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint64)]
 
@@ -307,6 +330,13 @@ SIGNATURES = {
     "gbwt_hip_fm_last_chain_info": (_int, [_p, C.POINTER(FmChainInfo)]),
     "gbwt_hip_fm_chains": (_int, [_p, _p, _p, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmChainOptions), _p, _p, _u64, C.POINTER(_u64), _p, _p, _u64, C.POINTER(_u64)]),
     "gbwt_hip_fm_chains_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmChainOptions), C.POINTER(FmChainRows)]),
+    "gbwt_hip_fm_set_text": (_int, [_p, _p, _u64]),
+    "gbwt_hip_fm_set_text_device": (_int, [_p, _p, _u64, _p]),
+    "gbwt_hip_fm_keep_path_text": (_int, [_p, _p, _p]),
+    "gbwt_hip_fm_last_align_info": (_int, [_p, C.POINTER(FmAlignInfo)]),
+    "gbwt_hip_fm_alignments": (_int, [_p, _p, _p, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmChainOptions), C.POINTER(FmAlignOptions), _p, _p, _u64, C.POINTER(_u64), _p, _p, _u64,
+                                      C.POINTER(_u64)]),
+    "gbwt_hip_fm_alignments_device": (_int, [_p, _p, _p, _u64, _u64, C.POINTER(FmSeedOptions), C.POINTER(FmChainOptions), C.POINTER(FmAlignOptions), C.POINTER(FmAlignmentRows)]),
     "gbwt_hip_components_device": (_int, [_p, C.POINTER(Components)]),
     "gbwt_hip_weakly_connected_components": (_int, [_p, _p, _u64, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gbwt_hip_path_components": (_int, [_p, _p, _u64, _p]),

@@ -51,6 +51,15 @@ SEED_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8"), ("start", "<u4"), ("end", "
 CHAIN_DTYPE = np.dtype([("text_start", "<u8"), ("text_end", "<u8"), ("read_start", "<u4"), ("read_end", "<u4"), ("score", "<u4"), ("matches", "<u4"), ("strand", "<u4"),
                         ("path", "<u4")])                                                                   # gbwt_hip_fm_chain
 CHAIN_MATCH_DTYPE = np.dtype([("y", "<u8"), ("x", "<u4"), ("w", "<u4")])                                    # gbwt_hip_fm_chain_match
+ALIGNMENT_DTYPE = np.dtype([("text_start", "<u8"), ("text_end", "<u8"), ("chain", "<u4"), ("edit_distance", "<u4"), ("width", "<u4"), ("status", "<u4"), ("strand", "<u4"),
+                            ("path", "<u4")])                                                               # gbwt_hip_fm_alignment
+ALIGN_OK, ALIGN_WIDE, ALIGN_NONE = _lib.ALIGN_OK, _lib.ALIGN_WIDE, _lib.ALIGN_NONE
+_CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}
+
+
+def cigar_string(ops):
+    """The CIGAR of one alignment as text: `ops` are its u32 entries (length << 4) | op with BAM's codes I = 1, D = 2, '=' = 7, X = 8."""
+    return "".join(f"{int(v) >> 4}{_CIGAR_OPS[int(v) & 15]}" for v in ops)
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = _lib.STRAND_FORWARD, _lib.STRAND_REVERSE, _lib.STRAND_BOTH
 
 _COMPLEMENT = np.full(256, ord("N"), dtype=np.uint8)
@@ -184,15 +193,18 @@ class FMIndex:
         self._owner = owner                                # a path-level index: the GBZ it asks for tags, kept alive
 
     @classmethod
-    def from_text(cls, data, sentinel=0, device=0, count_only=False):
+    def from_text(cls, data, sentinel=0, device=0, count_only=False, keep_text=False):
         """The index of any bytes (gbwt_hip_fm_build_text): the suffix array is built on the device as suffix_array_text builds it.
-        count_only: no suffix array is kept, locate is refused."""
+        count_only: no suffix array is kept, locate is refused.  keep_text: the object keeps the text as well (set_text), for alignments."""
         text = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
         if text.ndim != 1:
             raise ValueError("data must be one-dimensional")
         handle = C.c_void_p()
         check(_lib.lib().gbwt_hip_fm_build_text(device, _ptr(text), text.size, int(sentinel), _lib.FM_COUNT_ONLY if count_only else 0, C.byref(handle)))
-        return cls(handle, device)
+        fm = cls(handle, device)
+        if keep_text:
+            fm.set_text(text)
+        return fm
 
     @classmethod
     def from_device(cls, d_text, n, sentinel=0, d_sa=None, device=0, count_only=False, stream=None):
@@ -212,6 +224,14 @@ class FMIndex:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+    def set_text(self, data):
+        """gbwt_hip_fm_set_text: the object keeps a copy of the text it was built from in HBM, which alignments() reads.  A text of another
+        length is BAD_ARGUMENT, one with another byte histogram INVALID_DATA; a second call replaces the first."""
+        text = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        if text.ndim != 1:
+            raise ValueError("data must be one-dimensional")
+        check(self._L.gbwt_hip_fm_set_text(self._fm, _ptr(text), text.size))
 
     def info(self):
         """gbwt_hip_fm_info as a dict: n, sigma, block_rows, blocks, primary, index_bytes, ..., the build's phase times and the last query's."""
@@ -352,9 +372,65 @@ class FMIndex:
         check(self._L.gbwt_hip_fm_last_chain_info(self._fm, C.byref(info)))
         return _as_dict(info)
 
+    @staticmethod
+    def _align_options(band, max_width, max_alignments):
+        values = [int(v) for v in (band, max_width, max_alignments)]
+        if any(v < 0 for v in values) or any(v >= 1 << 32 for v in values[:2]):
+            raise ValueError("band and max_width are 32-bit counts, max_alignments a count")
+        return _lib.FmAlignOptions(*values, 0, 0)
+
+    def alignments(self, reads, min_length=1, strands=STRAND_BOTH, max_occurrences=1000, max_gap=0, max_skew=0, gap_cost=1, min_score=1, max_matches=0, band=16, max_width=0,
+                   max_alignments=0):
+        """The alignments of every read's chains (gbwt_hip_fm_alignments): (read_offsets[m + 1], alignments, cigar_offsets, cigars).  The
+        chains are those of chains(reads, <the same seed and chain keywords>); per (read, strand) the first max_alignments of them (0: all) are
+        aligned to the kept text (set_text, from_text(keep_text=True), PathFMIndex.keep_text) by a banded edit distance: `band` diagonals
+        on either side of the chain's own, at most max_width (0: 256) in all.  `alignments` is a structured array of ALIGNMENT_DTYPE -- status
+        ALIGN_OK, ALIGN_WIDE (the band is wider than max_width) or ALIGN_NONE (no end inside the band) --, row k of it the alignments of read k,
+        forward strand first, in chain order; row a of (cigar_offsets, cigars) holds the CIGAR of alignment a as u32 entries (cigar_string)."""
+        offsets, data = _patterns_csr(reads)
+        seed_opts = self._seed_options(min_length, strands, max_occurrences)
+        chain_opts = self._chain_options(max_gap, max_skew, gap_cost, min_score, max_matches)
+        align_opts = self._align_options(band, max_width, max_alignments)
+        m = offsets.size - 1
+        read_offsets = np.zeros(m + 1, dtype=np.uint64)
+        n_alignments, n_cigars = C.c_uint64(0), C.c_uint64(0)
+        request = (self._fm, _ptr(offsets), _ptr(data), m, C.byref(seed_opts), C.byref(chain_opts), C.byref(align_opts), _ptr(read_offsets))
+        check(self._L.gbwt_hip_fm_alignments(*request, None, 0, C.byref(n_alignments), None, None, 0, C.byref(n_cigars)))   # the size query computes, the fill only copies
+        alignments = np.zeros(max(1, n_alignments.value), dtype=ALIGNMENT_DTYPE)
+        cigar_offsets = np.zeros(n_alignments.value + 1, dtype=np.uint64)
+        cigars = np.zeros(max(1, n_cigars.value), dtype=np.uint32)
+        check(self._L.gbwt_hip_fm_alignments(*request, alignments.ctypes.data, alignments.size, C.byref(n_alignments), _ptr(cigar_offsets), cigars.ctypes.data, cigars.size,
+                                             C.byref(n_cigars)))
+        return read_offsets, alignments[: n_alignments.value], cigar_offsets, cigars[: n_cigars.value]
+
+    def alignments_device(self, d_offsets, d_bytes, m, nbytes, min_length=1, strands=STRAND_BOTH, max_occurrences=1000, max_gap=0, max_skew=0, gap_cost=1, min_score=1, max_matches=0,
+                          band=16, max_width=0, max_alignments=0):
+        """gbwt_hip_fm_alignments_device: a _lib.FmAlignmentRows whose d_read_offsets[m + 1], d_alignments[total_alignments],
+        d_cigar_offsets[total_alignments + 1] and d_cigars[total_cigars] stay in HBM until the next alignments request."""
+        out = _lib.FmAlignmentRows()
+        seed_opts = self._seed_options(min_length, strands, max_occurrences)
+        chain_opts = self._chain_options(max_gap, max_skew, gap_cost, min_score, max_matches)
+        align_opts = self._align_options(band, max_width, max_alignments)
+        check(self._L.gbwt_hip_fm_alignments_device(self._fm, *self._device_patterns(d_offsets, d_bytes, m, nbytes), C.byref(seed_opts), C.byref(chain_opts), C.byref(align_opts),
+                                                    C.byref(out)))
+        return out
+
+    def last_align_info(self):
+        """gbwt_hip_fm_last_align_info as a dict: items, chains, alignments, wide, unreachable, cells, cigar_ops, lds_alignments,
+        global_alignments, tile_bytes, text_bytes, scratch bytes, phase times."""
+        info = _lib.FmAlignInfo()
+        check(self._L.gbwt_hip_fm_last_align_info(self._fm, C.byref(info)))
+        return _as_dict(info, skip_reserved=True)
+
 
 class PathFMIndex(FMIndex):
     """The FM-index of the text of paths of a GBZ (GBZ.fm_index): FMIndex, and the graph positions of the occurrences."""
+
+    def keep_text(self):
+        """gbwt_hip_fm_keep_path_text: the object keeps the text of its paths -- asked of the bases family again and copied on the device --,
+        which alignments() reads."""
+        g = self._owner
+        check(self._L.gbwt_hip_fm_keep_path_text(self._fm, g._h, g._ws))
 
     def graph_positions_csr(self, patterns, unique=False):
         """(offsets[m + 1], tags): row k holds the tags -- ((node << 11) | (orientation << 10)) + offset, 0 on an endmarker -- of the first
@@ -1326,15 +1402,19 @@ class GBZ(GBWT):
         check(self._L.gbwt_hip_write_suffix_array(self._h, self._ws, os.fsencode(base), C.byref(runs)))
         return runs.value
 
-    def fm_index(self, path_ids, endmarker=0, count_only=False):
+    def fm_index(self, path_ids, endmarker=0, count_only=False, keep_text=False):
         """The FM-index of the text path_sequences(path_ids, FORWARD, endmarker) returns (gbwt_hip_path_fm_index): a PathFMIndex, built on the
-        device from the text and suffix array of suffix_array_device(path_ids, endmarker).  endmarker: a byte value, not None."""
+        device from the text and suffix array of suffix_array_device(path_ids, endmarker).  endmarker: a byte value, not None.  keep_text:
+        the object keeps the text as well (PathFMIndex.keep_text), for alignments."""
         ids = np.ascontiguousarray(path_ids, dtype=np.uint64)
         if endmarker is None:
             raise ValueError("an FM-index of paths needs an endmarker: the tags of the text count one behind every path")
         handle = C.c_void_p()
         check(self._L.gbwt_hip_path_fm_index(self._h, self._ws, _ptr(ids), ids.size, self._endmarker(endmarker), _lib.FM_COUNT_ONLY if count_only else 0, C.byref(handle)))
-        return PathFMIndex(handle, self._device, owner=self)
+        fm = PathFMIndex(handle, self._device, owner=self)
+        if keep_text:
+            fm.keep_text()
+        return fm
 
     def last_suffix_array_info(self):
         """The last suffix array built on this workspace (gbwt_hip_last_suffix_array_info): a dict -- n, rounds, active (the active set behind

@@ -24,6 +24,14 @@ constexpr gbwt_hip_fm_chain_options DEFAULT_CHAIN_OPTIONS{0, 0, 0, 0, 0, 0, 0};
 // The checks that answer before a device is touched: the reads, the seed options, the chain options, then the object
 gbwt_hip_status check_request(const gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, bool on_host, const gbwt_hip_fm_seed_options *&seed_opts,
                               const gbwt_hip_fm_chain_options *&chain_opts) {
+    const gbwt_hip_status st = fm_check_chain_request(offsets, bytes, m, on_host, seed_opts, chain_opts);
+    return st != GBWT_HIP_OK ? st : fm_check_object(fm, FM_LOCATE, nullptr, nullptr, 0);
+}
+
+}  // namespace
+
+gbwt_hip_status gbwt_hip::fm_check_chain_request(const uint64_t *offsets, const void *bytes, uint64_t m, bool on_host, const gbwt_hip_fm_seed_options *&seed_opts,
+                                                 const gbwt_hip_fm_chain_options *&chain_opts) {
     gbwt_hip_status st = fm_check_patterns(offsets, bytes, m, on_host);
     if (st != GBWT_HIP_OK) return st;
     if (!seed_opts) seed_opts = &DEFAULT_SEED_OPTIONS;
@@ -35,8 +43,10 @@ gbwt_hip_status check_request(const gbwt_hip_fm_index *fm, const uint64_t *offse
     if (chain_opts->max_gap > FM_CHAIN_MAX_OPTION || chain_opts->max_skew > FM_CHAIN_MAX_OPTION) return fail(GBWT_HIP_BAD_ARGUMENT, "max_gap and max_skew: at most 2^31 - 1");
     const FmChainParams P = fm_chain_params(chain_opts->max_gap, chain_opts->max_skew, chain_opts->gap_cost, chain_opts->min_score);
     if (uint64_t(P.gap_cost) * P.max_skew > FM_CHAIN_MAX_OPTION) return fail(GBWT_HIP_BAD_ARGUMENT, "gap_cost x max_skew must stay below 2^31");
-    return fm_check_object(fm, FM_LOCATE, nullptr, nullptr, 0);
+    return GBWT_HIP_OK;
 }
+
+namespace {
 
 // The chains of the seeds rows the object holds, into its chains state
 gbwt_hip_status chains_of_seeds(gbwt_hip_fm_index *fm, const gbwt_hip_fm_seed_options &seed_opts, const gbwt_hip_fm_chain_options &chain_opts, float seeds_ms) {
@@ -139,9 +149,11 @@ gbwt_hip_status chains_of_seeds(gbwt_hip_fm_index *fm, const gbwt_hip_fm_seed_op
     }
 }
 
+}  // namespace
+
 // A seeds request with hits as text positions through the object's seeds state and memo, then the chaining.  Exactly one of h_offsets / d_offsets.
-gbwt_hip_status chains_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m, uint64_t bytes,
-                               const gbwt_hip_fm_seed_options &seed_opts, const gbwt_hip_fm_chain_options &chain_opts) {
+gbwt_hip_status gbwt_hip::fm_chains_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m,
+                                            uint64_t bytes, const gbwt_hip_fm_seed_options &seed_opts, const gbwt_hip_fm_chain_options &chain_opts) {
     gbwt_hip_fm_chain_state &st = fm->chain;
     const std::initializer_list<int64_t> params = {seed_opts.min_length, seed_opts.strands, static_cast<int64_t>(seed_opts.max_occurrences), static_cast<int64_t>(m),
                                                    chain_opts.max_gap, chain_opts.max_skew, chain_opts.gap_cost, chain_opts.min_score, static_cast<int64_t>(chain_opts.max_matches)};
@@ -156,6 +168,8 @@ gbwt_hip_status chains_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets,
     if (h_offsets) st.memo.store({{h_offsets, (m + 1) * sizeof(uint64_t)}, {h_bytes, h_offsets[m]}}, params);
     return GBWT_HIP_OK;
 }
+
+namespace {
 
 gbwt_hip_fm_chain_rows rows_of(const gbwt_hip_fm_index *fm) {
     const gbwt_hip_fm_chain_state &st = fm->chain;
@@ -186,7 +200,7 @@ gbwt_hip_status gbwt_hip_fm_chains(gbwt_hip_fm_index *fm, const uint64_t *offset
     if (!total_chains || !total_matches || !out_read_offsets) return fail(GBWT_HIP_BAD_ARGUMENT, "null totals / read offsets");
     if (chains && !out_match_offsets) return fail(GBWT_HIP_BAD_ARGUMENT, "null match offsets (one more than the chains)");
     gbwt_hip_status st = check_request(fm, offsets, bytes, m, true, seed_opts, chain_opts);
-    if (st == GBWT_HIP_OK) st = chains_compute(fm, offsets, bytes, nullptr, nullptr, m, 0, *seed_opts, *chain_opts);
+    if (st == GBWT_HIP_OK) st = fm_chains_compute(fm, offsets, bytes, nullptr, nullptr, m, 0, *seed_opts, *chain_opts);
     if (st != GBWT_HIP_OK) return st;
     const gbwt_hip_fm_chain_rows rows = rows_of(fm);
     *total_chains = rows.total_chains;
@@ -212,7 +226,7 @@ gbwt_hip_status gbwt_hip_fm_chains_device(gbwt_hip_fm_index *fm, const uint64_t 
     if (!out) return fail(GBWT_HIP_BAD_ARGUMENT, "null output");
     *out = gbwt_hip_fm_chain_rows{nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
     gbwt_hip_status st = check_request(fm, d_offsets, d_bytes, m, false, seed_opts, chain_opts);
-    if (st == GBWT_HIP_OK) st = chains_compute(fm, nullptr, nullptr, d_offsets, static_cast<const uint8_t *>(d_bytes), m, bytes, *seed_opts, *chain_opts);
+    if (st == GBWT_HIP_OK) st = fm_chains_compute(fm, nullptr, nullptr, d_offsets, static_cast<const uint8_t *>(d_bytes), m, bytes, *seed_opts, *chain_opts);
     if (st != GBWT_HIP_OK) return st;
     *out = rows_of(fm);
     return GBWT_HIP_OK;

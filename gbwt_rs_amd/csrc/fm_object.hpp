@@ -1,6 +1,6 @@
 // fm_object.hpp -- the FM-index object of the C ABI as its translation units see it (capi_fm.hip: the build and count / locate / graph
-// positions; capi_fm_seeds.hip: the seeds of reads; capi_fm_chains.hip: their chains), and the checks of a request that they make before
-// any device work.
+// positions; capi_fm_seeds.hip: the seeds of reads; capi_fm_chains.hip: their chains; capi_fm_align.hip: the kept text and the alignments
+// of the chains), and the checks of a request that they make before any device work.
 #pragma once
 
 #include <string>
@@ -32,6 +32,17 @@ struct gbwt_hip_fm_chain_state {
     gbwt_hip_fm_chain_info info{};
 };
 
+// The rows of the last alignments request of an object, and what it was
+struct gbwt_hip_fm_align_state {
+    gbwt_hip::DeviceBuffer q_offsets, q_bytes;                 // reads given on the host: a copy of its own, whatever the seeds state holds by now
+    gbwt_hip::DeviceBuffer read_offsets, alignments, cigar_offsets, cigars;
+    uint64_t device_bytes() const { return gbwt_hip::bytes_of({&q_offsets, &q_bytes, &read_offsets, &alignments, &cigar_offsets, &cigars}); }
+    gbwt_hip::EventSet<4> ev{gbwt_hip::OnFirstUse{}};
+    gbwt_hip::RequestKey memo;
+    uint64_t m = 0, total_alignments = 0, total_cigars = 0;
+    gbwt_hip_fm_align_info info{};
+};
+
 // One FM-index: what fm_layout.hpp describes in HBM, the rows of its last request, and -- for an index of paths -- what the graph-position
 // call needs to turn text positions into tags.  One host thread at a time.
 struct gbwt_hip_fm_index {
@@ -47,6 +58,9 @@ struct gbwt_hip_fm_index {
     std::vector<uint64_t> path_ids;
     int endmarker = 0;
     gbwt_hip::DeviceBuffer path_offsets;                  // [path_ids.size() + 1] text offsets of the paths, each with its endmarker: the segments of the chains
+    // the text, where the caller gave it to the object (gbwt_hip_fm_set_text, gbwt_hip_fm_keep_path_text): what the alignments read
+    gbwt_hip::DeviceBuffer text;
+    bool has_text = false;
     // the last request: patterns given on the host, ranges and occurrence counts, row offsets, positions, the row of every position, tags;
     // sorted_* / flag / rank / uoff / kept: a unique request; words: [0] flags, [1] backward steps
     gbwt_hip::DeviceBuffer q_offsets, q_bytes, ranges, occ, roff, positions, rows, tags, tmp_values, tmp_rows, sorted_values, sorted_rows, flag, rank, uoff, kept, temp, words;
@@ -57,6 +71,7 @@ struct gbwt_hip_fm_index {
     gbwt_hip_fm_index_info info{};
     gbwt_hip_fm_seed_state seed;      // the last seeds request: rows of its own, beside those of the queries above
     gbwt_hip_fm_chain_state chain;    // the last chains request: rows of its own, beside the seeds rows it was made from
+    gbwt_hip_fm_align_state align;    // the last alignments request: rows of its own, beside the chains rows it was made from
     gbwt_hip::Stream stream{gbwt_hip::OnFirstUse{}};      // the last member: it goes first, before the buffers its work used
 };
 
@@ -98,5 +113,13 @@ inline gbwt_hip_status fm_check_seed_options(const gbwt_hip_fm_seed_options &opt
 // h_offsets / d_offsets; bytes: the read bytes behind d_bytes (the host form: offsets[m]).  The request has passed its checks.
 gbwt_hip_status fm_seeds_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m, uint64_t bytes,
                                  const gbwt_hip_fm_seed_options &opts, bool graph, const gbwt_hip_index *ix, gbwt_hip_workspace *ws);
+
+// The checks of a chains request in front of the object (capi_fm_chains.hip): the reads, the seed options, the chain options.  Null
+// options become the defaults
+gbwt_hip_status fm_check_chain_request(const uint64_t *offsets, const void *bytes, uint64_t m, bool on_host, const gbwt_hip_fm_seed_options *&seed_opts,
+                                       const gbwt_hip_fm_chain_options *&chain_opts);
+// The rows of a chains request into the object's chains state, through its memo (capi_fm_chains.hip), for the requests that start with one
+gbwt_hip_status fm_chains_compute(gbwt_hip_fm_index *fm, const uint64_t *h_offsets, const void *h_bytes, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t m, uint64_t bytes,
+                                  const gbwt_hip_fm_seed_options &seed_opts, const gbwt_hip_fm_chain_options &chain_opts);
 
 }  // namespace gbwt_hip

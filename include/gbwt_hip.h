@@ -667,6 +667,92 @@ typedef struct {
 gbwt_hip_status gbwt_hip_fm_chains_device(gbwt_hip_fm_index *fm, const uint64_t *d_offsets, const void *d_bytes, uint64_t m, uint64_t bytes, const gbwt_hip_fm_seed_options *seed_opts,
                                           const gbwt_hip_fm_chain_options *chain_opts, gbwt_hip_fm_chain_rows *out);
 
+/* ---- Alignments of chains: banded edit distance and CIGARs ----------------------------------------------------------------
+ * A chain says which placement of a read its exact matches support; an alignment says how the read lies there: where it starts and ends
+ * in the text, how many edits, and the CIGAR.  Integer arithmetic, nothing heuristic.  It needs the text, which the builds do not keep:
+ *
+ * THE TEXT.  gbwt_hip_fm_set_text / gbwt_hip_fm_set_text_device give the object a copy of n bytes in HBM (n != the n of the index:
+ * GBWT_HIP_BAD_ARGUMENT; a byte histogram that is not the index's -- its code table and C -- : GBWT_HIP_INVALID_DATA.  One kernel pass: it
+ * catches a wrong text cheaply and is no proof of equality).  gbwt_hip_fm_keep_path_text, on an object of gbwt_hip_path_fm_index with the
+ * handle it was made from and a workspace of it (the checks of gbwt_hip_fm_graph_positions), asks the bases family on `ws` for the
+ * object's own path ids with its endmarker and copies the text device to device.  A second call replaces the text; gbwt_hip_fm_close
+ * frees it.  The text is no part of index_bytes / planned_index_bytes: gbwt_hip_fm_last_align_info reports it as text_bytes.
+ *
+ * WHICH CHAINS.  Per item (read, strand) the first max_alignments chains in peeling order (0: all).  A read's row holds the alignments of
+ * its forward strand, then those of its reverse strand, in chain order; every considered chain yields exactly one row, whatever its status.
+ * THE READ AND THE TEXT.  P[0, L) is the read as the strand of the chain sees it (the reverse complement is computed on the device); T is
+ * the kept text.  Bytes are bytes: no case folding, and N == N.
+ * BOUNDS.  [lo, hi) = [0, n) on an index of a plain text; on an index of paths the bases of the chain's `path` without its endmarker:
+ * lo = path_offsets[path], hi = path_offsets[path + 1] - 1.  An alignment never touches an endmarker byte, whatever its value.
+ * THE BAND.  A member (y, x, w) of the chain lies on the diagonal d = y - x (signed 64-bit).  d0 = min d - band, d1 = max d + band,
+ * W = d1 - d0 + 1.  W > max_width: status GBWT_HIP_ALIGN_WIDE, nothing is computed, the CIGAR row is empty.
+ * CELLS.  H(i, j) for 0 <= i <= L and j = i + d, d0 <= d <= d1; only cells with lo <= j <= hi exist, every other one is unreachable.
+ * H(0, j) = 0 for every existing cell of row 0: the start in the text is free.  For i >= 1, H(i, j) is the smallest candidate that comes
+ * from an existing, reachable cell: the diagonal H(i - 1, j - 1) + (P[i - 1] != T[j - 1]); the insertion (a read byte without a text
+ * byte) H(i - 1, j) + 1; the deletion (a text byte without a read byte) H(i, j - 1) + 1.  The direction of the cell is the first of
+ * (diagonal, insertion, deletion) that attains the minimum; a cell without a candidate is unreachable.
+ * THE RESULT.  edit_distance = the smallest H(L, j) over the band, text_end = the smallest j that attains it.  No reachable cell in row L
+ * (the read overhangs its path by more than the band allows): status GBWT_HIP_ALIGN_NONE, edit_distance 0xFFFFFFFF, text_start =
+ * text_end = 0, an empty CIGAR row.
+ * THE CIGAR.  The walk back starts at (L, text_end) and follows the directions until i == 0, where text_start = j.  The free start means
+ * that no leading deletion occurs, the smallest end that no trailing one does.  The operations stand in read order, run-length encoded as
+ * u32 = (length << 4) | op with BAM's codes: I = 1, D = 2, '=' = 7, X = 8.
+ *
+ * An alignments request is a chains request followed by the alignment: afterwards the chains rows and the seeds rows of the object are
+ * those of that request, and gbwt_hip_fm_chains / gbwt_hip_fm_seeds with the same arguments compute nothing.  The alignment's scratch is a
+ * function of (items, considered chains, the directions that do not fit the LDS tile, the CIGAR bound of 2 L entries per computed
+ * alignment); more than the free device memory is GBWT_HIP_CAPACITY with the bytes needed, before the first kernel that aligns; all of it
+ * is freed before the call returns.  A computed alignment of a read of 2^28 bytes or more is GBWT_HIP_UNSUPPORTED. */
+gbwt_hip_status gbwt_hip_fm_set_text(gbwt_hip_fm_index *fm, const void *text, uint64_t n);
+gbwt_hip_status gbwt_hip_fm_set_text_device(gbwt_hip_fm_index *fm, const void *d_text, uint64_t n, void *stream);
+gbwt_hip_status gbwt_hip_fm_keep_path_text(gbwt_hip_fm_index *fm, const gbwt_hip_index *index, gbwt_hip_workspace *ws);
+
+typedef struct {
+    uint32_t band, max_width;        /* band is taken as given (0: the chain's own diagonals); max_width 0: 256; both at most 1024 */
+    uint64_t max_alignments;         /* per (read, strand); 0: all chains */
+    uint32_t flags, reserved;        /* 0 */
+} gbwt_hip_fm_align_options;         /* 24 bytes; NULL = {16, 256, 0, 0, 0} */
+/* chain: the index of the chain in the chains rows of the same request; width: W, set for every status */
+typedef struct { uint64_t text_start, text_end; uint32_t chain, edit_distance, width, status, strand, path; } gbwt_hip_fm_alignment;  /* 40 bytes */
+#define GBWT_HIP_ALIGN_OK 0u
+#define GBWT_HIP_ALIGN_WIDE 1u
+#define GBWT_HIP_ALIGN_NONE 2u
+/* The last computed alignments request of an object.  items: reads x strands; chains: those considered; alignments: the rows (one per
+ * considered chain); wide / unreachable: rows of status WIDE / NONE; cells: the sum of (L + 1) x W over the computed ones (every status
+ * but WIDE); cigar_ops: CIGAR entries; lds_alignments / global_alignments: computed alignments whose directions went to the LDS tile / to
+ * scratch in HBM; tile_bytes: the tile -- directions of L x ceil(W / 16) x 4 bytes fit up to it -- and text_bytes: the kept text; both
+ * are set in every answer; HIP-event times: chains_ms (0 where the chains step was answered from the object's chains rows), select_ms
+ * (the considered chains, their bands and sizes), dp_ms, trace_ms (0: the walk back runs inside the DP kernel and is part of dp_ms),
+ * rows_ms. */
+typedef struct {
+    uint64_t requests, items, chains, alignments, wide, unreachable, cells, cigar_ops, lds_alignments, global_alignments, tile_bytes, text_bytes, planned_scratch_bytes,
+        peak_scratch_bytes;
+    float chains_ms, select_ms, dp_ms, trace_ms, rows_ms, reserved;
+} gbwt_hip_fm_align_info;
+gbwt_hip_status gbwt_hip_fm_last_align_info(const gbwt_hip_fm_index *fm, gbwt_hip_fm_align_info *out);
+
+/* Reads, seed options and chain options as gbwt_hip_fm_chains takes them.  out_read_offsets[m + 1], *total_alignments and *total_cigars
+ * always; alignments == NULL (and cigars == NULL) is the size query, and the call that repeats its request with buffers only copies.
+ * out_cigar_offsets[*total_alignments + 1] is written together with the alignments.  A capacity that is too small is GBWT_HIP_CAPACITY
+ * with the totals set and nothing written.  Checked before any device work, in this order: null outputs; the reads; the seed options; the
+ * chain options; the align options (non-zero flags / reserved; max_width or band above 1024); then the object (a count-only index is
+ * GBWT_HIP_UNSUPPORTED, and so is one without a text: see gbwt_hip_fm_set_text and gbwt_hip_fm_keep_path_text). */
+gbwt_hip_status gbwt_hip_fm_alignments(gbwt_hip_fm_index *fm, const uint64_t *offsets, const void *bytes, uint64_t m, const gbwt_hip_fm_seed_options *seed_opts,
+                                       const gbwt_hip_fm_chain_options *chain_opts, const gbwt_hip_fm_align_options *align_opts, uint64_t *out_read_offsets,
+                                       gbwt_hip_fm_alignment *alignments, uint64_t capacity, uint64_t *total_alignments, uint64_t *out_cigar_offsets, uint32_t *cigars,
+                                       uint64_t cigar_capacity, uint64_t *total_cigars);
+/* The device form: the rows stay in HBM, owned by the object, until its next alignments request. */
+typedef struct {
+    const uint64_t *d_read_offsets;              /* [m + 1] */
+    const gbwt_hip_fm_alignment *d_alignments;   /* [total_alignments] */
+    const uint64_t *d_cigar_offsets;             /* [total_alignments + 1] */
+    const uint32_t *d_cigars;                    /* [total_cigars] */
+    uint64_t total_alignments, total_cigars, m;
+} gbwt_hip_fm_alignment_rows;
+gbwt_hip_status gbwt_hip_fm_alignments_device(gbwt_hip_fm_index *fm, const uint64_t *d_offsets, const void *d_bytes, uint64_t m, uint64_t bytes,
+                                              const gbwt_hip_fm_seed_options *seed_opts, const gbwt_hip_fm_chain_options *chain_opts, const gbwt_hip_fm_align_options *align_opts,
+                                              gbwt_hip_fm_alignment_rows *out);
+
 /* ---- graph topology: weakly connected components, contig path selection -------------------------------------------------------------
  * GBZ::weakly_connected_components (src/gbz.rs:570-598; known answer src/gbz/tests.rs:503-518): the node ids of the graph that the GBWT
  * records describe, partitioned by "joined through an edge, whatever the orientations" (the successors and predecessors of both
